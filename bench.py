@@ -19,7 +19,14 @@ Protocol (state-independent by construction -- the cost of a sweep depends on ho
      what a user sees for the first B iterations);  B is a property of the workload, NOT of --warmup;
   2. `--warmup W` untimed iterations;  3. exactly `--steps K` timed iterations -> `value` (settled chains).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload HL] [--chains C] [--burnin B] [--no-cpu]
+A plain run (no --full) is lean: it has no burn-in of its own -- the chains settle during its `--warmup W` iterations, which start
+from the random start (an explicit `--burnin B` puts the burn-in back) -- then it times the `--steps K` iterations and prints the
+result line, and with `--dump-outputs DIR` what the last timed iteration computed, as .npy files.  `--full` is the whole protocol
+above plus the legs that run on their own after the timed region: the oracle parity check, the latency form, one chain alone and
+the CPU baseline (`--no-parity`, `--no-latency-form`, `--no-cpu` drop one of them again).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload HL] [--chains C] [--burnin B] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu] [--no-parity] [--no-latency-form] ...
 
 For N > 1 the driver launches this file under torch.distributed.run, one rank per GPU; chains are independent (no
 data-path collective, scaling: weak) and the retained allocation samples of the timed iterations are all-gathered
@@ -268,6 +275,36 @@ def cpu_baseline(w, scale, states, budget_s):
                       f"chain of the GPU run; 1 probe iteration alone first ({time.perf_counter() - t0:.0f} s of wall time in total)"}
 
 
+DUMP_CHAINS = 64                 # chains whose allocations and Gibbs state --dump-outputs writes (a fixed, seeded sample)
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, g, res, last_sample, seed):
+    """What a caller of the timed path receives after its last step, as DIR/<name>.npy (float32 / float64): the sweep's results
+    for every chain (pmdi_gibbs_results: picked particle, log-weights, the counters the oracle also keeps) and, for a seeded sample
+    of chains, the retained allocation sample (pmdi_gibbs_pack_samples) and the Gibbs state (pmdi_gibbs_get).  Written before the
+    --full legs, which step the chains further."""
+    C, P = res["logweight"].shape
+    pick = np.sort(np.random.default_rng(seed).choice(C, size=min(C, DUMP_CHAINS), replace=False))
+    lw = res["logweight"] if C * P * 8 <= DUMP_BYTES // 2 else res["logweight"][pick]
+    states = [g.get(int(c)) for c in pick]
+    out = {"p_star": res["p_star"].astype(np.float64),
+           "logweight": lw.astype(np.float64),
+           "sweep_counters": res["stats"][:, :5].astype(np.float64),       # n_operations, n_resamples, n_clones, max_id, sum_classes
+           "sample_chains": pick.astype(np.float64),
+           "allocations": last_sample[torch.from_numpy(pick).to(last_sample.device)].cpu().numpy().astype(np.float32),
+           "order": np.stack([st["order"] for st in states]).astype(np.float32),
+           "feature_flags": np.stack([st["flags"] for st in states]).astype(np.float32)}
+    for name in ("M", "gamma", "gamma0", "Phi", "v", "Z"):
+        out[name] = np.stack([np.asarray(st[name], dtype=np.float64) for st in states])
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BYTES:
+        raise SystemExit(f"bench: --dump-outputs would write {total} bytes (limit {DUMP_BYTES})")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -275,15 +312,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="HL", choices=sorted(DESCR))
     ap.add_argument("--chains", type=int, default=0, help="independent chains per GPU (one workgroup each); 0 = the workload's default")
-    ap.add_argument("--burnin", type=int, default=-1, help="iterations from the random start before --warmup; -1 = the workload's default")
+    ap.add_argument("--burnin", type=int, default=-1, help="iterations from the random start before --warmup; -1 = the workload's default with --full, none in a plain run (its --warmup iterations start from the random start)")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink n of the workload (debug only)")
     ap.add_argument("--pool-frac", type=float, default=0.0, help="cluster ids per dataset a chain's pool holds, as a fraction of the reference's N*P+1 "
                     "(src/pmdi.jl:140); 0 = the workload's default (POOL_FRAC).  A sweep that needs more stops with PMDI_E_POOL: the bench then starts "
                     "over with the full pool and the chain count that fits it")
     ap.add_argument("--block", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of one timed-state chain (outside the timed region)")
-    ap.add_argument("--no-latency-form", action="store_true", help="skip the split-form leg (K > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed iteration computed to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run the parity check, the latency form, "
+                    "one chain alone and the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the oracle check of timed-state chains (outside the timed region)")
+    ap.add_argument("--no-latency-form", action="store_true", help="with --full: skip the split-form and one-chain-alone legs")
     ap.add_argument("--cpu-seconds", type=float, default=60.0, help="wall-time budget of the CPU baseline leg")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
@@ -318,7 +358,14 @@ def main():
     w = workloads.make(args.workload, args.scale)
     n, N, P, K = w["n"], w["N"], w["P"], w["K"]
     C = args.chains or DEFAULTS[args.workload][0]
-    burnin = args.burnin if args.burnin >= 0 else DEFAULTS[args.workload][1]
+    # --full (or an explicit --burnin) keeps the workload's burn-in ahead of the warm-up.  A plain run has none of its own: its --warmup
+    # iterations start from the random start and go through the burn-in loop below (which checks the pools after the first sweep)
+    own_burnin = args.full or args.burnin >= 0
+    if own_burnin:
+        burnin, warmup = (args.burnin if args.burnin >= 0 else DEFAULTS[args.workload][1]), args.warmup
+    else:
+        burnin, warmup = args.warmup, 0
+    burnin_reported = burnin if own_burnin else 0
     # chain c of rank r draws from Philox key base + r * 2^32 + c: no two chains of a job share a stream
     seed = 1000 + (rank << 32)
     chains_requested = C
@@ -410,7 +457,7 @@ def main():
     burnin_s = time.perf_counter() - tb
     g.results()          # raises if a chain reported an error
     # ---- 2. warm-up ----
-    for _ in range(args.warmup):
+    for _ in range(warmup):
         iteration()
     # ---- 3. the timed region: exactly --steps iterations ----
     samples = torch.empty((args.steps, C, K, n), dtype=torch.uint8, device=dev)
@@ -462,12 +509,12 @@ def main():
         achieved = alg / (kernel_ms * 1e-3)
         traffic = None
         tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-        key = f"{args.workload}|chains={C}|burnin={burnin}|warmup={args.warmup}|steps={args.steps}|scale={args.scale}"
+        key = f"{args.workload}|chains={C}|burnin={burnin_reported}|warmup={args.warmup}|steps={args.steps}|scale={args.scale}"
         if os.path.exists(tpath):       # PMC-measured HBM bytes per sweep of this exact command line (profiles/README.md), else null
             tj = json.load(open(tpath))
             traffic = tj.get(key, {}).get("hbm_bytes_per_sweep")
             if traffic is None:           # the bytes of a sweep do not depend on how many sweeps were timed: same workload, chains, burn-in
-                pre = f"{args.workload}|chains={C}|burnin={burnin}|"
+                pre = f"{args.workload}|chains={C}|burnin={burnin_reported}|"
                 traffic = next((v.get("hbm_bytes_per_sweep") for k_, v in tj.items() if k_.startswith(pre) and k_.endswith(f"|scale={args.scale}")), None)
         # second ceiling: how busy the issue slots of the dominant kernel are (PMC, profiles/r04/pmc_instruction_mix.json): HBM is at a few
         # per cent of its peak here and says little about this kernel; its waves wait on dependent LDS / L2 round trips, logs and barriers
@@ -490,14 +537,14 @@ def main():
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": DESCR[args.workload] if args.scale == 1.0 else f"{args.workload} scaled n={n}",
-                       "chains_per_gpu": C, "chains_requested": chains_requested, "burnin_iterations": burnin,
+                       "chains_per_gpu": C, "chains_requested": chains_requested, "burnin_iterations": burnin_reported,
                        "pool_ids_per_dataset": int(sw.cap), "pool_frac_of_reference": float(sw.cap) / float(N * P + 1),
                        "block_threads": sw.block_threads, "lds_bytes_per_workgroup": sw.lds_bytes,
                        "workgroups_per_chain": (K if sw.split else 1),
                        "swept_obs_per_iter": n_s, "parallelism": f"chains x{world}",
                        "host_side": "none inside an iteration: hypers, shuffle, sweep, label alignment are device kernels (pmdi_gibbs_step)"},
             "obs_particles_per_sec": total_iters * n_s * P / dt,
-            "burnin_iters_per_sec": (burnin * C * world / burnin_s) if burnin else None,
+            "burnin_iters_per_sec": (burnin * C * world / burnin_s) if burnin_reported else None,
             "sweep_kernel_ms": kernel_ms,
             "sweep_kernel_ms_each": [round(float(a.elapsed_time(b)), 1) for a, b in events],
             "allgather_ms": allgather_ms, "allgather_bytes_per_rank": (int(samples.numel()) if allgather_ms is not None else None),
@@ -538,7 +585,9 @@ def main():
         comm.close()
     if dist is not None:
         dist.destroy_process_group()
-    if rank == 0 and not args.no_parity and args.workload != "cfg5":
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, g, res, samples[-1], seed)
+    if rank == 0 and args.full and not args.no_parity and args.workload != "cfg5":
         # ---- parity of the timed kernel instantiation, outside the timed region (cfg5: the oracle needs minutes per sweep)
         by_cost = np.argsort(costs)
         last_round = int(sw.launch_order()[-1]) if hasattr(sw, "launch_order") else int(by_cost[0])
@@ -547,7 +596,7 @@ def main():
         if out["parity_check"] != "ok":
             print(json.dumps(out))
             raise SystemExit("bench: the timed kernel's results differ from the oracle's: " + json.dumps(out["parity_check_detail"]))
-    if rank == 0 and K > 1 and not args.no_latency_form and not sw.split:
+    if rank == 0 and args.full and K > 1 and not args.no_latency_form and not sw.split:
         # ---- the latency form on settled chains of this run: K cooperating workgroups per chain, as many chains as are resident at once
         order_c = np.argsort(costs)
         C2 = max(1, min(C, 512 // K))
@@ -577,11 +626,11 @@ def main():
                                "note": "K cooperating workgroups per chain (one per dataset), one sc1 hand-off per swept observation; "
                                        "same settled chains as the throughput run, 3 timed iterations after 2"}
         g2.close(); sw2.close()
-    if rank == 0 and not args.no_latency_form:
+    if rank == 0 and args.full and not args.no_latency_form:
         out["one_chain_alone"] = one_chain_alone(pkg, w, g, int(np.argsort(costs)[C // 2]), seed, local_rank, args.workload == "cfg5", torch)
     if rank == 0:
         print(f"[bench] GPU part done: {out['value']:.1f} iters/s", file=sys.stderr, flush=True)
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             order = np.argsort(costs)
             pick = [int(order[int(q * (C - 1))]) for q in (0.5, 0.1, 0.9, 0.3, 0.7, 0.2, 0.8, 0.4)]   # settled chains across the cost range
             states = [g.get(c) for c in pick]

@@ -47,11 +47,24 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     extra = os.environ.get("PMDI_EXTRA_HIPCC_FLAGS", "").split()
     bdir = os.path.join(_PKG, "build" if not os.environ.get("PMDI_LIB_PATH") else "build_ab")
+    if not force and _up_to_date(extra, bdir):     # nothing to do: write nothing (the tree may belong to another user)
+        return LIB_PATH
     os.makedirs(bdir, exist_ok=True)
     import fcntl
     with open(os.path.join(bdir, ".lock"), "w") as lock:      # ranks of one node may call build() at the same moment
         fcntl.flock(lock, fcntl.LOCK_EX)
         return _build_locked(force, verbose, hipcc, extra, bdir)
+
+
+def _up_to_date(extra, bdir):
+    stamp = os.path.join(bdir, "flags.txt")
+    if not os.path.exists(stamp) or not os.path.exists(LIB_PATH) or open(stamp).read() != " ".join(extra):
+        return False
+    hdr_time = max(os.path.getmtime(p) for p in _HEADERS)
+    objs = [os.path.join(bdir, os.path.basename(src) + ".o") for src in _SOURCES]
+    if not all(os.path.exists(o) and os.path.getmtime(o) >= max(os.path.getmtime(src), hdr_time) for o, src in zip(objs, _SOURCES)):
+        return False
+    return os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(o) for o in objs)
 
 
 def _build_locked(force, verbose, hipcc, extra, bdir):

@@ -5,8 +5,8 @@
 Then, on the GPU box, run the variants back to back in one gpurun call (same box, same thermal state):
 
     for v in build_ab/lib_a.so build_ab/lib_b.so particlemdi.jl_amd/libpmdi_hip.so; do
-        PMDI_NO_BUILD=1 PMDI_LIB_PATH=$v python bench.py --no-cpu --steps 8 --warmup 2 > gpurun_out/ab.json 2> gpurun_out/ab.err || exit 1
-        python scripts/bline.py $v < gpurun_out/ab.json
+        PMDI_NO_BUILD=1 PMDI_LIB_PATH=$v python bench.py --full --no-cpu --steps 8 --warmup 2 > "$OUT/ab.json" 2> "$OUT/ab.err" || exit 1
+        python scripts/bline.py $v < "$OUT/ab.json"
     done
 
 A variant must pass `pytest tests/test_gpu_sweep.py tests/test_gpu_soak.py -m gpu` with PMDI_LIB_PATH set before its bench number means

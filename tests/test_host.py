@@ -125,6 +125,41 @@ def test_bench_byte_models():
     assert b.algorithmic_bytes(w, P, n, n1, work, stats, layout="particle") > C * per_chain
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 arrays only, a seeded chain sample that does not change from run to run,
+    and the rows of the sampled chains taken from the right chains."""
+    import importlib.util
+    import os
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("pmdi_bench", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    C, P, K, n, N = 100, 16, 2, 30, 5
+    rng = np.random.default_rng(3)
+    res = {"logweight": rng.random((C, P)), "p_star": np.arange(C), "stats": rng.integers(0, 9, (C, 8))}
+    last = torch.from_numpy(rng.integers(1, N + 1, (C, K, n)).astype(np.uint8))
+
+    class FakeGibbs:
+        def get(self, c):
+            return {"M": np.full(K, c + 0.5), "gamma": np.ones((N, K)), "gamma0": np.ones((N, K)), "Phi": np.ones(1), "v": 1.0, "Z": 2.0,
+                    "s": np.ones((n, K), dtype=np.int64), "order": np.arange(n) + c, "flags": np.ones(7, dtype=np.uint8)}
+
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), FakeGibbs(), res, last, 1000)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"p_star.npy", "logweight.npy", "allocations.npy", "sample_chains.npy"} <= set(names)
+    for f in names:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    pick = np.load(tmp_path / "a" / "sample_chains.npy").astype(np.int64)
+    assert len(pick) == b.DUMP_CHAINS and len(set(pick.tolist())) == len(pick)
+    assert np.array_equal(np.load(tmp_path / "a" / "allocations.npy"), last.numpy()[pick].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "M.npy")[:, 0], pick + 0.5)
+    assert np.array_equal(np.load(tmp_path / "a" / "logweight.npy"), res["logweight"])
+
+
 def _literal_generate_psm(path, burnin, thin):
     """src/output_analysis/consensus_map.jl:31-65, line by line, in numpy (1-based arithmetic kept)."""
     from math import comb
