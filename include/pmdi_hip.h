@@ -105,7 +105,10 @@ typedef struct {
     uint64_t seed;         /* chain c uses seed + c */
     int32_t q1_mode;       /* 0 reference: new_id zeroed per iteration (src/pmdi.jl:167); 1: per step */
     int32_t q2_mode;       /* 0 pmdi(): history not permuted on resample (src/pmdi.jl:321-324); 1 __pmdi() (src/__pmdi.jl:285) */
-    int64_t pool_cap;      /* cluster pool ids per dataset; 0 = N*P+1 (src/pmdi.jl:140) */
+    int64_t pool_cap;      /* cluster pool ids per dataset; 0 = N*P+1 (src/pmdi.jl:140); at least N + 2.  A sweep whose
+                              largest cluster id (pmdi_sweep_stats.max_id) fits gives the same results as with N*P+1; a chain
+                              that needs more stops that sweep with PMDI_E_POOL in its own err slot and keeps its input
+                              allocations (s_out = s_in); the other chains of the launch are swept as usual */
     int32_t block_threads; /* 0 = choose (and split the chains of a sweep into concurrent launches by weight); else 128/256/512/1024 */
     int32_t reserved;
     const pmdi_tuning *tuning; /* NULL = all automatic (read during pmdi_create only) */

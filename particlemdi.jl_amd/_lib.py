@@ -14,7 +14,8 @@ _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("PMDI_LIB_PATH") or os.path.join(_PKG, "libpmdi_hip.so")   # override: A/B builds only
 _SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_hypers.hip", "pmdi_api.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
 _HEADERS = [os.path.join(_PKG, "csrc", "pmdi_internal.h"), os.path.join(_PKG, "csrc", "pmdi_device.h"),
-            os.path.join(_PKG, "csrc", "pmdi_sweep2_body.h"), os.path.join(_PKG, "csrc", "pmdi_arith.h"),
+            os.path.join(_PKG, "csrc", "pmdi_sweep_body.h"), os.path.join(_PKG, "csrc", "pmdi_sweep2_body.h"),
+            os.path.join(_PKG, "csrc", "pmdi_arith.h"),
             os.path.join(_ROOT, "include", "pmdi_hip.h")]
 
 GAUSSIAN, CATEGORICAL, NEGBINOM = 0, 1, 2
@@ -584,12 +585,16 @@ class Gibbs:
         fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
         _check(lib().pmdi_gibbs_set(self.h, int(chain), _ptr(f64(M)), _ptr(g), _ptr(g0), _ptr(f64(Phi)), _ptr(vZ), _ptr(s_), _ptr(o_), _ptr(fl)))
 
-    def results(self):
+    def results(self, check=True):
+        """Counters and outputs of the last sweep of every chain.  check=False: a chain's error (sticky until pmdi_gibbs_set gives it a
+        new state) does not raise; "err" holds every chain's code (0, or PMDI_E_POOL for a chain that ran out of cluster ids)."""
         sw = self.sw
         stats = np.zeros((sw.C, 8), dtype=np.int64); err = np.zeros(sw.C, dtype=np.int32)
         ps = np.zeros(sw.C, dtype=np.int64); lw = np.zeros((sw.C, sw.P))
-        _check(lib().pmdi_gibbs_results(self.h, _ptr(stats), _ptr(err), _ptr(ps), _ptr(lw)))
-        return {"stats": stats, "p_star": ps, "logweight": lw}
+        rc = lib().pmdi_gibbs_results(self.h, _ptr(stats), _ptr(err), _ptr(ps), _ptr(lw))
+        if check or rc not in (0, -4, -6):
+            _check(rc)
+        return {"stats": stats, "p_star": ps, "logweight": lw, "err": err}
 
     def view(self):
         v = GibbsView()

@@ -40,15 +40,46 @@ def replay(z, data, kinds, sweeper_factory, check_featsel=True):
     return sw
 
 
-def t5_invariants(state, N, P, K, n_obs):
-    """test/runtests.jl:147-162 on an exported state (particle (K,P,N), counts/cluster_n (K,cap))."""
-    cap = N * P + 1
+def t5_invariants(state, N, P, K, n_obs, cap=None):
+    """test/runtests.jl:147-162 on an exported state (particle (K,P,N), counts/cluster_n (K,cap)); cap: the handle's pool_cap
+    (None = N*P+1, src/pmdi.jl:140)."""
+    if cap is None:
+        cap = N * P + 1
     for k in range(K):
         part = state["particle"][k]
+        assert part.min() >= 1 and part.max() <= cap, (part.min(), part.max(), cap)
         for j in range(P):
             assert state["cluster_n"][k, part[j] - 1].sum() == n_obs        # :147,:156
         cnt = np.bincount(part.ravel(), minlength=cap + 1)[1:cap + 1]
         assert (cnt == state["counts"][k][:cap]).all()                    # :149-153,:158-162
+
+
+def pool_need(oracle_result):
+    """Cluster ids per dataset a sweep needs: the largest id any step of any dataset touched (the oracle's stats["max_id"]; a clone
+    takes max_k + 1).  A handle whose pool_cap is at least this sweeps it exactly as the oracle does; one id less stops the chain with
+    PMDI_E_POOL."""
+    return int(oracle_result["stats"]["max_id"])
+
+
+def check_state_cap(dev, orc, cap, live_only=False):
+    """The exported state of a handle with pool_cap = cap (counts / cluster_n (K, cap)) against the oracle's (N*P+1 ids): particle and
+    max_id equal, counts equal on ids 1..cap and zero above cap in the oracle, cluster_n the same.  live_only: cluster_n only on the
+    live ids 1..max_id.  The sizes of ids above max_id are whatever earlier steps left there (the reference defines none of them):
+    the general kernel leaves what the oracle leaves, but not where the two sides swept different histories (a handle whose last
+    sweep stopped with PMDI_E_POOL, an oracle that also ran a burn-in), and the settled-chain kernel does not export those at all."""
+    assert (dev["particle"] == orc["particle"]).all(), "particle"
+    assert (dev["max_id"] == orc["max_id"]).all(), ("max_id", dev["max_id"], orc["max_id"])
+    assert (dev["max_id"] <= cap).all()
+    assert dev["counts"].shape[1] == cap and dev["cluster_n"].shape[1] == cap
+    assert (dev["counts"] == orc["counts"][:, :cap]).all(), "counts"
+    assert not orc["counts"][:, cap:].any()
+    if live_only:
+        for k in range(dev["particle"].shape[0]):
+            m = int(orc["max_id"][k])
+            assert (dev["cluster_n"][k, :m] == orc["cluster_n"][k, :m]).all(), ("cluster_n", k)
+    else:
+        assert (dev["cluster_n"] == orc["cluster_n"][:, :cap]).all(), "cluster_n"
+        assert not orc["cluster_n"][:, cap:].any()
 
 
 def check_work_counters(wk, rec, trace, N, kernel):

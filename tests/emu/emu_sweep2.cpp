@@ -45,6 +45,11 @@ size_t layout_arena(DsetDev &d, int N, int P, long long cap, long long n_rows_ss
     return o;
 }
 
+// every dataset's arena sits between two guard regions of a known byte pattern, checked after every sweep: a write past the end
+// of the per-id tables (ids beyond cap) -- on the GPU the next chain's arena -- shows up here
+constexpr size_t GUARD = 4096;
+constexpr unsigned char GUARD_BYTE = 0xA5;
+
 struct Emu {
     int K, N, P;
     long long n, cap;
@@ -88,13 +93,18 @@ void entry(void *p)
 
 extern "C" {
 
+enum { EMU_E_GUARD = -100 };
+
 // data[k]: n x D_k row-major doubles (integer types: levels 1..L / counts >= 0 as doubles); kinds[k]: K_GAUSSIAN / K_CATEGORICAL / K_NEGBINOM
+// cap: cluster ids per dataset (pmdi_config::pool_cap); 0 = N*P+1 (src/pmdi.jl:140); below N + 2 is rejected, as pmdi_create does
 void *emu_create(int K, long long n, int N, int P, const int *D, const double *const *data, unsigned long long seed, int q1,
-                 int cols_l, int idcap, const int *kinds, int cls, int cdfl)
+                 int cols_l, int idcap, const int *kinds, int cls, int cdfl, long long cap)
 {
     if (K < 1 || K > pmdi_s2::KMAX2 || (P != 256 && P != 512 && P != 1024 && P != 2048) || N > 64) return nullptr;
+    if (cap == 0) cap = (long long)N * P + 1;
+    if (cap < N + 2 || cap > (long long)N * P + 1) return nullptr;
     Emu *e = new Emu();
-    e->K = K; e->N = N; e->P = P; e->n = n; e->cap = (long long)N * P + 1; e->seed = seed; e->q1 = q1;
+    e->K = K; e->N = N; e->P = P; e->n = n; e->cap = cap; e->seed = seed; e->q1 = q1;
     {
         const int nw = P > 1024 ? 8 : 4;
         const int mx = pmdi_s2::class_slots_max(K, P / (64 * nw), nw);
@@ -152,8 +162,10 @@ void *emu_create(int K, long long n, int N, int P, const int *D, const double *c
             }
         }
         d.stride = layout_arena(d, N, P, e->cap, n);
-        e->arena[k].assign(d.stride, 0);
-        d.arena = e->arena[k].data();
+        e->arena[k].assign(GUARD + d.stride + GUARD, 0);
+        memset(e->arena[k].data(), GUARD_BYTE, GUARD);
+        memset(e->arena[k].data() + GUARD + d.stride, GUARD_BYTE, GUARD);
+        d.arena = e->arena[k].data() + GUARD;
     }
     e->sumD = flag_off;
     return e;
@@ -169,7 +181,17 @@ long long emu_lds_bytes(void *h)
     return L.total;
 }
 
-// one sweep of one chain; 0-based labels / order; returns err (0 ok, 1 requeue, -4 pool)
+// the first guard byte of dataset k's arena that is not the pattern any more (offset from the arena's start), or 0 if none changed
+static long long guard_broken(const Emu *e, int k)
+{
+    const unsigned char *g = (const unsigned char *)e->arena[k].data();
+    const size_t stride = e->ds[k].stride;
+    for (size_t j = 0; j < GUARD; ++j) if (g[j] != GUARD_BYTE) return (long long)j - (long long)GUARD - 1;
+    for (size_t j = 0; j < GUARD; ++j) if (g[GUARD + stride + j] != GUARD_BYTE) return (long long)(stride + j) + 1;
+    return 0;
+}
+
+// one sweep of one chain; 0-based labels / order; returns err (0 ok, 1 requeue, -4 pool, EMU_E_GUARD a guard byte changed)
 int emu_sweep(void *h, long long iter, const int *s_in, const int *order, long long n1, const double *Pi, const double *logphi,
               const unsigned char *flags, double lw_init, int *s_out, double *lw_out, int *pstar, long long *stats, long long *work,
               double *trace, int *particle, int *counts, int *cn, int *maxid_out)
@@ -195,6 +217,14 @@ int emu_sweep(void *h, long long iter, const int *s_in, const int *order, long l
     for (int k = 0; k < e->K; ++k) go = go && e->ds[k].kind == K_GAUSSIAN;
     RunArg r{&a, e->K, e->P / (64 * nw), nw, go};
     wavesim::run_block(64 * nw, 0, (size_t)a.s2.total, entry, &r);
+    for (int k = 0; k < e->K; ++k) {
+        const long long at = guard_broken(e, k);
+        if (at) {
+            fprintf(stderr, "emu: dataset %d: guard byte at arena offset %lld (arena %zu bytes, cap %lld) was written\n", k,
+                    at > 0 ? at - 1 : at + 1, e->ds[k].stride, e->cap);
+            return EMU_E_GUARD;
+        }
+    }
     if (work) for (int k = 0; k < e->K; ++k) for (int j = 0; j < 8; ++j) work[k * 8 + j] = wk[k * 8 + j];
     if (err == 0 && particle) {
         // what pmdi_export_state does: expand the columns back to particle[n, p, k]

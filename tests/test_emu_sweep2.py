@@ -6,7 +6,7 @@ performance are the GPU tests' business."""
 import numpy as np
 import pytest
 
-from _cases import expected_work_counters, t5_invariants
+from _cases import check_state_cap, expected_work_counters, pool_need, t5_invariants
 from conftest import random_hypers
 
 
@@ -225,3 +225,143 @@ def test_lane_order_inside_a_wave_does_not_matter(O, monkeypatch):
     data, z = _gauss(rng, 160, 2, sep=3.0)
     _compare(O, data, 6, 256, 2, 51, 40, settle=True, truth=z, allow_requeue=0)
     assert _chain(O, data, 6, 256, 11, 4, 2, allow_requeue=1) >= 1
+
+
+# ---- reduced cluster pools (pmdi_config::pool_cap < N*P+1) at the exact PMDI_E_POOL boundary: with need = the oracle's
+#      stats["max_id"] of the sweep, cap = need must give the oracle's sweep bit for bit and cap = need - 1 must stop it with -4; the
+#      guard regions around every dataset's arena catch a write one id past the per-id tables
+
+def _planted_inputs(rng, n, K, N, truth, scramble, settle):
+    s = np.repeat((truth + 1)[:, None], K, axis=1)
+    idx = rng.random((n, K)) < scramble
+    s[idx] = rng.integers(1, N + 1, size=int(idx.sum()))
+    Pi, Phi = random_hypers(rng, N, K)
+    Pi[:3] += settle; Pi /= Pi.sum(0)
+    return s, rng.permutation(n) + 1, Pi, Phi
+
+
+def _burn_in_inputs(O, data, kinds, N, P, seed, burn, n1):
+    """The inputs of iteration burn + 1 of a real Gibbs chain (as _chain): labels, order, Pi, Phi."""
+    n, K = data[0].shape[0], len(data)
+    hy = O.Hypers(n, N, K, seed=seed)
+    o = O.Oracle(data, kinds, N, P, seed=seed)
+    for it in range(1, burn + 1):
+        Pi = hy.step(it)
+        ro = o.sweep(it, np.array(hy.s), np.array(hy.order), n1, Pi, hy.Phi)
+        hy.s[:] = ro["s"]
+        hy.align_labels(it)
+    Pi = hy.step(burn + 1)
+    out = np.array(hy.s), np.array(hy.order), Pi, np.array(hy.Phi)
+    o.close(); hy.close()
+    return out
+
+
+def _oracle(O, data, kinds, N, P, seed, it, inp, n1):
+    """One sweep of a fresh oracle (N*P+1 ids): result, per-step record, work counters, exported state."""
+    n = data[0].shape[0]
+    o = O.Oracle(data, kinds, N, P, seed=seed)
+    rec = o.debug_steps(n - n1 + 1)
+    ro = o.sweep(it, *inp[:2], n1, *inp[2:], trace=True)
+    out = ro, rec, o.work(), o.export()
+    o.close()
+    return out
+
+
+def _equal(re, want, N, n, cap):
+    ro, rec, (up, mv), eo = want
+    assert re["err"] == 0, f"kernel stopped with err {re['err']} (reason {re['why']}) at cap {cap}"
+    bad = np.where(~np.isclose(re["trace"], ro["trace"], rtol=1e-9, atol=1e-9).all(axis=1))[0]
+    assert bad.size == 0, f"first diverging swept observation {bad[0]}: emu={re['trace'][bad[0]]} oracle={ro['trace'][bad[0]]}"
+    assert (re["s"] == ro["s"]).all() and re["p_star"] == ro["p_star"]
+    assert np.allclose(re["logweight"], ro["logweight"], rtol=1e-12, atol=1e-12)
+    for key in ("n_operations", "n_resamples", "n_clones", "max_id", "sum_classes"):
+        assert re["stats"][key] == ro["stats"][key], key
+    ev, cols, splits = expected_work_counters(rec, ro["trace"], N, item_cap=None)
+    wk = re["work"]
+    assert (wk[:, 1] == up).all() and (wk[:, 3] == mv).all() and wk[:, 2].sum() == ro["stats"]["n_clones"]
+    assert (wk[:, 0] == ev).all() and (wk[:, 5] == cols).all() and (wk[:, 6] == splits).all(), (wk, ev, cols, splits)
+    check_state_cap(re["state"], eo, cap, live_only=True)         # (this kernel exports no sizes above max_id)
+    t5_invariants(re["state"], N, re["state"]["particle"].shape[1], len(re["state"]["max_id"]), n, cap=cap)
+
+
+def _boundary(O, data, kinds, N, P, seed, it, inp, n1, refit=None, idcap_near=None, **kw):
+    """need from the oracle; the emulator at cap = need equals it, at cap = need - 1 stops with PMDI_E_POOL keeping the input labels.
+    refit: candidate inputs (it, inp) for the next sweep of that failed handle -- the first whose need fits is swept and compared.
+    idcap_near: sweep once more at both caps with the LDS id tables ending that many ids from need.  Returns need."""
+    from _emu import EmuSweeper
+    n, K = data[0].shape[0], len(data)
+    want = _oracle(O, data, kinds, N, P, seed, it, inp, n1)
+    need = pool_need(want[0])
+    assert need - 1 >= N + 2, need                              # (pmdi_create's lower bound)
+    idcaps = [kw.pop("idcap", 128)] + ([need + d for d in idcap_near] if idcap_near else [])
+    for idcap in idcaps:
+        e = EmuSweeper(data, N, P, seed=seed, kinds=kinds, cap=need, idcap=idcap, **kw)
+        _equal(e.sweep(it, *inp[:2], n1, *inp[2:], trace=True), want, N, n, need)
+        e.close()
+        e = EmuSweeper(data, N, P, seed=seed, kinds=kinds, cap=need - 1, idcap=idcap, **kw)
+        r = e.sweep(it, *inp[:2], n1, *inp[2:], trace=True)
+        assert r["err"] == -4, (r["err"], r["why"], need, idcap)
+        assert (r["s"] == inp[0]).all()                           # the chain keeps its allocations
+        if refit and idcap == idcaps[0]:
+            for it2, inp2 in refit:
+                w2 = _oracle(O, data, kinds, N, P, seed, it2, inp2, n1)
+                if pool_need(w2[0]) <= need - 1:
+                    _equal(e.sweep(it2, *inp2[:2], n1, *inp2[2:], trace=True), w2, N, n, need - 1)
+                    break
+            else:
+                raise AssertionError(f"no refit candidate needs fewer than {need} ids")
+        e.close()
+    return need
+
+
+POOL = {     # name: (kinds, P, n, N, scrambled fraction of the planted labels, prior mass added to three labels, emulator arguments)
+    "K1": (["gaussian"], 256, 160, 6, 0.08, 1.0, {}),
+    "K2": (["gaussian"] * 2, 256, 160, 6, 0.08, 1.0, {}),
+    "K3": (["gaussian"] * 3, 256, 160, 6, 0.08, 1.0, {}),
+    "K4": (["gaussian"] * 4, 256, 160, 6, 0.08, 1.0, {}),
+    "gau+cat+nb": (["gaussian", "categorical", "negbinom"], 512, 160, 6, 0.08, 1.0, {}),
+    "P2048-cls32": (["gaussian", "categorical"], 2048, 120, 12, 0.03, 5.0, {"cls": 32}),
+    "arena-tables": (["gaussian"] * 2, 256, 160, 6, 0.08, 1.0, {"cols_l": 2, "idcap": 8}),
+}
+
+
+@pytest.mark.parametrize("name", list(POOL))
+def test_reduced_pool_boundary_from_a_planted_state(O, name):
+    """A mid-chain state (the planted clustering, a few labels scrambled): at cap = need the settled-chain kernel's sweep equals the
+    oracle's in everything, at need - 1 it stops with PMDI_E_POOL; nothing is written outside the arena either way.  The handle that
+    failed then sweeps inputs that fit: the oracle's results, whatever the failed sweep left in its tables."""
+    kinds, P, n, N, scramble, settle, kw = POOL[name]
+    K = len(kinds)
+    rng = np.random.default_rng(600 + len(name) + P)
+    data, z = _mixed(rng, n, kinds)
+    n1 = n // 4
+    seed = 610 + K
+    inp = _planted_inputs(rng, n, K, N, z, scramble, settle)
+    want = _oracle(O, data, kinds, N, P, seed, 2, inp, n1)[0]
+    refit = []
+    for _ in range(3):         # the next iteration of that chain (its labels settle), in a few orders; else the planted clustering itself
+        Pi, Phi = random_hypers(rng, N, K)
+        Pi[:3] += settle; Pi /= Pi.sum(0)
+        refit.append((3, (want["s"], rng.permutation(n) + 1, Pi, Phi)))
+    for _ in range(3):
+        refit.append((3, _planted_inputs(rng, n, K, N, z, 0.0, 20.0)))
+    need = _boundary(O, data, kinds, N, P, seed, 2, inp, n1, refit=refit, **kw)
+    print(f"{name}: need {need} (idcap {kw.get('idcap', 128)})")
+
+
+@pytest.mark.parametrize("kinds,P,N,near", [(["gaussian"] * 2, 512, 6, (-2, 0, 1)), (["gaussian", "categorical", "negbinom"], 256, 8, None)],
+                         ids=["K2-P512", "mixed"])
+def test_reduced_pool_boundary_after_burn_in(O, kinds, P, N, near):
+    """The inputs of a real Gibbs chain after a short burn-in on the oracle (as _chain).  K2-P512 needs fewer ids than the LDS tables
+    hold (cap < idcap = 128), and is swept again with those tables ending near cap: idcap = need - 2, need, need + 1."""
+    rng = np.random.default_rng(650 + P)
+    n, K = 200, len(kinds)
+    data, _ = _mixed(rng, n, kinds)
+    n1 = n // 4
+    seed = 651 + K
+    burn = 5
+    inp = _burn_in_inputs(O, data, kinds, N, P, seed, burn, n1)
+    need = _boundary(O, data, kinds, N, P, seed, burn + 1, inp, n1, idcap_near=near)
+    print(f"{'+'.join(kinds)} P={P} after burn-in: need {need}")
+    if near:
+        assert need < 128

@@ -160,11 +160,12 @@ FULL = {"cfg3": 3, "HL": 3, "cfg4": 2, "cfg5": 1}
 SIZES = {"cfg3": (5000, 30, 1024), "HL": (10000, 20, 1024), "cfg4": (10000, 50, 2048), "cfg5": (20000, 50, 4096)}
 
 
-def _one_iteration_vs_oracle(pkg, O, w, sw, g, chains, it, base_seed, fsel, tag):
+def _one_iteration_vs_oracle(pkg, O, w, sw, g, chains, it, base_seed, fsel, tag, cap=None):
     """ONE whole Gibbs iteration of the device-resident chains `chains`, compared piece by piece with the oracle from the same
     state: hyper-parameter kernel, sweep (allocations, p_star, counters, work counters, log-weights, exported state, T5
-    invariants), feature selection, label alignment."""
-    from _cases import check_work_counters
+    invariants), feature selection, label alignment.  cap: the handle's reduced pool_cap -- a chain's sweep stops with PMDI_E_POOL
+    (keeping its allocations) exactly when the oracle's sweep needs more ids; the others are compared, their exported state at cap."""
+    from _cases import check_state_cap, check_work_counters, pool_need
     n, K, N, P = w["n"], w["K"], w["N"], w["P"]
     n1 = g.n1
     st0 = {c: g.get(c) for c in chains}
@@ -185,7 +186,7 @@ def _one_iteration_vs_oracle(pkg, O, w, sw, g, chains, it, base_seed, fsel, tag)
         assert np.isclose(b["v"], hy.v, rtol=1e-9) and np.isclose(b["Z"], hy.Z, rtol=1e-9)
         hys[c] = hy
     g.step(pkg.STEP_SWEEP)
-    res = g.results()
+    res = g.results(check=cap is None)
     work = sw.work_counters()
     swept = sw.swept_by()             # which kernel finished each chain's sweep: 0 general, 1 settled-chain, 2 general after a hand-over
     oracles = {}
@@ -198,6 +199,14 @@ def _one_iteration_vs_oracle(pkg, O, w, sw, g, chains, it, base_seed, fsel, tag)
         flags = [b["flags"][sum(w["D"][:k]):sum(w["D"][:k + 1])] for k in range(K)]
         ro = orc.sweep(it, b["s"], b["order"], n1, Pi, b["Phi"], flags, lw_init=1.0, trace=True)
         st2 = g.get(c)
+        if cap is not None:
+            fit = pool_need(ro) <= cap
+            assert (res["err"][c] == 0) == fit, (tag, c, int(res["err"][c]), pool_need(ro), cap)
+            if not fit:                   # that chain stopped with PMDI_E_POOL, keeping its allocations
+                print(f"{tag}: chain {c} needs {pool_need(ro)} ids > pool_cap {cap}: PMDI_E_POOL")
+                assert (st2["s"] == b["s"]).all()
+                orc.close()
+                continue
         print(f"{tag}: chain {c} swept by kernel {int(swept[c])} (0 general, 1 settled-chain, 2 handed over mid-sweep), oracle sweep {ro['stats']['seconds']:.1f} s, stats {ro['stats']}")
         if not (st2["s"] == ro["s"]).all():
             # where did the chain leave the oracle?  (shuffled position of the first differing allocation, per dataset)
@@ -214,7 +223,9 @@ def _one_iteration_vs_oracle(pkg, O, w, sw, g, chains, it, base_seed, fsel, tag)
         assert (wk[:, 1] == up).all() and (wk[:, 3] == mv).all() and wk[:, 2].sum() == ro["stats"]["n_clones"]
         check_work_counters(wk, rec, ro["trace"], N, int(swept[c]))
         dev_state, ora_state = sw.export_state(c), orc.export()
-        t5_invariants(dev_state, N, P, K, n)
+        t5_invariants(dev_state, N, P, K, n, cap=cap)
+        if cap is not None:
+            check_state_cap(dev_state, ora_state, cap, live_only=True)
         assert (dev_state["particle"] == ora_state["particle"]).all()
         assert (dev_state["max_id"] == ora_state["max_id"]).all()
         for k in range(K):
@@ -223,13 +234,16 @@ def _one_iteration_vs_oracle(pkg, O, w, sw, g, chains, it, base_seed, fsel, tag)
             assert (dev_state["cluster_n"][k][:m] == ora_state["cluster_n"][k][:m]).all()
         oracles[c] = (orc, ro)
     # ---- feature selection (cfg5) and label alignment from the same state
+    done = [c for c in chains if c in oracles]
     if fsel:
         g.step(pkg.STEP_FEATSEL)
-        for c in chains:
+        for c in done:
             of, _ = oracles[c][0].feature_select(it, oracles[c][1]["s"])
             assert (g.get(c)["flags"] == np.concatenate(of)).all()
     g.step(pkg.STEP_ALIGN)
-    for c in chains:
+    for c in set(chains) - set(done):
+        hys[c].close()
+    for c in done:
         hy = hys[c]
         hy.s[:] = oracles[c][1]["s"]
         hy.gamma, hy.Phi = st1[c]["gamma"], st1[c]["Phi"]
@@ -237,7 +251,7 @@ def _one_iteration_vs_oracle(pkg, O, w, sw, g, chains, it, base_seed, fsel, tag)
         st3 = g.get(c)
         assert (st3["s"] == np.array(hy.s)).all() and (st3["gamma"] == hy.gamma).all()
         oracles[c][0].close(); hy.close()
-    return {c: dict(oracles[c][1], kernel=int(swept[c])) for c in chains}
+    return {c: dict(oracles[c][1], kernel=int(swept[c])) for c in done}
 
 
 @pytest.mark.parametrize("cfg,ksplit", [("cfg3", 0), ("cfg3", 1), ("HL", 0), ("HL", 1), ("cfg4", 0), ("cfg4", 1), ("cfg5", None),
