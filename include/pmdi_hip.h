@@ -355,9 +355,9 @@ int pmdi_work_counters(pmdi_handle *h, int64_t *out);
  * the settled-chain kernel (csrc/pmdi_sweep2.hip: any mix of Gaussian / Categorical / NegBinom datasets, K <= 4, N <= 64, D <= 64,
  * P in {256, 512, 1024, 2048}, default quirk modes, one workgroup per chain; PMDI_SETTLED=0 switches it off), else 0.
  * given_back4 (optional, 4 Int64): chains that kernel has handed back to the general kernel so far because a step outgrew its
- * tables -- [0] unused (always 0: any number of reachable clusters is evaluated in place); [1] steps with more than 32 particle
- * classes in a dataset (a subset of [2]); [2] steps with more than 16 particle classes in a dataset, or cluster ids beyond 16 bits;
- * [3] in total.  A handed-back chain is swept by the general kernel inside the same call: allocations, picked particle and
+ * tables -- [0] unused (always 0: any number of reachable clusters is evaluated in place); [1] steps with more than twice the class
+ * capacity in particle classes in a dataset (more than 32 at the default capacity of 16; a subset of [2]); [2] steps with more particle
+ * classes in a dataset than the capacity (16 by default, tuning.s2_cls), or cluster ids beyond 16 bits; [3] in total = [2].  A handed-back chain is swept by the general kernel inside the same call: allocations, picked particle and
  * counters never depend on which kernel ran (the traced ESS agrees to ~1e-13: tree-ordered sums). */
 int pmdi_settled_kernel(pmdi_handle *h, int64_t *given_back4);
 

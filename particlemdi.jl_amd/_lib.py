@@ -273,6 +273,10 @@ class Sweeper:
     def __init__(self, data, kinds, N, P, n_chains=1, seed=0, device=0, q1_mode=0, q2_mode=0,
                  pool_cap=0, block_threads=0, tuning=None):
         """tuning: dict of pmdi_tuning fields (include/pmdi_hip.h) that override the PMDI_* environment variables for this handle."""
+        known = {name for name, _ in _Tuning._fields_} - {"reserved"}
+        for name in (tuning or {}):        # (setattr on a ctypes Structure would take any name and the knob would silently do nothing)
+            if name not in known:
+                raise KeyError(f"unknown tuning knob {name!r}; pmdi_tuning has {sorted(known)}")
         L = lib()
         self.K = len(data)
         if self.K > KMAX:
@@ -391,8 +395,8 @@ class Sweeper:
 
     def given_back(self):
         """Chains the settled-chain kernel has handed back to the general kernel so far (include/pmdi_hip.h, pmdi_settled_kernel):
-        [0] unused (0), [1] steps with more than 32 particle classes (a subset of [2]), [2] more than 16 particle classes or cluster
-        ids beyond 16 bits, [3] total."""
+        [0] unused (0), [1] steps with more than twice the class capacity in particle classes (more than 32 at the default capacity
+        of 16; a subset of [2]), [2] more particle classes than the capacity or cluster ids beyond 16 bits, [3] total."""
         out = np.zeros(4, dtype=np.int64)
         lib().pmdi_settled_kernel(self.h, _ptr(out))
         return out

@@ -138,7 +138,7 @@ struct SweepArgs {
     int *handed;                // [chain] number of the sweep in which the chain was last given back (such a chain goes to the general
                                 // kernel directly for the next few sweeps: it tends to be given back again), or null
     int sweep_no;               // this sweep's number (per handle)
-    long long *requeue_total;   // [4] chains given back so far, by reason (reachable clusters, chosen clusters, classes), and in total
+    long long *requeue_total;   // [4] chains given back so far: [0] unused, [1] more than twice the class capacity, [2] classes or wide ids, [3] in total (pmdi_hip.h)
     int requeue_only;           // 1: this launch of the general kernel sweeps exactly those chains
     int slot_base;              // split mode launched in residency-sized batches: first chain slot of this launch
     int err_keep;               // 1: a successful sweep leaves err[chain] as it is (device-resident chains: the first error sticks)

@@ -2208,7 +2208,7 @@ struct Sweep2 {
                     if (!a.err_keep) PM2_G(int, a.err)[chain] = 0;                         // (its K cooperating workgroups only ever write an error)
                     if (a.handed) PM2_G(int, a.handed)[chain] = a.sweep_no;
                     if (a.requeue_total) {
-                        pm2_atomic_add((u64 *)a.requeue_total + 3, (u64)1); pm2_atomic_add((u64 *)a.requeue_total + (failed - 2), (u64)1);
+                        pm2_atomic_add((u64 *)a.requeue_total + 3, (u64)1); pm2_atomic_add((u64 *)a.requeue_total + 2, (u64)1);
                         if (failed == 4 && sc()[SC_TMP1] > 2 * CLS) pm2_atomic_add((u64 *)a.requeue_total + 1, (u64)1);      // (how many of them would not fit twice the classes either)
                     }
                 }
@@ -2307,7 +2307,7 @@ struct Sweep2 {
             if (!a.err_keep) PM2_G(int, a.err)[chain] = 0;
             if (a.handed) PM2_G(int, a.handed)[chain] = a.sweep_no;
             if (a.requeue_total) {
-                pm2_atomic_add((u64 *)a.requeue_total + 3, (u64)1); pm2_atomic_add((u64 *)a.requeue_total + (fcode - 2), (u64)1);
+                pm2_atomic_add((u64 *)a.requeue_total + 3, (u64)1); pm2_atomic_add((u64 *)a.requeue_total + 2, (u64)1);      // (fcode 3 wide ids, 4 classes: both [2], pmdi_hip.h)
                 if (fcode == 4 && sc()[SC_TMP1] > 2 * CLS) pm2_atomic_add((u64 *)a.requeue_total + 1, (u64)1);
             }
             PM2_G(long long, a.cost)[chain] = PM2_CLOCK() - t_start;

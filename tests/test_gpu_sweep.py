@@ -508,6 +508,9 @@ def test_hand_over_mid_sweep_equals_oracle(pkg, O, kinds, P, N, flags):
     gb = sw.given_back()
     print(f"{'+'.join(kinds)} P={P}: kernels that finished the chain-sweeps {sorted(seen)}; hand-overs {gb.tolist()} of {4 * C} chain-sweeps")
     assert 2 in seen and gb[3] >= 2          # chains were handed over mid-sweep ...
+    # ... and the counters mean what include/pmdi_hip.h says: [0] unused, [2] every hand-over (more classes than the capacity, or
+    # ids beyond 16 bits), [1] those of them with more than twice the capacity, [3] the total
+    assert gb[0] == 0 and gb[2] == gb[3] and 0 <= gb[1] <= gb[2], gb.tolist()
     sw.close()
 
 

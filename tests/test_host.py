@@ -239,3 +239,14 @@ def test_read_allocations_line_endings_and_short_files(pkg, tmp_path):
     from particlemdi_jl_amd.psm import generate_psm
     with pytest.raises(ValueError, match="no rows left"):
         generate_psm(str(p), burnin=7, host=True)
+
+
+def test_unknown_tuning_knob_is_an_error(pkg):
+    """Sweeper(tuning={...}) sets fields of a ctypes Structure, which would take any attribute name: a mistyped knob must raise
+    (before anything touches a device), every real field of pmdi_tuning must be accepted by that check."""
+    x = np.zeros((4, 2))
+    for bad in ("setled", "kspit", "reserved", "Settled"):
+        with pytest.raises(KeyError, match=bad):
+            pkg.Sweeper([x], ["gaussian"], 2, 8, tuning={bad: 0})
+    from particlemdi_jl_amd import _lib
+    assert "settled" in dict(_lib._Tuning._fields_) and "ksplit" in dict(_lib._Tuning._fields_)
