@@ -236,6 +236,51 @@ int pmdi_label_counts_device(pmdi_handle *h, const int32_t *s, int32_t *counts, 
 int pmdi_psm_counts_device(int32_t device, const uint8_t *samples, int64_t S, int32_t K, int64_t n,
                            int64_t row_lo, int64_t row_hi, int32_t n_labels, int32_t *counts, void *stream);
 
+/* ---- get_consensus_allocations (src/output_analysis/consensus_map.jl:92-105): hclust + cutree of a PSM on the device ----
+ * hc = hclust(1 .- Symmetric(psm.psm[orderby], :L), linkage = linkage); cutree(hc, k = k) or cutree(hc, h = h).
+ *
+ * pmdi_psm_distance_device: the n x n Float64 distance matrix of psm.psm[which + 1] from the output of
+ * pmdi_psm_counts_device with row_lo = 0, row_hi = n (device int32 [K][n][n]) and the sample count S, in the reference's
+ * order of operations: p_k = count / S (:53); which < K: d = 1.0 - p_k; which == K ("Overall", K > 1 only):
+ * o = 0.0, o += p_k / K for k = 1..K (:59), d = 1.0 - o; diagonal 0; symmetric, both halves written.
+ * Stateless; `device` is the HIP device ordinal; asynchronous on `stream`; n <= 65535.
+ *
+ * pmdi_hclust_device: agglomerative clustering of B distance matrices (device Float64, n x n column-major each, one
+ * after the other) by the nearest-neighbour chain with Lance-Williams updates, one persistent workgroup per matrix.
+ * Only the lower triangle (i > j, at dist[i + n * j]) of every matrix is read: it is checked (a NaN, infinite or
+ * negative distance is PMDI_E_DATA) and mirrored (Symmetric(., :L), :98), then the matrix is the kernel's work space --
+ * the matrices are OVERWRITTEN and the call allocates no n x n scratch of its own (a caller that wants to keep its
+ * matrix passes a copy).  n = 1: no merges.  n <= 65535, B <= 65535.
+ * Linkages (Clustering.jl 0.14.0's; distances, not squared distances, go in), for the merged pair i, j and any other
+ * cluster k with sizes n_i, n_j, n_k:
+ *   SINGLE min(d_ik, d_jk) . COMPLETE max(d_ik, d_jk) . AVERAGE (n_i d_ik + n_j d_jk) / (n_i + n_j) .
+ *   WARD sqrt(((n_i + n_k) d_ik^2 + (n_j + n_k) d_jk^2 - n_k d_ij^2) / (n_i + n_j + n_k)),
+ * in IEEE double arithmetic, evaluated left to right as written with i the lower slot, never fused.
+ * Ties are part of the interface (a PSM over S samples has at most S + 1 distinct distances):
+ *   - every cluster lives in a slot 1..n; observation i starts in slot i; the merged cluster keeps the HIGHER of the
+ *     two slots, the lower one is retired (the update is applied to live slots only);
+ *   - the nearest neighbour of the chain's tip is the live slot at the smallest distance, the LOWEST slot among equals,
+ *     except that the tip's predecessor in the chain wins any tie with that minimum; tip and predecessor are merged when
+ *     the predecessor is the tip's nearest neighbour, and the chain goes on from what is left of it;
+ *   - an empty chain starts at the lowest live slot;
+ *   - the n - 1 merges are sorted by height with a stable sort (chain order breaks ties) and numbered as R's / Julia's
+ *     hclust does: merges (n-1) x 2 column-major Int64, -i for observation i, +r for the cluster made by row r, first
+ *     column the cluster that held the lower slot, second column the one that held the higher slot; heights n - 1;
+ *   - order: the n leaves depth first from the last row, first column before second, so every cluster of the
+ *     dendrogram is a contiguous run of it.
+ * merges_out, heights_out, order_out are HOST arrays (per matrix, one after the other), so the call SYNCHRONISES `stream`
+ * before it returns; the sort, the numbering and the leaf order run on the host, the matrix never leaves the device.
+ *
+ * pmdi_cutree: host-only (no device needed).  k clusters (k = -1: not given; otherwise 1 <= k <= n: the last k - 1
+ * merges are undone) or every merge with height <= h (h = NaN: not given); at least one of them (the @assert of :94), k
+ * wins if both are given (:99-103).  labels_out[i]: 1.. in order of first appearance by observation index. */
+enum { PMDI_LINK_SINGLE = 0, PMDI_LINK_AVERAGE = 1, PMDI_LINK_COMPLETE = 2, PMDI_LINK_WARD = 3 };
+int pmdi_psm_distance_device(int32_t device, const int32_t *counts, int64_t S, int32_t K, int64_t n, int32_t which,
+                             double *dist_out, void *stream);
+int pmdi_hclust_device(int32_t device, double *dist, int32_t B, int64_t n, int32_t linkage, int64_t *merges_out,
+                       double *heights_out, int64_t *order_out, void *stream);
+int pmdi_cutree(int64_t n, const int64_t *merges, const double *heights, int64_t k, double h, int64_t *labels_out);
+
 /* ---- device-resident Gibbs chains -----------------------------------------
  * Everything pmdi() does per iteration AROUND the sweep, for every chain of the handle, without leaving the
  * device: shuffle!(order_obs) (src/pmdi.jl:172), update_M!, update_gamma!, Pi, update_Phi!, update_Z, update_v

@@ -12,7 +12,7 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("PMDI_LIB_PATH") or os.path.join(_PKG, "libpmdi_hip.so")   # override: A/B builds only
-_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_hypers.hip", "pmdi_api.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
+_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_api.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
 _HEADERS = [os.path.join(_PKG, "csrc", "pmdi_internal.h"), os.path.join(_PKG, "csrc", "pmdi_device.h"),
             os.path.join(_PKG, "csrc", "pmdi_sweep_body.h"), os.path.join(_PKG, "csrc", "pmdi_sweep2_body.h"),
             os.path.join(_PKG, "csrc", "pmdi_arith.h"),
@@ -37,6 +37,7 @@ EXPORTS = [
     "pmdi_csv_close", "pmdi_csv_read_allocations", "pmdi_format_float64", "pmdi_work_counters", "pmdi_shader_clock_hz", "pmdi_is_split",
     "pmdi_comm_unique_id", "pmdi_comm_init_rank", "pmdi_comm_init_all", "pmdi_comm_destroy", "pmdi_comm_rank", "pmdi_comm_size",
     "pmdi_allgather_samples", "pmdi_settled_kernel", "pmdi_chain_swept_by", "pmdi_tuning_default", "pmdi_tuning_from_env",
+    "pmdi_psm_distance_device", "pmdi_hclust_device", "pmdi_cutree",
 ]
 
 
@@ -191,6 +192,12 @@ def lib():
     L.pmdi_psm_counts_device.argtypes = [C.c_int32, vp, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, vp, vp]
     L.pmdi_label_counts_device.restype = C.c_int
     L.pmdi_label_counts_device.argtypes = [vp, vp, vp, vp]
+    L.pmdi_psm_distance_device.restype = C.c_int
+    L.pmdi_psm_distance_device.argtypes = [i32, vp, i64, i32, i64, i32, vp, vp]
+    L.pmdi_hclust_device.restype = C.c_int
+    L.pmdi_hclust_device.argtypes = [i32, vp, i32, i64, i32, vp, vp, vp, vp]
+    L.pmdi_cutree.restype = C.c_int
+    L.pmdi_cutree.argtypes = [i64, vp, vp, i64, dbl, vp]
     L.pmdi_chain_costs.restype = C.c_int
     L.pmdi_chain_costs.argtypes = [vp, vp]
     L.pmdi_comm_unique_id.restype = C.c_int

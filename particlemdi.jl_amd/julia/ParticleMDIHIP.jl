@@ -307,6 +307,42 @@ function read_allocations(outputFile::String, burnin::Int64 = 0, thin::Int64 = 1
     return samples, split(unsafe_string(pointer(names)), '\n')
 end
 
+# ---- get_consensus_allocations (src/output_analysis/consensus_map.jl:92-105) on the device ----------------------
+# (like the rest of this file: written against include/pmdi_hip.h, not executed -- there is no Julia where this was built)
+const LINKAGES = Dict(:single => Int32(0), :average => Int32(1), :complete => Int32(2), :ward => Int32(3))
+
+struct Hclust
+    merges::Matrix{Int64}      # (n-1) x 2: -i observation i, +r the cluster made by row r
+    heights::Vector{Float64}
+    order::Vector{Int64}
+end
+
+# dist: device pointer to B distance matrices (n x n Float64 each; the lower triangle is read, the matrices are overwritten)
+function hclust_device(dist::Ptr{Cvoid}, n::Integer, B::Integer = 1; linkage::Symbol = :ward, device::Integer = 0,
+                       stream::Ptr{Cvoid} = C_NULL)
+    merges = Array{Int64, 3}(undef, max(n - 1, 0), 2, B); heights = Matrix{Float64}(undef, max(n - 1, 0), B)
+    order = Matrix{Int64}(undef, n, B)
+    check(ccall((:pmdi_hclust_device, LIB), Cint,
+                (Int32, Ptr{Cvoid}, Int32, Int64, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}),
+                device, dist, B, n, LINKAGES[linkage], merges, heights, order, stream))
+    return [Hclust(merges[:, :, b], heights[:, b], order[:, b]) for b in 1:B]
+end
+
+# counts: device pointer to the Int32 [K][n][n] output of pmdi_psm_counts_device (row_lo = 0, row_hi = n); which is 1-based,
+# K + 1 = "Overall"; dist_out: device memory for n x n Float64
+psm_distance_device(counts::Ptr{Cvoid}, S::Integer, K::Integer, n::Integer, which::Integer, dist_out::Ptr{Cvoid};
+                    device::Integer = 0, stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:pmdi_psm_distance_device, LIB), Cint, (Int32, Ptr{Cvoid}, Int64, Int32, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
+                device, counts, S, K, n, which - 1, dist_out, stream))
+
+function cutree(hc::Hclust; k::Union{Int64, Nothing} = nothing, h::Union{Float64, Nothing} = nothing)
+    n = length(hc.order)
+    labels = Vector{Int64}(undef, n)
+    check(ccall((:pmdi_cutree, LIB), Cint, (Int64, Ptr{Int64}, Ptr{Float64}, Int64, Float64, Ptr{Int64}),
+                n, hc.merges, hc.heights, k === nothing ? -1 : k, h === nothing ? NaN : h, labels))
+    return labels
+end
+
 # ---- the cluster plugin protocol on the device (unit-level entry points) ----------------------
 # calc_logprob / cluster_add! / calc_logmarginal for a batch of stand-alone clusters of dataset k;
 # see pmdi_clusters_new, pmdi_cluster_add, pmdi_calc_logprob, pmdi_calc_logmarginal in the header.

@@ -5,6 +5,10 @@ turned into the posterior-similarity matrix of generate_psm (consensus_map.jl:31
 diagonal 1; for K > 1 an extra "Overall" matrix = mean of the K matrices.
 
 Chains are independent, so this is the ONLY collective of the path.
+
+What a user wants from that matrix comes next in the same file of the reference: get_consensus_allocations
+(consensus_map.jl:92-105) = cutree(hclust(1 .- Symmetric(psm, :L))), here on the device (hclust, cutree,
+get_consensus_allocations below; include/pmdi_hip.h states the tie rule).
 """
 import numpy as np
 
@@ -86,6 +90,118 @@ class PosteriorSimilarityMatrix:
 
     def __init__(self, psm, names):
         self.psm, self.names = psm, names
+
+
+class PsmCounts:
+    """The device-resident form of a posterior-similarity matrix: `counts` = the int32 CUDA tensor (K, n, n) of
+    psm_counts_device(samples, 0, n), `S` = the number of pooled samples behind it.  get_consensus_allocations takes it in
+    place of a PosteriorSimilarityMatrix, so a run that never wrote a CSV needs no round trip through the host."""
+
+    def __init__(self, counts, S, names=None):
+        self.counts, self.S, self.names = counts, int(S), names
+
+
+LINKAGES = {"single": 0, "average": 1, "complete": 2, "ward": 3}       # PMDI_LINK_* of include/pmdi_hip.h
+
+
+class HClust:
+    """What hclust returns: `merges` (n-1, 2) int64 in the hclust convention (-i observation i, +r the cluster made by row r),
+    `heights` (n-1,) non-decreasing, `order` (n,) 1-based leaf order in which every cluster is a contiguous run."""
+
+    def __init__(self, merges, heights, order, linkage="ward"):
+        self.merges, self.heights, self.order, self.linkage = merges, heights, order, linkage
+
+
+def psm_distance_device(counts, S, which):
+    """1 .- Symmetric(psm.psm[which + 1], :L) (consensus_map.jl:98) from device-resident co-clustering counts: counts is the
+    int32 CUDA tensor (K, n, n) of psm_counts_device(samples, 0, n); which = K is the "Overall" matrix (K > 1).  Returns a
+    float64 CUDA tensor (n, n), symmetric with a zero diagonal (libpmdi_hip.so, pmdi_psm_distance_device)."""
+    import ctypes as C
+    import torch
+    from ._lib import _check, lib
+    if not counts.is_cuda or counts.dtype != torch.int32 or counts.dim() != 3 or counts.shape[1] != counts.shape[2]:
+        raise ValueError("psm_distance_device needs the int32 CUDA tensor (K, n, n) of psm_counts_device(samples, 0, n)")
+    cnt = counts.contiguous()
+    K, n, _ = cnt.shape
+    out = torch.empty((n, n), dtype=torch.float64, device=cnt.device)
+    st = torch.cuda.current_stream(cnt.device)
+    _check(lib().pmdi_psm_distance_device(cnt.device.index or 0, C.c_void_p(cnt.data_ptr()), int(S), K, n, int(which),
+                                          C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream)))
+    return out
+
+
+def hclust(dist, linkage="ward", overwrite=False):
+    """hclust(dist, linkage = ...) of the reference's clustering package on the MI355X (pmdi_hclust_device: nearest-neighbour
+    chain, one workgroup per matrix; the tie rule is in include/pmdi_hip.h).  dist: an (n, n) distance matrix -- numpy
+    (uploaded once) or a float64 CUDA tensor -- or a CUDA tensor (B, n, n) of B matrices clustered in one launch (a list of
+    HClust comes back).  Only the lower triangle dist[..., i, j], i > j, is read (Symmetric(., :L)).  The input is left
+    alone unless overwrite=True, which hands a contiguous, already SYMMETRIC CUDA tensor to the kernel as its work space.
+    There is no CPU path: without a device this raises."""
+    import ctypes as C
+    import torch
+    from ._lib import _check, _ptr, lib
+    if linkage not in LINKAGES:
+        raise ValueError(f"linkage {linkage!r} is not one of {sorted(LINKAGES)}")
+    if isinstance(dist, np.ndarray):
+        if not torch.cuda.is_available():
+            raise RuntimeError("hclust: no MI355X visible (there is no CPU path)")
+        dist, overwrite = torch.from_numpy(np.asarray(dist, dtype=np.float64)).cuda(), False
+    if not dist.is_cuda or dist.dtype != torch.float64 or dist.dim() not in (2, 3) or dist.shape[-1] != dist.shape[-2]:
+        raise ValueError("hclust needs an (n, n) or (B, n, n) float64 matrix (numpy, or a CUDA tensor)")
+    single = dist.dim() == 2
+    # the library reads column-major lower triangles: element (i, j), i > j, at [j, i] of a row-major tensor
+    work = dist if overwrite and dist.is_contiguous() else dist.transpose(-1, -2).clone(memory_format=torch.contiguous_format)
+    B, n = (1 if single else work.shape[0]), work.shape[-1]
+    merges = np.zeros((B, 2, max(n - 1, 0)), dtype=np.int64)
+    heights = np.zeros((B, max(n - 1, 0)), dtype=np.float64)
+    order = np.zeros((B, n), dtype=np.int64)
+    st = torch.cuda.current_stream(work.device)
+    _check(lib().pmdi_hclust_device(work.device.index or 0, C.c_void_p(work.data_ptr()), B, n, LINKAGES[linkage],
+                                    _ptr(merges), _ptr(heights), _ptr(order), C.c_void_p(st.cuda_stream)))
+    out = [HClust(np.ascontiguousarray(merges[b].T), heights[b], order[b], linkage) for b in range(B)]
+    return out[0] if single else out
+
+
+def cutree(hc, k=None, h=None):
+    """cutree(hc, k = k) / cutree(hc, h = h): labels 1.. (numbered in order of first appearance by observation index) of the
+    k clusters left when the last k - 1 merges are undone, or of the clusters made by the merges with height <= h; k wins
+    when both are given (consensus_map.jl:99-103).  Host-only (pmdi_cutree)."""
+    from ._lib import _check, _ptr, lib
+    n = len(hc.order)
+    merges = np.ascontiguousarray(np.asarray(hc.merges, dtype=np.int64).reshape(n - 1, 2).T)       # column-major (n-1) x 2
+    heights = np.ascontiguousarray(hc.heights, dtype=np.float64)
+    labels = np.zeros(n, dtype=np.int64)
+    _check(lib().pmdi_cutree(n, _ptr(merges), _ptr(heights), -1 if k is None else int(k), float("nan") if h is None else float(h),
+                             _ptr(labels)))
+    return labels
+
+
+def get_consensus_allocations(psm, k=None, h=None, linkage="ward", orderby=0, device=None):
+    """get_consensus_allocations(psm; k, h, linkage = :ward, orderby) of src/output_analysis/consensus_map.jl:92-105: the
+    consensus clustering, cutree(hclust(1 .- Symmetric(psm.psm[orderby], :L), linkage), k or h); orderby is 1-based and 0
+    means the last matrix ("Overall" when K > 1).  psm: the PosteriorSimilarityMatrix of generate_psm (the chosen host
+    matrix is uploaded once) or a PsmCounts (everything stays on the device).  Returns int64 labels 1.. (n,)."""
+    import torch
+    if k is None and h is None:
+        raise ValueError("You must specify either k (number of clusters) or h (height to cut dendrogram)")
+    if isinstance(psm, PsmCounts):
+        K = psm.counts.shape[0]
+        n_mat = K + (1 if K > 1 else 0)
+        which = (n_mat if orderby == 0 else int(orderby)) - 1
+        if not 0 <= which < n_mat:
+            raise ValueError(f"orderby={orderby}: there are {n_mat} matrices")
+        hc = hclust(psm_distance_device(psm.counts, psm.S, which), linkage, overwrite=True)
+    else:
+        which = (len(psm.psm) if orderby == 0 else int(orderby)) - 1
+        if not 0 <= which < len(psm.psm):
+            raise ValueError(f"orderby={orderby}: there are {len(psm.psm)} matrices")
+        if not torch.cuda.is_available():
+            raise RuntimeError("get_consensus_allocations: no MI355X visible (there is no CPU path)")
+        m = psm.psm[which]
+        t = (torch.from_numpy(np.asarray(m, dtype=np.float64)) if isinstance(m, np.ndarray) else m).to(
+            torch.device("cuda", 0 if device is None else int(device)))
+        hc = hclust(1.0 - t, linkage)
+    return cutree(hc, k=k, h=h)
 
 
 def generate_psm(outputFile, burnin=0, thin=1, host=False, device=None):
