@@ -321,6 +321,51 @@ int pmdi_gibbs_set(pmdi_gibbs *g, int32_t chain, const double *M, const double *
  * pmdi_sweep_stats), err per chain, p_star 1-based, logweight n_chains x P.  Fails if a chain reported an error. */
 int pmdi_gibbs_results(pmdi_gibbs *g, int64_t *stats, int32_t *err, int64_t *p_star, double *logweight);
 
+/* ---- streaming PSM accumulator: pool the chains of a device-resident run without keeping their samples ----
+ * The co-clustering counts are additive over samples, so K * n * n int32 that take every retained iteration's
+ * allocations as they are produced replace the n_iter x n_chains x K x n sample buffer of pmdi_gibbs_iterate and the
+ * one-shot, overwriting pmdi_psm_counts_device.  One accumulator lives on one device.  Like every handle here it is not
+ * thread-safe, and all calls on one accumulator must be issued on ONE stream or be ordered by the caller: an add is a
+ * plain read-modify-write of the counts (every tile is owned by one workgroup of a launch; no atomics).  Everything is
+ * asynchronous on `stream` except create / destroy.  All arithmetic is integer: every result is exact.
+ *
+ * create: 1 <= K <= PMDI_KMAX, 1 <= n <= 65535 (the limit of pmdi_psm_distance_device), 0 <= n_labels <= 255 are checked
+ *   before the device is touched (PMDI_E_ARG); no usable device is PMDI_E_DEVICE.  n_labels as in pmdi_psm_counts_device:
+ *   every label is < n_labels, 1..64 selects the matrix-core kernel, 0 (unknown) or > 64 the byte compares; a label >= a
+ *   non-zero n_labels is a caller error whose matches are not counted.  The counts start at zero.
+ * add_samples: samples = device uint8 [S][K][n], the layout of pmdi_psm_counts_device; counts[k][i][j] += #{t : s_t[k][i] ==
+ *   s_t[k][j]}.  Only the 128 x 128 (64 x 64 for byte compares) tiles with block-row >= block-column are computed; the upper
+ *   triangle is filled by pmdi_psm_acc_counts.
+ * add_gibbs: the current allocations of every chain of g (n_chains samples), packed into a buffer the accumulator
+ *   allocates at its first use.  PMDI_E_ARG unless g's K and n are the accumulator's and, when n_labels != 0, its N <= n_labels.
+ * merge: counts += other counts (device int32 [K][n][n] on the accumulator's device, of which only i >= j is read: a
+ *   pmdi_psm_counts_device result, or another accumulator's counts), S += its S.  Pools accumulators of several handles or,
+ *   after a copy, of several GPUs.
+ * S is an int32 count per pair: an add or merge that would take S past INT32_MAX is PMDI_E_ARG and adds nothing.
+ * counts: mirrors the lower triangle into the upper one if anything was added since the last call, and returns the device
+ *   pointer [K][n][n]: full, symmetric, diagonal = S -- what pmdi_psm_distance_device takes.  The pointer stays valid (and
+ *   keeps changing with later adds) until destroy.
+ * reset: counts = 0, S = 0. */
+typedef struct pmdi_psm_acc pmdi_psm_acc;
+int pmdi_psm_acc_create(int32_t device, int32_t K, int64_t n, int32_t n_labels, pmdi_psm_acc **out);
+int pmdi_psm_acc_destroy(pmdi_psm_acc *a);
+int pmdi_psm_acc_reset(pmdi_psm_acc *a, void *stream);
+int pmdi_psm_acc_add_samples(pmdi_psm_acc *a, const uint8_t *samples, int64_t S, void *stream);
+int pmdi_psm_acc_add_gibbs(pmdi_psm_acc *a, pmdi_gibbs *g, void *stream);
+int pmdi_psm_acc_merge(pmdi_psm_acc *a, const int32_t *counts, int64_t S, void *stream);
+int64_t pmdi_psm_acc_samples(const pmdi_psm_acc *a);
+int pmdi_psm_acc_counts(pmdi_psm_acc *a, const int32_t **counts, int64_t *S, void *stream);
+
+/* pmdi_gibbs_iterate with a retention rule in place of the sample buffer: n_iter iterations (the same steps in the same
+ * order) and, after local iteration t = 1 .. n_iter, pmdi_psm_acc_add_gibbs(acc, g) iff t > burnin and
+ * (t - burnin - 1) % thin == 0.  burnin >= 0 iterations are discarded, thin >= 1; acc may be NULL (then this is
+ * pmdi_gibbs_iterate without samples).  The accumulator is checked against g, and the retained samples against the
+ * INT32_MAX limit of S, before the first iteration runs.
+ * Relation to the reference: a CSV written by pmdi(..., thin = 1) holds the state after iterations 0 .. iter (row 0 is the
+ * initial state, src/pmdi.jl:158), so this rule keeps exactly the rows that generate_psm(file, burnin + 1, thin) keeps
+ * (src/output_analysis/consensus_map.jl:33,38). */
+int pmdi_gibbs_run(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, void *stream);
+
 /* Device pointers of the resident state (zero-copy consumers; layouts of pmdi_sweep_device). */
 typedef struct {
     double *M, *gamma, *gamma0, *Phi, *vZ, *Pi, *log1p_phi, *feature_prob, *logweight;

@@ -8,3 +8,5 @@ from ._lib import (  # noqa: F401
     ClusterBatch, Comm, CsvWriter, Gibbs, format_float64, read_allocations, PmdiError, Sweeper, build, lib,
     STEP_ALIGN, STEP_BEGIN, STEP_FEATSEL, STEP_HYPERS, STEP_SWEEP,
 )
+from .pmdi import pmdi_pooled  # noqa: F401,E402    (not pmdi(): the name is the submodule's)
+from .psm import PsmAccumulator, PsmCounts, retained_iterations  # noqa: F401,E402

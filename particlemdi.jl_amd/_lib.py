@@ -12,7 +12,7 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("PMDI_LIB_PATH") or os.path.join(_PKG, "libpmdi_hip.so")   # override: A/B builds only
-_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_api.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
+_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_api.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
 _HEADERS = [os.path.join(_PKG, "csrc", "pmdi_internal.h"), os.path.join(_PKG, "csrc", "pmdi_device.h"),
             os.path.join(_PKG, "csrc", "pmdi_sweep_body.h"), os.path.join(_PKG, "csrc", "pmdi_sweep2_body.h"),
             os.path.join(_PKG, "csrc", "pmdi_arith.h"),
@@ -38,6 +38,8 @@ EXPORTS = [
     "pmdi_comm_unique_id", "pmdi_comm_init_rank", "pmdi_comm_init_all", "pmdi_comm_destroy", "pmdi_comm_rank", "pmdi_comm_size",
     "pmdi_allgather_samples", "pmdi_settled_kernel", "pmdi_chain_swept_by", "pmdi_tuning_default", "pmdi_tuning_from_env",
     "pmdi_psm_distance_device", "pmdi_hclust_device", "pmdi_cutree",
+    "pmdi_psm_acc_create", "pmdi_psm_acc_destroy", "pmdi_psm_acc_reset", "pmdi_psm_acc_add_samples", "pmdi_psm_acc_add_gibbs",
+    "pmdi_psm_acc_merge", "pmdi_psm_acc_samples", "pmdi_psm_acc_counts", "pmdi_gibbs_run",
 ]
 
 
@@ -198,6 +200,23 @@ def lib():
     L.pmdi_hclust_device.argtypes = [i32, vp, i32, i64, i32, vp, vp, vp, vp]
     L.pmdi_cutree.restype = C.c_int
     L.pmdi_cutree.argtypes = [i64, vp, vp, i64, dbl, vp]
+    L.pmdi_psm_acc_create.restype = C.c_int
+    L.pmdi_psm_acc_create.argtypes = [i32, i32, i64, i32, C.POINTER(vp)]
+    L.pmdi_psm_acc_destroy.argtypes = [vp]
+    L.pmdi_psm_acc_reset.restype = C.c_int
+    L.pmdi_psm_acc_reset.argtypes = [vp, vp]
+    L.pmdi_psm_acc_add_samples.restype = C.c_int
+    L.pmdi_psm_acc_add_samples.argtypes = [vp, vp, i64, vp]
+    L.pmdi_psm_acc_add_gibbs.restype = C.c_int
+    L.pmdi_psm_acc_add_gibbs.argtypes = [vp, vp, vp]
+    L.pmdi_psm_acc_merge.restype = C.c_int
+    L.pmdi_psm_acc_merge.argtypes = [vp, vp, i64, vp]
+    L.pmdi_psm_acc_samples.restype = i64
+    L.pmdi_psm_acc_samples.argtypes = [vp]
+    L.pmdi_psm_acc_counts.restype = C.c_int
+    L.pmdi_psm_acc_counts.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), vp]
+    L.pmdi_gibbs_run.restype = C.c_int
+    L.pmdi_gibbs_run.argtypes = [vp, i64, i64, i64, vp, vp]
     L.pmdi_chain_costs.restype = C.c_int
     L.pmdi_chain_costs.argtypes = [vp, vp]
     L.pmdi_comm_unique_id.restype = C.c_int
@@ -562,6 +581,12 @@ class Gibbs:
     def iterate(self, n_iter=1, samples_ptr=None, stream=None):
         _check(lib().pmdi_gibbs_iterate(self.h, int(n_iter), C.c_void_p(samples_ptr) if samples_ptr else None,
                                         C.c_void_p(stream) if stream else None))
+
+    def run(self, n_iter, burnin=0, thin=1, acc=None, stream=None):
+        """pmdi_gibbs_run: n_iter iterations; after local iteration t = 1..n_iter the allocations of every chain are added to
+        `acc` (a psm.PsmAccumulator) iff t > burnin and (t - burnin - 1) % thin == 0 (psm.retained_iterations)."""
+        _check(lib().pmdi_gibbs_run(self.h, int(n_iter), int(burnin), int(thin), acc.h if acc is not None else None,
+                                    C.c_void_p(stream) if stream else None))
 
     def pack_samples(self, out_ptr, stream=None):
         _check(lib().pmdi_gibbs_pack_samples(self.h, C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))

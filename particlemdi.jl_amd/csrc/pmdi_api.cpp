@@ -200,6 +200,17 @@ struct pmdi_gibbs {
     std::vector<void *> owned;
 };
 
+// Streaming PSM accumulator (pmdi_psm_acc_* entry points)
+struct pmdi_psm_acc {
+    int device = 0, K = 0, n_labels = 0;
+    long long n = 0;
+    int *counts = nullptr;               // [K][n][n]; the strict upper triangle is current only while !dirty
+    unsigned char *pack = nullptr;       // [n_chains][K][n] label bytes of pmdi_psm_acc_add_gibbs, allocated at first use
+    size_t pack_bytes = 0;
+    int64_t S = 0;                       // samples behind the counts
+    bool dirty = false;                  // something was added since the last mirror
+};
+
 namespace {
 
 int dev_alloc(pmdi_handle *h, void **p, size_t bytes)
@@ -919,6 +930,122 @@ int pmdi_psm_counts_device(int32_t device, const uint8_t *samples, int64_t S, in
     return PMDI_OK;
 }
 
+int pmdi_psm_acc_destroy(pmdi_psm_acc *a)
+{
+    if (!a) return PMDI_OK;
+    (void)hipSetDevice(a->device);
+    (void)hipDeviceSynchronize();
+    if (a->counts) (void)hipFree(a->counts);
+    if (a->pack) (void)hipFree(a->pack);
+    delete a;
+    return PMDI_OK;
+}
+
+int pmdi_psm_acc_create(int32_t device, int32_t K, int64_t n, int32_t n_labels, pmdi_psm_acc **out)
+{
+    if (!out) return fail(PMDI_E_ARG, "null argument");
+    *out = nullptr;
+    if (K < 1 || K > PMDI_KMAX_I) return fail(PMDI_E_ARG, "K=%d outside 1..%d", K, PMDI_KMAX_I);
+    if (n < 1 || n > 65535) return fail(PMDI_E_ARG, "n=%lld outside 1..65535", (long long)n);
+    if (n_labels < 0 || n_labels > 255) return fail(PMDI_E_ARG, "n_labels=%d outside 0..255", n_labels);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(PMDI_E_DEVICE, "no HIP device visible (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(PMDI_E_DEVICE, "device %d not in 0..%d", device, ndev - 1);
+    HIP_TRY(hipSetDevice(device));
+    pmdi_psm_acc *a = new (std::nothrow) pmdi_psm_acc();
+    if (!a) return fail(PMDI_E_MEMORY, "out of host memory");
+    a->device = device; a->K = K; a->n = n; a->n_labels = n_labels;
+    const size_t bytes = (size_t)K * n * n * 4;
+    hipError_t e = hipMalloc((void **)&a->counts, bytes);
+    if (e != hipSuccess) { a->counts = nullptr; pmdi_psm_acc_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e)); }
+    if (hipMemset(a->counts, 0, bytes) != hipSuccess) { pmdi_psm_acc_destroy(a); return fail(PMDI_E_DEVICE, "hipMemset failed"); }
+    *out = a;
+    return PMDI_OK;
+}
+
+int pmdi_psm_acc_reset(pmdi_psm_acc *a, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipMemsetAsync(a->counts, 0, (size_t)a->K * a->n * a->n * 4, (hipStream_t)stream));
+    a->S = 0; a->dirty = false;
+    return PMDI_OK;
+}
+
+int pmdi_psm_acc_add_samples(pmdi_psm_acc *a, const uint8_t *samples, int64_t S, void *stream)
+{
+    if (!a || (!samples && S != 0)) return fail(PMDI_E_ARG, "null argument");
+    if (S < 0) return fail(PMDI_E_ARG, "S=%lld < 0", (long long)S);
+    if (S > 2147483647LL - a->S) return fail(PMDI_E_ARG, "%lld + %lld samples overflow the int32 counts", (long long)a->S, (long long)S);
+    if (S == 0) return PMDI_OK;
+    HIP_TRY(hipSetDevice(a->device));
+    hipError_t e = pmdi_launch_psm_acc_add(samples, S, a->K, a->n, a->n_labels, a->counts, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "psm-accumulate launch: %s", hipGetErrorString(e));
+    a->S += S; a->dirty = true;
+    return PMDI_OK;
+}
+
+// what pmdi_psm_acc_add_gibbs checks before it touches anything (pmdi_gibbs_run asks once, before its first iteration)
+static int psm_acc_accepts(const pmdi_psm_acc *a, const pmdi_gibbs *g, int64_t n_adds)
+{
+    const pmdi_config &c = g->h->cfg;
+    if (c.K != a->K || c.n != a->n)
+        return fail(PMDI_E_ARG, "the accumulator holds K=%d n=%lld, the chains K=%d n=%lld", a->K, a->n, c.K, (long long)c.n);
+    if (a->n_labels != 0 && c.N > a->n_labels) return fail(PMDI_E_ARG, "the chains use N=%d labels, the accumulator n_labels=%d", c.N, a->n_labels);
+    if (c.device != a->device) return fail(PMDI_E_ARG, "the chains live on device %d, the accumulator on device %d", c.device, a->device);
+    if (n_adds > (2147483647LL - a->S) / c.n_chains)
+        return fail(PMDI_E_ARG, "%lld + %lld x %d samples overflow the int32 counts", (long long)a->S, (long long)n_adds, c.n_chains);
+    return PMDI_OK;
+}
+
+int pmdi_psm_acc_add_gibbs(pmdi_psm_acc *a, pmdi_gibbs *g, void *stream)
+{
+    if (!a || !g) return fail(PMDI_E_ARG, "null argument");
+    const int rc = psm_acc_accepts(a, g, 1);
+    if (rc) return rc;
+    const pmdi_config &c = g->h->cfg;
+    const size_t per = (size_t)c.n_chains * c.K * c.n;
+    HIP_TRY(hipSetDevice(a->device));
+    if (per > a->pack_bytes) {            // (first use, or a handle with more chains than the last one: the old buffer may still be read)
+        if (a->pack) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(a->pack); a->pack = nullptr; a->pack_bytes = 0; }
+        hipError_t e = hipMalloc((void **)&a->pack, per);
+        if (e != hipSuccess) { a->pack = nullptr; return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", per, hipGetErrorString(e)); }
+        a->pack_bytes = per;
+    }
+    hipError_t e = pmdi_launch_pack_samples(g->ga.s, a->pack, (long long)per, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "pack-samples launch: %s", hipGetErrorString(e));
+    return pmdi_psm_acc_add_samples(a, a->pack, c.n_chains, stream);
+}
+
+int pmdi_psm_acc_merge(pmdi_psm_acc *a, const int32_t *counts, int64_t S, void *stream)
+{
+    if (!a || !counts) return fail(PMDI_E_ARG, "null argument");
+    if (S < 0) return fail(PMDI_E_ARG, "S=%lld < 0", (long long)S);
+    if (S > 2147483647LL - a->S) return fail(PMDI_E_ARG, "%lld + %lld samples overflow the int32 counts", (long long)a->S, (long long)S);
+    HIP_TRY(hipSetDevice(a->device));
+    hipError_t e = pmdi_launch_psm_acc_merge(a->counts, counts, a->K, a->n, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "psm-merge launch: %s", hipGetErrorString(e));
+    a->S += S; a->dirty = true;
+    return PMDI_OK;
+}
+
+int64_t pmdi_psm_acc_samples(const pmdi_psm_acc *a) { return a ? a->S : 0; }
+
+int pmdi_psm_acc_counts(pmdi_psm_acc *a, const int32_t **counts, int64_t *S, void *stream)
+{
+    if (!a || !counts) return fail(PMDI_E_ARG, "null argument");
+    if (a->dirty) {
+        HIP_TRY(hipSetDevice(a->device));
+        hipError_t e = pmdi_launch_psm_acc_mirror(a->counts, a->K, a->n, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(PMDI_E_DEVICE, "psm-mirror launch: %s", hipGetErrorString(e));
+        a->dirty = false;
+    }
+    *counts = a->counts;
+    if (S) *S = a->S;
+    return PMDI_OK;
+}
+
 int pmdi_label_counts_device(pmdi_handle *h, const int32_t *s, int32_t *counts, void *stream)
 {
     if (!h || !s || !counts) return fail(PMDI_E_ARG, "null argument");
@@ -1384,6 +1511,27 @@ int pmdi_gibbs_iterate(pmdi_gibbs *g, int64_t n_iter, uint8_t *samples, void *st
             hipError_t e = pmdi_launch_pack_samples(g->ga.s, samples + (size_t)t * per, per, (hipStream_t)stream);
             if (e != hipSuccess) return fail(PMDI_E_DEVICE, "pack-samples launch: %s", hipGetErrorString(e));
         }
+    }
+    return PMDI_OK;
+}
+
+int pmdi_gibbs_run(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, void *stream)
+{
+    if (!g || n_iter < 0) return fail(PMDI_E_ARG, "bad argument");
+    if (burnin < 0 || thin < 1) return fail(PMDI_E_ARG, "burnin=%lld must be >= 0 and thin=%lld >= 1", (long long)burnin, (long long)thin);
+    if (acc) {
+        const int64_t kept = n_iter > burnin ? (n_iter - burnin - 1) / thin + 1 : 0;
+        const int rc = psm_acc_accepts(acc, g, kept);
+        if (rc) return rc;
+    }
+    for (int64_t t = 1; t <= n_iter; ++t) {
+        int rc;
+        if ((rc = pmdi_gibbs_step(g, PMDI_STEP_BEGIN, stream)) || (rc = pmdi_gibbs_step(g, PMDI_STEP_HYPERS, stream)) ||
+            (rc = pmdi_gibbs_step(g, PMDI_STEP_SWEEP, stream)))
+            return rc;
+        if (g->feature_select && (rc = pmdi_gibbs_step(g, PMDI_STEP_FEATSEL, stream))) return rc;
+        if ((rc = pmdi_gibbs_step(g, PMDI_STEP_ALIGN, stream))) return rc;
+        if (acc && t > burnin && (t - burnin - 1) % thin == 0 && (rc = pmdi_psm_acc_add_gibbs(acc, g, stream))) return rc;
     }
     return PMDI_OK;
 }

@@ -232,3 +232,7 @@ hipError_t pmdi_launch_psm_counts(const unsigned char *samples, long long S, int
 hipError_t pmdi_launch_psm_counts_mfma(const unsigned char *samples, long long S, int K, long long n, long long row_lo, long long row_hi,
                                        int n_labels, int *counts, hipStream_t stream);
 hipError_t pmdi_launch_label_counts(const int *s, int *counts, int n_rows, long long n, int N, hipStream_t stream);
+// the streaming PSM accumulator (pmdi_psm_acc.hip): counts [K][n][n]; add touches the tiles with block-row >= block-column only
+hipError_t pmdi_launch_psm_acc_add(const unsigned char *samples, long long S, int K, long long n, int n_labels, int *counts, hipStream_t stream);
+hipError_t pmdi_launch_psm_acc_mirror(int *counts, int K, long long n, hipStream_t stream);
+hipError_t pmdi_launch_psm_acc_merge(int *a, const int *b, int K, long long n, hipStream_t stream);

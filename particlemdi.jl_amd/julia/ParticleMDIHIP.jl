@@ -292,6 +292,88 @@ function pmdi_device(dataFiles, dataTypes, N::Int64, particles::Int64, ρ::Float
     return
 end
 
+# ---- streaming PSM accumulator and pooled runs (include/pmdi_hip.h, pmdi_psm_acc_*, pmdi_gibbs_run) --------------
+# (like the rest of this file: written against include/pmdi_hip.h, not executed -- there is no Julia where this was built)
+function psm_acc_create(K::Integer, n::Integer; n_labels::Integer = 0, device::Integer = 0)
+    a = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pmdi_psm_acc_create, LIB), Cint, (Int32, Int32, Int64, Int32, Ref{Ptr{Cvoid}}), device, K, n, n_labels, a))
+    return a[]
+end
+psm_acc_destroy(a::Ptr{Cvoid}) = ccall((:pmdi_psm_acc_destroy, LIB), Cint, (Ptr{Cvoid},), a)
+psm_acc_reset(a::Ptr{Cvoid}; stream::Ptr{Cvoid} = C_NULL) = check(ccall((:pmdi_psm_acc_reset, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), a, stream))
+# samples: device pointer to UInt8 [S][K][n]
+psm_acc_add_samples(a::Ptr{Cvoid}, samples::Ptr{Cvoid}, S::Integer; stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:pmdi_psm_acc_add_samples, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}), a, samples, S, stream))
+psm_acc_add_gibbs(a::Ptr{Cvoid}, g::Ptr{Cvoid}; stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:pmdi_psm_acc_add_gibbs, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), a, g, stream))
+# counts: device pointer to Int32 [K][n][n] on the accumulator's device (only i >= j is read)
+psm_acc_merge(a::Ptr{Cvoid}, counts::Ptr{Cvoid}, S::Integer; stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:pmdi_psm_acc_merge, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}), a, counts, S, stream))
+psm_acc_samples(a::Ptr{Cvoid}) = ccall((:pmdi_psm_acc_samples, LIB), Int64, (Ptr{Cvoid},), a)
+# -> (device pointer to the full, symmetric Int32 [K][n][n], S): what psm_distance_device takes
+function psm_acc_counts(a::Ptr{Cvoid}; stream::Ptr{Cvoid} = C_NULL)
+    counts = Ref{Ptr{Cvoid}}(C_NULL); S = Ref{Int64}(0)
+    check(ccall((:pmdi_psm_acc_counts, LIB), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Int64}, Ptr{Cvoid}), a, counts, S, stream))
+    return counts[], S[]
+end
+gibbs_run(g::Ptr{Cvoid}, n_iter::Integer; burnin::Integer = 0, thin::Integer = 1, acc::Ptr{Cvoid} = C_NULL, stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:pmdi_gibbs_run, LIB), Cint, (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}), g, n_iter, burnin, thin, acc, stream))
+
+"""
+    pmdi_pooled(dataFiles, dataTypes, N, particles, ρ, iter, n_chains; burnin = 0, thin = 1, featureSelect = false,
+                seed = rand(UInt64), device = 0, q2_mode = 0) -> (acc, counts, S)
+
+`n_chains` independent chains on one MI355X, pooled on the device: after local iteration t > burnin with
+(t - burnin - 1) % thin == 0 the allocations of every chain go into one streaming accumulator -- the rows
+generate_psm(file, burnin + 1, thin) would keep of each chain's CSV, without the CSVs.  Returns the accumulator (the caller
+destroys it with psm_acc_destroy when done with the counts), the device pointer to the Int32 [K][n][n] counts and S; hand the
+last two to psm_distance_device / hclust_device / cutree.  Writes no files.  Untested twin of pmdi.py's pmdi_pooled.
+"""
+function pmdi_pooled(dataFiles, dataTypes, N::Int64, particles::Int64, ρ::Float64, iter::Int64, n_chains::Int64;
+                     burnin::Int64 = 0, thin::Int64 = 1, featureSelect::Bool = false, seed::UInt64 = rand(UInt64),
+                     device::Integer = 0, q2_mode::Integer = 0)
+    kinds = [device_kind(t) for t in dataTypes]
+    @assert all(k -> k >= 0, kinds) "pmdi_pooled needs cluster types with a device kernel"
+    K = length(dataFiles)
+    n_obs = size(dataFiles[1], 1)
+    @assert length(dataTypes) == K "Number of datatypes not equal to number of datasets"
+    @assert all(size(d, 1) == n_obs for d in dataFiles) "Datasets don't have same number of observations. Each row must correspond to the same underlying observational unit across datasets."
+    @assert 0 < ρ < 1 "ρ must be between 0 and 1"
+    @assert 1 < N <= n_obs "Number of clusters must be greater than 1 and not greater than the number of observations"
+    @assert particles > 1 "Conditional particle filter requires 2 or more particles"
+    @assert n_chains >= 1 "n_chains must be >= 1"
+    @assert 0 <= burnin < iter "burnin must be >= 0 and smaller than iter"
+    @assert thin >= 1 "thin must be >= 1"
+    mats = [kinds[k] == 0 ? convert(Matrix{Float64}, dataFiles[k]) : convert(Matrix{Int64}, dataFiles[k]) for k in 1:K]
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve mats begin
+        ds = [CDataset(kinds[k], Int32(size(mats[k], 2)), Int64(n_obs),
+                       kinds[k] == 0 ? pointer(mats[k]) : Ptr{Float64}(C_NULL),
+                       kinds[k] == 0 ? Ptr{Int64}(C_NULL) : pointer(mats[k])) for k in 1:K]
+        cfg = Ref(CConfig(PMDI_ABI_VERSION, Int32(device), Int32(K), Int32(N), Int32(particles), Int32(n_chains),
+                          Int64(n_obs), seed, Int32(0), Int32(q2_mode), Int64(0), Int32(0), Int32(0), C_NULL))
+        check(ccall((:pmdi_create, LIB), Cint, (Ref{CConfig}, Ptr{CDataset}, Ref{Ptr{Cvoid}}), cfg, ds, handle))
+    end
+    h = handle[]
+    g = Ref{Ptr{Cvoid}}(C_NULL)
+    acc = C_NULL
+    try
+        check(ccall((:pmdi_gibbs_create, LIB), Cint, (Ptr{Cvoid}, Float64, Int32, Ref{Ptr{Cvoid}}), h, ρ, featureSelect ? 1 : 0, g))
+        acc = psm_acc_create(K, n_obs; n_labels = N, device = device)
+        gibbs_run(g[], iter; burnin = burnin, thin = thin, acc = acc)
+        check(ccall((:pmdi_gibbs_results, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Ptr{Int64}, Ptr{Float64}),
+                    g[], C_NULL, C_NULL, C_NULL, C_NULL))                        # synchronises; a kernel-side error surfaces here
+        counts, S = psm_acc_counts(acc)
+        return acc, counts, S
+    catch
+        acc == C_NULL || psm_acc_destroy(acc)
+        rethrow()
+    finally
+        g[] == C_NULL || ccall((:pmdi_gibbs_destroy, LIB), Cint, (Ptr{Cvoid},), g[])
+        ccall((:pmdi_destroy, LIB), Cint, (Ptr{Cvoid},), h)
+    end
+end
+
 # ---- generate_psm's reading of an output file (src/output_analysis/consensus_map.jl:32-47), natively ----------
 # returns (samples::Array{UInt8,3} of size (n_obs, K, rows kept) -- i.e. [row][k][i] in C order --, names)
 function read_allocations(outputFile::String, burnin::Int64 = 0, thin::Int64 = 1)

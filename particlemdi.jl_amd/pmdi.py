@@ -39,19 +39,19 @@ def coerce_categorical(data):
     return out
 
 
-def pmdi(dataFiles, dataTypes, N, particles, rho, iter, outputFile, thin=1, featureSelect=None,
-         dataNames=None, seed=0, device=0, q1_mode=0, q2_mode=0, return_state=False):
-    """Runs particleMDI on the given datasets (signature of src/pmdi.jl:36-40 plus the
-    seed/device keywords this implementation needs).  dataTypes entries are
-    "GaussianCluster" / "CategoricalCluster" / "NegBinomCluster" (or the short names)."""
+def _need(cond, msg):
+    if not cond:
+        raise ValueError(msg)
+
+
+def _check_arguments(dataFiles, dataTypes, N, particles, rho, dataNames=None):
+    """The argument checks of src/pmdi.jl:50-55 (@assert in the reference; ValueError here so that `python -O` keeps them),
+    shared by pmdi() and pmdi_pooled().  Returns (K, n_obs, dataNames)."""
     K = len(dataFiles)
     n_obs = int(dataFiles[0].shape[0])
     if dataNames is None:
         dataNames = [f"K{i}" for i in range(1, K + 1)]
-    # src/pmdi.jl:50-55 (@assert in the reference; ValueError here so that `python -O` keeps them)
-    def need(cond, msg):
-        if not cond:
-            raise ValueError(msg)
+    need = _need
     need(len(dataTypes) == K, "Number of datatypes not equal to number of datasets")
     need(len(dataNames) == K, "Number of data names not equal to number of datasets")
     need(all(d.shape[0] == n_obs for d in dataFiles),
@@ -64,6 +64,15 @@ def pmdi(dataFiles, dataTypes, N, particles, rho, iter, outputFile, thin=1, feat
             raise TypeError(f"{t!r} has no device kernel; user-defined cluster types run on the "
                             "reference's own CPU loop (see INTEGRATION.md), not here")
     need(int(np.floor(rho * n_obs)) >= 1, "floor(ρ·n) must be >= 1 (the reference indexes order_obs[0] otherwise)")
+    return K, n_obs, dataNames
+
+
+def pmdi(dataFiles, dataTypes, N, particles, rho, iter, outputFile, thin=1, featureSelect=None,
+         dataNames=None, seed=0, device=0, q1_mode=0, q2_mode=0, return_state=False):
+    """Runs particleMDI on the given datasets (signature of src/pmdi.jl:36-40 plus the
+    seed/device keywords this implementation needs).  dataTypes entries are
+    "GaussianCluster" / "CategoricalCluster" / "NegBinomCluster" (or the short names)."""
+    K, n_obs, dataNames = _check_arguments(dataFiles, dataTypes, N, particles, rho, dataNames)
 
     sweeper = Sweeper(dataFiles, dataTypes, N, particles, n_chains=1, seed=seed, device=device,
                       q1_mode=q1_mode, q2_mode=q2_mode)
@@ -100,3 +109,28 @@ def pmdi(dataFiles, dataTypes, N, particles, rho, iter, outputFile, thin=1, feat
     g.close()
     sweeper.close()
     return state
+
+
+def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=0, thin=1, featureSelect=False,
+                seed=0, device=0, q1_mode=0, q2_mode=0):
+    """`n_chains` independent chains of particleMDI on one MI355X, pooled on the device: runs `iter` iterations of every
+    chain, discards the first `burnin`, adds every `thin`-th one after that (psm.retained_iterations) of every chain to one
+    streaming accumulator (psm.PsmAccumulator) and returns its psm.PsmCounts -- the device-resident posterior-similarity
+    matrix psm.get_consensus_allocations takes; `.to_host()` gives the reference's Posterior_similarity_matrix.  No sample
+    buffer, no files.  Arguments as pmdi(); chain c draws from seed + c."""
+    from .psm import PsmAccumulator
+    K, n_obs, names = _check_arguments(dataFiles, dataTypes, N, particles, rho)
+    _need(n_chains >= 1, "n_chains must be >= 1")
+    _need(0 <= burnin < iter, "burnin must be >= 0 and smaller than iter (nothing would be retained)")
+    _need(thin >= 1, "thin must be >= 1")
+    sweeper = Sweeper(dataFiles, dataTypes, N, particles, n_chains=n_chains, seed=seed, device=device,
+                      q1_mode=q1_mode, q2_mode=q2_mode)
+    g = Gibbs(sweeper, rho=rho, feature_select=bool(featureSelect))
+    acc = PsmAccumulator(K, n_obs, n_labels=N, device=device)
+    try:
+        g.run(iter, burnin=burnin, thin=thin, acc=acc)
+        g.results()                      # synchronises; raises on a kernel-side error of any chain
+        return acc.counts(names=names)   # (the view keeps the accumulator alive)
+    finally:
+        g.close()
+        sweeper.close()

@@ -100,6 +100,137 @@ class PsmCounts:
     def __init__(self, counts, S, names=None):
         self.counts, self.S, self.names = counts, int(S), names
 
+    def to_host(self):
+        """The PosteriorSimilarityMatrix generate_psm would return for the same samples, with the arithmetic of psm_rows
+        (consensus_map.jl:50-63): count / S below the diagonal, identity elsewhere, "Overall" = the mean of the K matrices
+        when K > 1.  The integers come off the device; the divisions are IEEE doubles on the host."""
+        import torch
+        if self.S < 1:
+            raise ValueError("PsmCounts.to_host: no samples behind the counts")
+        cnt = self.counts.cpu()
+        K, n, _ = cnt.shape
+        out = torch.zeros((K + (1 if K > 1 else 0), n, n), dtype=torch.float64)
+        idx = torch.arange(n)
+        lower = (idx[:, None] > idx[None, :])
+        eye = (idx[:, None] == idx[None, :]).to(torch.float64)
+        S_t = torch.full((), float(self.S), dtype=torch.float64)
+        K_t = torch.full((), float(K), dtype=torch.float64)
+        for k in range(K):
+            out[k] = torch.div(cnt[k].to(torch.float64), S_t) * lower + eye
+        if K > 1:
+            out[K] = eye
+            for k in range(K):
+                out[K] += torch.div(out[k], K_t)
+            out[K] = out[K] * (1.0 - eye) + eye       # diagind .= 1.0
+        names = list(self.names) if self.names is not None else [f"K{i}" for i in range(1, K + 1)]
+        rows = out.numpy()
+        return PosteriorSimilarityMatrix([rows[k] for k in range(rows.shape[0])], names + (["Overall"] if K > 1 else []))
+
+
+def retained_iterations(n_iter, burnin=0, thin=1):
+    """The local iteration numbers t in 1..n_iter after which Gibbs.run / pmdi_gibbs_run adds the chains' allocations to its
+    accumulator: t > burnin and (t - burnin - 1) % thin == 0.  With rows 0..iter of a CSV written by pmdi(..., thin=1) (row 0 is
+    the initial state) these are the rows generate_psm(file, burnin + 1, thin) keeps (consensus_map.jl:33,38)."""
+    n_iter, burnin, thin = int(n_iter), int(burnin), int(thin)
+    if n_iter < 0 or burnin < 0 or thin < 1:
+        raise ValueError("retained_iterations needs n_iter >= 0, burnin >= 0, thin >= 1")
+    return [t for t in range(1, n_iter + 1) if t > burnin and (t - burnin - 1) % thin == 0]
+
+
+class _DeviceInt32View:
+    """What torch.as_tensor needs to wrap device memory it does not own (no copy); the tensor keeps this object, and this
+    object the accumulator, alive."""
+
+    def __init__(self, owner, ptr, shape):
+        self._owner = owner
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<i4", "data": (int(ptr), False), "version": 2,
+                                         "strides": None}
+
+
+class PsmAccumulator:
+    """Streaming co-clustering counts on one MI355X (include/pmdi_hip.h, pmdi_psm_acc_*): K * n * n int32 that take the
+    allocations of every retained iteration of every chain as they are produced, so pooling chains needs neither a sample
+    buffer nor a CSV.  n_labels as in psm_counts_device (the model's N; 0 = unknown).  All calls go to the current torch
+    stream of the device; use one stream per accumulator.  Exact: integer arithmetic only."""
+
+    def __init__(self, K, n, n_labels=0, device=0):
+        import ctypes as C
+        from ._lib import _check, lib
+        self.h = None
+        h = C.c_void_p()
+        _check(lib().pmdi_psm_acc_create(int(device), int(K), int(n), int(n_labels), C.byref(h)))
+        self.h, self.K, self.n, self.n_labels, self.device = h, int(K), int(n), int(n_labels), int(device)
+
+    def _stream(self):
+        import ctypes as C
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+
+    def close(self):
+        if getattr(self, "h", None):
+            from ._lib import lib
+            lib().pmdi_psm_acc_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def S(self):
+        from ._lib import lib
+        return int(lib().pmdi_psm_acc_samples(self.h))
+
+    def reset(self):
+        from ._lib import _check, lib
+        _check(lib().pmdi_psm_acc_reset(self.h, self._stream()))
+
+    def add_samples(self, samples):
+        """samples: CUDA uint8 tensor (S, K, n) on the accumulator's device, the layout of psm_counts_device."""
+        import ctypes as C
+        import torch
+        from ._lib import _check, lib
+        if not samples.is_cuda or samples.dtype != torch.uint8 or samples.dim() != 3:
+            raise ValueError("PsmAccumulator.add_samples needs a CUDA uint8 tensor (S, K, n)")
+        if tuple(samples.shape[1:]) != (self.K, self.n) or (samples.device.index or 0) != self.device:
+            raise ValueError(f"PsmAccumulator.add_samples: samples {tuple(samples.shape)} on {samples.device}, "
+                             f"the accumulator holds K={self.K} n={self.n} on device {self.device}")
+        smp = samples.contiguous()
+        _check(lib().pmdi_psm_acc_add_samples(self.h, C.c_void_p(smp.data_ptr()), int(smp.shape[0]), self._stream()))
+
+    def add_gibbs(self, gibbs):
+        """The current allocations of every chain of a _lib.Gibbs: n_chains samples."""
+        from ._lib import _check, lib
+        _check(lib().pmdi_psm_acc_add_gibbs(self.h, gibbs.h, self._stream()))
+
+    def merge(self, other):
+        """counts += other's counts, S += other's S; other is a PsmAccumulator or a PsmCounts on the same device (only its
+        lower triangle and diagonal are read)."""
+        import ctypes as C
+        import torch
+        from ._lib import _check, lib
+        pc = other.counts() if isinstance(other, PsmAccumulator) else other
+        cnt = pc.counts
+        if not cnt.is_cuda or cnt.dtype != torch.int32 or tuple(cnt.shape) != (self.K, self.n, self.n) \
+                or (cnt.device.index or 0) != self.device:
+            raise ValueError(f"PsmAccumulator.merge needs int32 counts ({self.K}, {self.n}, {self.n}) on device {self.device}")
+        cnt = cnt.contiguous()
+        _check(lib().pmdi_psm_acc_merge(self.h, C.c_void_p(cnt.data_ptr()), int(pc.S), self._stream()))
+
+    def counts(self, names=None):
+        """The PsmCounts of everything added so far: a zero-copy int32 CUDA tensor view (K, n, n) of the accumulator's memory
+        (full, symmetric, diagonal = S) that keeps the accumulator alive -- and keeps changing with later adds, after which
+        counts() has to be called again before the upper triangle is read."""
+        import ctypes as C
+        import torch
+        from ._lib import _check, lib
+        ptr, S = C.c_void_p(), C.c_int64(0)
+        _check(lib().pmdi_psm_acc_counts(self.h, C.byref(ptr), C.byref(S), self._stream()))
+        view = torch.as_tensor(_DeviceInt32View(self, ptr.value, (self.K, self.n, self.n)), device=torch.device("cuda", self.device))
+        return PsmCounts(view, S.value, names)
+
 
 LINKAGES = {"single": 0, "average": 1, "complete": 2, "ward": 3}       # PMDI_LINK_* of include/pmdi_hip.h
 
