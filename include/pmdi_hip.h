@@ -366,6 +366,61 @@ int pmdi_psm_acc_counts(pmdi_psm_acc *a, const int32_t **counts, int64_t *S, voi
  * (src/output_analysis/consensus_map.jl:33,38). */
 int pmdi_gibbs_run(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, void *stream);
 
+/* ---- streaming summary accumulator: what the reference's users read from the output file, and R-hat, without samples ----
+ * The second accumulator beside pmdi_psm_acc: it takes the state of every chain after every retained iteration on the device
+ * and keeps, per chain or pooled, what src/output_analysis/ reads back from the CSV per iteration.  C = n_chains, K datasets,
+ * N labels, npairs = K (K - 1) / 2 (0 when K = 1), sumD = sum_k D_k.  Arrays (row-major, the order of pmdi_summary_get):
+ *   nclust_hist  [K][N + 1] Int64  over all retained (iteration, chain): samples in which dataset k had exactly m distinct
+ *                                  labels -- the histogram of get_nclust's matrix (nclust_plots.jl:17-36, :32; plot_nclust_hist :39)
+ *   nclust_sum, nclust_sumsq [C][K] Int64  per chain, the sum of m and of m * m (R-hat of the cluster count)
+ *   M_mean, M_m2 [C][K] Float64, Phi_mean, Phi_m2 [C][npairs] Float64  per chain Welford state of the mass parameters
+ *                                  (the MassParameter_k columns, src/pmdi.jl:147-158) and of Phi (the phi_a_b columns get_phi
+ *                                  returns, phi_plots.jl:16-25, whose column means plot_phi_matrix shows, :38).  For the t-th
+ *                                  retained value x of a chain, t = 1, 2, ...:
+ *                                      d = x - mean;  mean = mean + d / t;  m2 = m2 + d * (x - mean);
+ *                                  three lines of separate IEEE double operations (never fused), one lane per (chain, scalar),
+ *                                  in retention order: a plain loop over the same doubles reproduces every bit.
+ *   flag_count   [sumD] Int64      sum over retained (iteration, chain) of feature_flag: divided by T * C it is
+ *                                  get_feature_select_probs (feature_select_plots.jl:180-192).  Only touched by an add whose
+ *                                  source carries flags (add_arrays with flags != NULL, add_gibbs of chains with feature selection).
+ *   trace_nclust [trace_cap][K] Int64, trace_M [trace_cap][K], trace_Phi [trace_cap][npairs] Float64: row t - 1 belongs to the
+ *                                  t-th add, t <= trace_cap (fixed at creation; rows not reached are zero): the sum over the
+ *                                  chains of m, and of M and Phi as ((0.0 + x_0) + x_1) + ... + x_{C-1}, chain order, one lane
+ *                                  per scalar -- bit-defined (plot_nclust_chain, plot_phi_chain).  Adds beyond the cap update
+ *                                  everything else and leave the trace alone.
+ * create: 1 <= K <= PMDI_KMAX, 2 <= N <= 255, n >= 1, n_chains >= 1 (n_chains * K <= INT32_MAX), sumD >= 0, trace_cap >= 0 are
+ *   checked before the device is touched (PMDI_E_ARG); no usable device is PMDI_E_DEVICE.  The state starts at zero.
+ * add_arrays: device arrays in the layouts of the resident state: s [C][K][n] 0-based int32, M [C][K], Phi [C][max(1, npairs)],
+ *   flags [C][sumD] bytes or NULL.  A label outside 0..N-1 is not counted and sets a device flag that pmdi_summary_get reports
+ *   as PMDI_E_DATA until pmdi_summary_reset.
+ * add_gibbs: the current s, M, Phi (and feature_flag when the chains run feature selection) of every chain of g.  PMDI_E_ARG
+ *   unless g's device, n_chains, K, N, n are the accumulator's, and its sumD too (chains without feature selection are also
+ *   taken by an accumulator created with sumD = 0: there is nothing to count).
+ * The number of adds T is bounded by INT32_MAX: an add that would pass it is PMDI_E_ARG and changes nothing.
+ * get: SYNCHRONISES `stream`, then copies to the host arrays that are not NULL (trace arrays: all trace_cap rows).
+ * reset: everything zero, T = 0.  Everything is asynchronous on `stream` except create, destroy and get; all calls on one
+ * accumulator go on ONE stream (the adds are read-modify-writes ordered by the stream). */
+typedef struct pmdi_summary pmdi_summary;
+int pmdi_summary_create(int32_t device, int32_t n_chains, int32_t K, int32_t N, int64_t n, int64_t sumD, int64_t trace_cap,
+                        pmdi_summary **out);
+int pmdi_summary_destroy(pmdi_summary *a);
+int pmdi_summary_reset(pmdi_summary *a, void *stream);
+int pmdi_summary_add_gibbs(pmdi_summary *a, pmdi_gibbs *g, void *stream);
+int pmdi_summary_add_arrays(pmdi_summary *a, const int32_t *s, const double *M, const double *Phi, const uint8_t *flags,
+                            void *stream);
+int64_t pmdi_summary_samples(const pmdi_summary *a);      /* T, the number of adds */
+int pmdi_summary_get(pmdi_summary *a, int64_t *nclust_hist, int64_t *nclust_sum, int64_t *nclust_sumsq, double *M_mean,
+                     double *M_m2, double *Phi_mean, double *Phi_m2, int64_t *flag_count, int64_t *trace_nclust,
+                     double *trace_M, double *trace_Phi, void *stream);
+
+/* pmdi_gibbs_run with a second accumulator: after every retained local iteration (the rule above) acc, then summ, get their
+ * add; either may be NULL, and pmdi_gibbs_run(g, ..., acc, stream) is pmdi_gibbs_run2(g, ..., acc, NULL, stream).  Both are
+ * checked against g and against their limits (S and T <= INT32_MAX) before the first iteration runs.  The rows summ sees are
+ * the rows get_phi / get_nclust / get_feature_select_probs keep with burnin + 1 (they read from data row `burnin`, row 0
+ * being the initial state: phi_plots.jl:21, nclust_plots.jl:20, feature_select_plots.jl:189). */
+int pmdi_gibbs_run2(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ,
+                    void *stream);
+
 /* Device pointers of the resident state (zero-copy consumers; layouts of pmdi_sweep_device). */
 typedef struct {
     double *M, *gamma, *gamma0, *Phi, *vZ, *Pi, *log1p_phi, *feature_prob, *logweight;

@@ -10,3 +10,6 @@ from ._lib import (  # noqa: F401
 )
 from .pmdi import pmdi_pooled  # noqa: F401,E402    (not pmdi(): the name is the submodule's)
 from .psm import PsmAccumulator, PsmCounts, retained_iterations  # noqa: F401,E402
+from .summary import (  # noqa: F401,E402
+    PosteriorSummary, SummaryAccumulator, get_feature_select_probs, get_nclust, get_phi,
+)

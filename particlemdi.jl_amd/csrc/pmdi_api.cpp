@@ -211,6 +211,19 @@ struct pmdi_psm_acc {
     bool dirty = false;                  // something was added since the last mirror
 };
 
+// Streaming summary accumulator (pmdi_summary_* entry points): one device slab, the arrays of include/pmdi_hip.h one after
+// the other (8-byte elements), then the error flag and the per-add scratch
+struct pmdi_summary {
+    int device = 0, C = 0, K = 0, N = 0, npairs = 0;
+    long long n = 0, sumD = 0, trace_cap = 0;
+    char *slab = nullptr;
+    size_t state_bytes = 0;              // what reset zeroes: every array and the error flag
+    long long *hist = nullptr, *nsum = nullptr, *nsumsq = nullptr, *flag_count = nullptr, *tr_nclust = nullptr;
+    double *M_mean = nullptr, *M_m2 = nullptr, *Phi_mean = nullptr, *Phi_m2 = nullptr, *tr_M = nullptr, *tr_Phi = nullptr;
+    int *err = nullptr, *nclust = nullptr;
+    int64_t T = 0;                       // adds so far
+};
+
 namespace {
 
 int dev_alloc(pmdi_handle *h, void **p, size_t bytes)
@@ -1046,6 +1059,136 @@ int pmdi_psm_acc_counts(pmdi_psm_acc *a, const int32_t **counts, int64_t *S, voi
     return PMDI_OK;
 }
 
+int pmdi_summary_destroy(pmdi_summary *a)
+{
+    if (!a) return PMDI_OK;
+    (void)hipSetDevice(a->device);
+    (void)hipDeviceSynchronize();
+    if (a->slab) (void)hipFree(a->slab);
+    delete a;
+    return PMDI_OK;
+}
+
+int pmdi_summary_create(int32_t device, int32_t n_chains, int32_t K, int32_t N, int64_t n, int64_t sumD, int64_t trace_cap,
+                        pmdi_summary **out)
+{
+    if (!out) return fail(PMDI_E_ARG, "null argument");
+    *out = nullptr;
+    if (K < 1 || K > PMDI_KMAX_I) return fail(PMDI_E_ARG, "K=%d outside 1..%d", K, PMDI_KMAX_I);
+    if (N < 2 || N > 255) return fail(PMDI_E_ARG, "N=%d outside 2..255", N);
+    if (n < 1) return fail(PMDI_E_ARG, "n=%lld < 1", (long long)n);
+    if (n_chains < 1 || (long long)n_chains * K > 2147483647LL) return fail(PMDI_E_ARG, "n_chains=%d: need n_chains >= 1 and n_chains * K <= INT32_MAX", n_chains);
+    if (sumD < 0) return fail(PMDI_E_ARG, "sumD=%lld < 0", (long long)sumD);
+    if (trace_cap < 0 || trace_cap > 2147483647LL) return fail(PMDI_E_ARG, "trace_cap=%lld outside 0..INT32_MAX (the bound of the number of adds)", (long long)trace_cap);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(PMDI_E_DEVICE, "no HIP device visible (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(PMDI_E_DEVICE, "device %d not in 0..%d", device, ndev - 1);
+    HIP_TRY(hipSetDevice(device));
+    pmdi_summary *a = new (std::nothrow) pmdi_summary();
+    if (!a) return fail(PMDI_E_MEMORY, "out of host memory");
+    a->device = device; a->C = n_chains; a->K = K; a->N = N; a->npairs = K * (K - 1) / 2; a->n = n; a->sumD = sumD; a->trace_cap = trace_cap;
+    const size_t CK = (size_t)n_chains * K, CP = (size_t)n_chains * a->npairs;
+    // 8-byte elements: hist, nsum, nsumsq, M_mean, M_m2, Phi_mean, Phi_m2, flag_count, tr_nclust, tr_M, tr_Phi, err; then nclust (int)
+    const size_t counts[11] = {(size_t)K * (N + 1), CK, CK, CK, CK, CP, CP, (size_t)sumD, (size_t)trace_cap * K, (size_t)trace_cap * K,
+                               (size_t)trace_cap * a->npairs};
+    long double total = 1.0L + (long double)CK;
+    for (size_t c : counts) total += (long double)c;
+    if (total * 8.0L > 4.0e18L) { delete a; return fail(PMDI_E_MEMORY, "the accumulator would need more than 4e18 bytes"); }
+    size_t off[12], o = 0;
+    for (int i = 0; i < 11; ++i) { off[i] = o; o += counts[i] * 8; }
+    off[11] = o; o += 8;
+    a->state_bytes = o;
+    const size_t bytes = o + CK * 4;
+    hipError_t e = hipMalloc((void **)&a->slab, bytes);
+    if (e != hipSuccess) { a->slab = nullptr; pmdi_summary_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e)); }
+    if (hipMemset(a->slab, 0, bytes) != hipSuccess) { pmdi_summary_destroy(a); return fail(PMDI_E_DEVICE, "hipMemset failed"); }
+    char *p = a->slab;
+    a->hist = (long long *)(p + off[0]); a->nsum = (long long *)(p + off[1]); a->nsumsq = (long long *)(p + off[2]);
+    a->M_mean = (double *)(p + off[3]); a->M_m2 = (double *)(p + off[4]); a->Phi_mean = (double *)(p + off[5]); a->Phi_m2 = (double *)(p + off[6]);
+    a->flag_count = (long long *)(p + off[7]); a->tr_nclust = (long long *)(p + off[8]); a->tr_M = (double *)(p + off[9]);
+    a->tr_Phi = (double *)(p + off[10]); a->err = (int *)(p + off[11]); a->nclust = (int *)(p + a->state_bytes);
+    *out = a;
+    return PMDI_OK;
+}
+
+int pmdi_summary_reset(pmdi_summary *a, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipMemsetAsync(a->slab, 0, a->state_bytes, (hipStream_t)stream));
+    a->T = 0;
+    return PMDI_OK;
+}
+
+int pmdi_summary_add_arrays(pmdi_summary *a, const int32_t *s, const double *M, const double *Phi, const uint8_t *flags, void *stream)
+{
+    if (!a || !s || !M || (!Phi && a->npairs > 0)) return fail(PMDI_E_ARG, "null argument");
+    if (a->T >= 2147483647LL) return fail(PMDI_E_ARG, "%lld + 1 adds pass INT32_MAX", (long long)a->T);
+    HIP_TRY(hipSetDevice(a->device));
+    SummaryArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.C = a->C; sa.K = a->K; sa.N = a->N; sa.npairs = a->npairs; sa.phi_stride = a->npairs > 0 ? a->npairs : 1;
+    sa.n = a->n; sa.sumD = a->sumD;
+    sa.s = s; sa.M = M; sa.Phi = Phi; sa.flags = flags;
+    sa.nclust = a->nclust; sa.err = a->err; sa.hist = a->hist; sa.nclust_sum = a->nsum; sa.nclust_sumsq = a->nsumsq;
+    sa.M_mean = a->M_mean; sa.M_m2 = a->M_m2; sa.Phi_mean = a->Phi_mean; sa.Phi_m2 = a->Phi_m2; sa.flag_count = a->flag_count;
+    if (a->T < a->trace_cap) {
+        sa.tr_nclust = a->tr_nclust + (size_t)a->T * a->K; sa.tr_M = a->tr_M + (size_t)a->T * a->K;
+        sa.tr_Phi = a->tr_Phi + (size_t)a->T * a->npairs;
+    }
+    hipError_t e = pmdi_launch_summary_add(sa, (long long)a->T + 1, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "summary-add launch: %s", hipGetErrorString(e));
+    a->T += 1;
+    return PMDI_OK;
+}
+
+// what pmdi_summary_add_gibbs checks before it touches anything (pmdi_gibbs_run2 asks once, before its first iteration)
+static int summary_accepts(const pmdi_summary *a, const pmdi_gibbs *g, int64_t n_adds)
+{
+    const pmdi_config &c = g->h->cfg;
+    if (c.n_chains != a->C || c.K != a->K || c.N != a->N || c.n != a->n)
+        return fail(PMDI_E_ARG, "the accumulator holds n_chains=%d K=%d N=%d n=%lld, the chains n_chains=%d K=%d N=%d n=%lld", a->C, a->K, a->N,
+                    a->n, c.n_chains, c.K, c.N, (long long)c.n);
+    if (a->sumD != g->h->sumD && !(a->sumD == 0 && !g->feature_select))
+        return fail(PMDI_E_ARG, "the accumulator holds sumD=%lld, the chains sumD=%d", a->sumD, g->h->sumD);
+    if (c.device != a->device) return fail(PMDI_E_ARG, "the chains live on device %d, the accumulator on device %d", c.device, a->device);
+    if (n_adds > 2147483647LL - a->T) return fail(PMDI_E_ARG, "%lld + %lld adds pass INT32_MAX", (long long)a->T, (long long)n_adds);
+    return PMDI_OK;
+}
+
+int pmdi_summary_add_gibbs(pmdi_summary *a, pmdi_gibbs *g, void *stream)
+{
+    if (!a || !g) return fail(PMDI_E_ARG, "null argument");
+    const int rc = summary_accepts(a, g, 1);
+    if (rc) return rc;
+    return pmdi_summary_add_arrays(a, g->ga.s, g->ga.M, g->ga.Phi, (g->feature_select && a->sumD > 0) ? g->flags : nullptr, stream);
+}
+
+int64_t pmdi_summary_samples(const pmdi_summary *a) { return a ? a->T : 0; }
+
+int pmdi_summary_get(pmdi_summary *a, int64_t *nclust_hist, int64_t *nclust_sum, int64_t *nclust_sumsq, double *M_mean, double *M_m2,
+                     double *Phi_mean, double *Phi_m2, int64_t *flag_count, int64_t *trace_nclust, double *trace_M, double *trace_Phi,
+                     void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t CK = (size_t)a->C * a->K, CP = (size_t)a->C * a->npairs, cap = (size_t)a->trace_cap;
+    int err = 0;
+    struct { void *dst; const void *src; size_t count; } cp[] = {
+        {nclust_hist, a->hist, (size_t)a->K * (a->N + 1)}, {nclust_sum, a->nsum, CK}, {nclust_sumsq, a->nsumsq, CK},
+        {M_mean, a->M_mean, CK}, {M_m2, a->M_m2, CK}, {Phi_mean, a->Phi_mean, CP}, {Phi_m2, a->Phi_m2, CP},
+        {flag_count, a->flag_count, (size_t)a->sumD}, {trace_nclust, a->tr_nclust, cap * a->K}, {trace_M, a->tr_M, cap * a->K},
+        {trace_Phi, a->tr_Phi, cap * a->npairs}};
+    for (const auto &c : cp)
+        if (c.dst && c.count) HIP_TRY(hipMemcpyAsync(c.dst, c.src, c.count * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&err, a->err, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (err) return fail(PMDI_E_DATA, "a label outside 0..%d was added (pmdi_summary_add_arrays); pmdi_summary_reset clears the accumulator", a->N - 1);
+    return PMDI_OK;
+}
+
 int pmdi_label_counts_device(pmdi_handle *h, const int32_t *s, int32_t *counts, void *stream)
 {
     if (!h || !s || !counts) return fail(PMDI_E_ARG, "null argument");
@@ -1515,25 +1658,31 @@ int pmdi_gibbs_iterate(pmdi_gibbs *g, int64_t n_iter, uint8_t *samples, void *st
     return PMDI_OK;
 }
 
-int pmdi_gibbs_run(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, void *stream)
+int pmdi_gibbs_run2(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, void *stream)
 {
     if (!g || n_iter < 0) return fail(PMDI_E_ARG, "bad argument");
     if (burnin < 0 || thin < 1) return fail(PMDI_E_ARG, "burnin=%lld must be >= 0 and thin=%lld >= 1", (long long)burnin, (long long)thin);
-    if (acc) {
-        const int64_t kept = n_iter > burnin ? (n_iter - burnin - 1) / thin + 1 : 0;
-        const int rc = psm_acc_accepts(acc, g, kept);
-        if (rc) return rc;
-    }
+    const int64_t kept = n_iter > burnin ? (n_iter - burnin - 1) / thin + 1 : 0;
+    int rc;
+    if (acc && (rc = psm_acc_accepts(acc, g, kept))) return rc;
+    if (summ && (rc = summary_accepts(summ, g, kept))) return rc;
     for (int64_t t = 1; t <= n_iter; ++t) {
-        int rc;
         if ((rc = pmdi_gibbs_step(g, PMDI_STEP_BEGIN, stream)) || (rc = pmdi_gibbs_step(g, PMDI_STEP_HYPERS, stream)) ||
             (rc = pmdi_gibbs_step(g, PMDI_STEP_SWEEP, stream)))
             return rc;
         if (g->feature_select && (rc = pmdi_gibbs_step(g, PMDI_STEP_FEATSEL, stream))) return rc;
         if ((rc = pmdi_gibbs_step(g, PMDI_STEP_ALIGN, stream))) return rc;
-        if (acc && t > burnin && (t - burnin - 1) % thin == 0 && (rc = pmdi_psm_acc_add_gibbs(acc, g, stream))) return rc;
+        if (t > burnin && (t - burnin - 1) % thin == 0) {
+            if (acc && (rc = pmdi_psm_acc_add_gibbs(acc, g, stream))) return rc;
+            if (summ && (rc = pmdi_summary_add_gibbs(summ, g, stream))) return rc;
+        }
     }
     return PMDI_OK;
+}
+
+int pmdi_gibbs_run(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, void *stream)
+{
+    return pmdi_gibbs_run2(g, n_iter, burnin, thin, acc, nullptr, stream);
 }
 
 int64_t pmdi_gibbs_iterations(const pmdi_gibbs *g) { return g ? g->iter : 0; }

@@ -236,3 +236,26 @@ hipError_t pmdi_launch_label_counts(const int *s, int *counts, int n_rows, long 
 hipError_t pmdi_launch_psm_acc_add(const unsigned char *samples, long long S, int K, long long n, int n_labels, int *counts, hipStream_t stream);
 hipError_t pmdi_launch_psm_acc_mirror(int *counts, int K, long long n, hipStream_t stream);
 hipError_t pmdi_launch_psm_acc_merge(int *a, const int *b, int K, long long n, hipStream_t stream);
+
+// One add of the streaming summary accumulator (pmdi_summary.hip): the source arrays in the GibbsArgs layouts, the
+// accumulator's state, and this add's trace row.
+struct SummaryArgs {
+    int C, K, N, npairs;        // chains, datasets, labels, K (K - 1) / 2 (0 when K = 1)
+    int phi_stride;             // max(1, npairs): chain stride of Phi
+    long long n, sumD;
+    const int *s;               // [C][K][n]  0-based labels
+    const double *M;            // [C][K]
+    const double *Phi;          // [C][phi_stride]
+    const unsigned char *flags; // [C][sumD], or null: flag_count is left alone
+    int *nclust;                // [C][K]     scratch: distinct labels per row of this add
+    int *err;                   // set to 1 by a label outside 0..N-1
+    long long *hist;            // [K][N + 1]
+    long long *nclust_sum, *nclust_sumsq;               // [C][K]
+    double *M_mean, *M_m2;      // [C][K]
+    double *Phi_mean, *Phi_m2;  // [C][npairs]
+    long long *flag_count;      // [sumD]
+    long long *tr_nclust;       // [K]        this add's trace row, or null (all three) when the trace takes no more rows
+    double *tr_M, *tr_Phi;      // [K], [npairs]
+};
+// t = 1, 2, ...: the number of this add (the divisor of the Welford recurrences)
+hipError_t pmdi_launch_summary_add(const SummaryArgs &a, long long t, hipStream_t stream);

@@ -112,13 +112,18 @@ def pmdi(dataFiles, dataTypes, N, particles, rho, iter, outputFile, thin=1, feat
 
 
 def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=0, thin=1, featureSelect=False,
-                seed=0, device=0, q1_mode=0, q2_mode=0):
+                seed=0, device=0, q1_mode=0, q2_mode=0, summary=False):
     """`n_chains` independent chains of particleMDI on one MI355X, pooled on the device: runs `iter` iterations of every
     chain, discards the first `burnin`, adds every `thin`-th one after that (psm.retained_iterations) of every chain to one
     streaming accumulator (psm.PsmAccumulator) and returns its psm.PsmCounts -- the device-resident posterior-similarity
     matrix psm.get_consensus_allocations takes; `.to_host()` gives the reference's Posterior_similarity_matrix.  No sample
-    buffer, no files.  Arguments as pmdi(); chain c draws from seed + c."""
-    from .psm import PsmAccumulator
+    buffer, no files.  Arguments as pmdi(); chain c draws from seed + c.
+    summary=True: a second accumulator (summary.SummaryAccumulator) takes the same retained iterations and the call returns
+    (counts, summary.PosteriorSummary): the Phi matrix, the cluster-count histogram, R-hat of M, Phi and the cluster counts
+    over the chains, a trace row per retained iteration and, with featureSelect=True, the feature-selection probabilities.
+    Its rows are the ones summary.get_phi / get_nclust / get_feature_select_probs keep with burnin + 1 in a file of pmdi()."""
+    from .psm import PsmAccumulator, retained_iterations
+    from .summary import SummaryAccumulator
     K, n_obs, names = _check_arguments(dataFiles, dataTypes, N, particles, rho)
     _need(n_chains >= 1, "n_chains must be >= 1")
     _need(0 <= burnin < iter, "burnin must be >= 0 and smaller than iter (nothing would be retained)")
@@ -127,10 +132,19 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
                       q1_mode=q1_mode, q2_mode=q2_mode)
     g = Gibbs(sweeper, rho=rho, feature_select=bool(featureSelect))
     acc = PsmAccumulator(K, n_obs, n_labels=N, device=device)
+    summ = None
+    if summary:
+        summ = SummaryAccumulator(n_chains, K, N, n_obs, sumD=sweeper.sumD if featureSelect else 0,
+                                  trace_cap=len(retained_iterations(iter, burnin, thin)), device=device)
     try:
-        g.run(iter, burnin=burnin, thin=thin, acc=acc)
+        g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ)
         g.results()                      # synchronises; raises on a kernel-side error of any chain
-        return acc.counts(names=names)   # (the view keeps the accumulator alive)
+        counts = acc.counts(names=names)   # (the view keeps the accumulator alive)
+        if summ is None:
+            return counts
+        return counts, summ.summary(names=names, feature_D=sweeper.D)
     finally:
+        if summ is not None:
+            summ.close()
         g.close()
         sweeper.close()
