@@ -281,6 +281,35 @@ int pmdi_hclust_device(int32_t device, double *dist, int32_t B, int64_t n, int32
                        double *heights_out, int64_t *order_out, void *stream);
 int pmdi_cutree(int64_t n, const int64_t *merges, const double *heights, int64_t k, double h, int64_t *labels_out);
 
+/* ---- which clustering: candidates scored against the co-clustering counts on the device ---------------------------
+ * The reference stops at the @assert of consensus_map.jl:94 (the caller names k or h).  pmdi_psm_score_device ranks given
+ * candidate clusterings by posterior expected loss against the PSM; everything the device computes is an integer.
+ *
+ * counts: device int32 [K][n][n], the output of pmdi_psm_counts_device(..., 0, n) or pmdi_psm_acc_counts; S the number of
+ * samples behind it.  Only counts[k][i][j] with i > j is read: the upper triangle and the diagonal may hold anything.
+ *   which <  K: w_ij = counts[which][i][j],    D = S;
+ *   which == K ("Overall", K > 1 only): w_ij = sum_k counts[k][i][j],  D = S K.
+ * This Overall is the exact mean of the K matrices, sum_k count_k / (S K).  It does NOT follow the reference's
+ * floating-point order 0.0 + p_1 / K + ... that pmdi_psm_distance_device reproduces for the distances: the scores are
+ * defined on the counts.
+ * cand: device int32, candidate b = the n labels at cand + b ld (ld >= n), any values, compared for equality only; the
+ * resident allocations s [C][K][n] are scored in place (dataset k of every chain: cand = s + k n, ld = K n, B = C; all
+ * C K rows: ld = n, B = C K).
+ * With delta_ij = [c_i == c_j] and P = n (n - 1) / 2, per candidate
+ *   agree_out[b] = sum_{i>j} delta_ij w_ij,   pairs_out[b] = sum_{i>j} delta_ij,   and once   total_out[0] = sum_{i>j} w_ij
+ * (HOST int64 arrays, so the call SYNCHRONISES `stream`).  With p_ij = w_ij / D the criteria follow on the host, each
+ * formed from exact integers and divided once:
+ *   Binder  sum_{i>j} |delta_ij - p_ij| = (D pairs + total - 2 agree) / D                               (lower is better)
+ *   PEAR    (sum delta p - E) / ((sum delta + sum p) / 2 - E), E = sum delta sum p / P  (Fritsch & Ickstadt 2009)
+ *           = 2 (agree P - pairs total) / ((D pairs + total) P - 2 pairs total); NaN when that denominator is 0  (higher is better)
+ * PMDI_E_ARG, before any device use: K outside 1..PMDI_KMAX; which outside 0..K, or which == K with K == 1; n < 1 or
+ * n > 65535; B < 1; ld < n; S < 1; a null pointer; D P >= 2^62 (the bound that keeps every sum above inside int64).
+ * n = 1: all zeros.  A count above S is a caller error and is not checked.  Stateless. */
+int pmdi_psm_score_device(int32_t device, const int32_t *counts, int64_t S, int32_t K, int64_t n, int32_t which,
+                          const int32_t *cand, int64_t B, int64_t ld,
+                          int64_t *agree_out /* host, B */, int64_t *pairs_out /* host, B */, int64_t *total_out /* host, 1 */,
+                          void *stream);
+
 /* ---- device-resident Gibbs chains -----------------------------------------
  * Everything pmdi() does per iteration AROUND the sweep, for every chain of the handle, without leaving the
  * device: shuffle!(order_obs) (src/pmdi.jl:172), update_M!, update_gamma!, Pi, update_Phi!, update_Z, update_v

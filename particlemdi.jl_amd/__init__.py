@@ -9,7 +9,10 @@ from ._lib import (  # noqa: F401
     STEP_ALIGN, STEP_BEGIN, STEP_FEATSEL, STEP_HYPERS, STEP_SWEEP,
 )
 from .pmdi import pmdi_pooled  # noqa: F401,E402    (not pmdi(): the name is the submodule's)
-from .psm import PsmAccumulator, PsmCounts, retained_iterations  # noqa: F401,E402
+from .psm import (  # noqa: F401,E402
+    AllocationScores, PsmAccumulator, PsmCounts, best_sampled_allocation, retained_iterations, score_allocations,
+    select_consensus_allocations,
+)
 from .summary import (  # noqa: F401,E402
     PosteriorSummary, SummaryAccumulator, get_feature_select_probs, get_nclust, get_phi,
 )

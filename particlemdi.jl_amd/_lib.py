@@ -12,7 +12,7 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("PMDI_LIB_PATH") or os.path.join(_PKG, "libpmdi_hip.so")   # override: A/B builds only
-_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_summary.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_api.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
+_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_summary.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_api.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
 _HEADERS = [os.path.join(_PKG, "csrc", "pmdi_internal.h"), os.path.join(_PKG, "csrc", "pmdi_device.h"),
             os.path.join(_PKG, "csrc", "pmdi_sweep_body.h"), os.path.join(_PKG, "csrc", "pmdi_sweep2_body.h"),
             os.path.join(_PKG, "csrc", "pmdi_arith.h"),
@@ -42,6 +42,7 @@ EXPORTS = [
     "pmdi_psm_acc_merge", "pmdi_psm_acc_samples", "pmdi_psm_acc_counts", "pmdi_gibbs_run",
     "pmdi_summary_create", "pmdi_summary_destroy", "pmdi_summary_reset", "pmdi_summary_add_gibbs", "pmdi_summary_add_arrays",
     "pmdi_summary_samples", "pmdi_summary_get", "pmdi_gibbs_run2",
+    "pmdi_psm_score_device",
 ]
 
 
@@ -200,6 +201,8 @@ def lib():
     L.pmdi_psm_distance_device.argtypes = [i32, vp, i64, i32, i64, i32, vp, vp]
     L.pmdi_hclust_device.restype = C.c_int
     L.pmdi_hclust_device.argtypes = [i32, vp, i32, i64, i32, vp, vp, vp, vp]
+    L.pmdi_psm_score_device.restype = C.c_int
+    L.pmdi_psm_score_device.argtypes = [i32, vp, i64, i32, i64, i32, vp, i64, i64, vp, vp, vp, vp]
     L.pmdi_cutree.restype = C.c_int
     L.pmdi_cutree.argtypes = [i64, vp, vp, i64, dbl, vp]
     L.pmdi_psm_acc_create.restype = C.c_int

@@ -943,6 +943,45 @@ int pmdi_psm_counts_device(int32_t device, const uint8_t *samples, int64_t S, in
     return PMDI_OK;
 }
 
+int pmdi_psm_score_device(int32_t device, const int32_t *counts, int64_t S, int32_t K, int64_t n, int32_t which,
+                          const int32_t *cand, int64_t B, int64_t ld, int64_t *agree_out, int64_t *pairs_out, int64_t *total_out,
+                          void *stream)
+{
+    if (!counts || !cand || !agree_out || !pairs_out || !total_out) return fail(PMDI_E_ARG, "pmdi_psm_score_device: null argument");
+    if (K < 1 || K > PMDI_KMAX || S < 1 || n < 1 || n > 65535 || B < 1 || ld < n)
+        return fail(PMDI_E_ARG, "pmdi_psm_score_device: S=%lld K=%d n=%lld B=%lld ld=%lld out of range (K <= %d, n <= 65535, ld >= n)",
+                    (long long)S, K, (long long)n, (long long)B, (long long)ld, PMDI_KMAX);
+    if (which < 0 || which > K || (which == K && K == 1))
+        return fail(PMDI_E_ARG, "pmdi_psm_score_device: which=%d, but there are %d matrices (the Overall one only for K > 1)", which,
+                    K + (K > 1));
+    const unsigned __int128 P = (unsigned __int128)(n * (n - 1) / 2);
+    const unsigned __int128 D = (unsigned __int128)S * (unsigned)(which == K ? K : 1);
+    if (D * P >= ((unsigned __int128)1 << 62))       // D pairs + total and every other sum of the criteria stay inside int64
+        return fail(PMDI_E_ARG, "pmdi_psm_score_device: S=%lld with n=%lld: D n (n - 1) / 2 >= 2^62", (long long)S, (long long)n);
+    if (n == 1) {                                    // no pairs
+        for (int64_t b = 0; b < B; ++b) agree_out[b] = pairs_out[b] = 0;
+        *total_out = 0;
+        return PMDI_OK;
+    }
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    struct Scratch {
+        void *p = nullptr;
+        ~Scratch() { if (p) (void)hipFree(p); }
+    } out;
+    const size_t bytes = ((size_t)2 * B + 1) * sizeof(unsigned long long);
+    HIP_TRY(hipMalloc(&out.p, bytes));
+    HIP_TRY(hipMemsetAsync(out.p, 0, bytes, st));
+    const hipError_t e = pmdi_launch_psm_score(counts, K, n, which, D > ((unsigned __int128)1 << 22) ? 1 : 0, cand, B, ld,
+                                               (unsigned long long *)out.p, st);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "psm-score launch: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(agree_out, out.p, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(pairs_out, (const char *)out.p + (size_t)B * 8, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(total_out, (const char *)out.p + (size_t)B * 16, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PMDI_OK;
+}
+
 int pmdi_psm_acc_destroy(pmdi_psm_acc *a)
 {
     if (!a) return PMDI_OK;

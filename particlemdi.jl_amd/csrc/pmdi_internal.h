@@ -236,6 +236,9 @@ hipError_t pmdi_launch_label_counts(const int *s, int *counts, int n_rows, long 
 hipError_t pmdi_launch_psm_acc_add(const unsigned char *samples, long long S, int K, long long n, int n_labels, int *counts, hipStream_t stream);
 hipError_t pmdi_launch_psm_acc_mirror(int *counts, int K, long long n, hipStream_t stream);
 hipError_t pmdi_launch_psm_acc_merge(int *a, const int *b, int K, long long n, hipStream_t stream);
+// candidates scored against the counts (pmdi_psm_score.hip): out = B agree, B pairs, 1 total, zeroed by the caller; wide: D > 2^22
+hipError_t pmdi_launch_psm_score(const int *counts, int K, long long n, int which, int wide, const int *cand, long long B, long long ld,
+                                 unsigned long long *out, hipStream_t stream);
 
 // One add of the streaming summary accumulator (pmdi_summary.hip): the source arrays in the GibbsArgs layouts, the
 // accumulator's state, and this add's trace row.

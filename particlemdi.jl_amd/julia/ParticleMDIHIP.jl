@@ -425,6 +425,26 @@ function cutree(hc::Hclust; k::Union{Int64, Nothing} = nothing, h::Union{Float64
     return labels
 end
 
+# ---- which clustering: candidates scored against the counts (pmdi_psm_score_device; not executed, as above) ----
+# counts as in psm_distance_device; cand: device pointer to Int32 labels, candidate b at cand + b * ld (ld >= n); which is
+# 1-based, K + 1 = "Overall".  Returns (agree, pairs, total, D); binder / pear follow include/pmdi_hip.h in BigInt, one division.
+function psm_score_device(counts::Ptr{Cvoid}, S::Integer, K::Integer, n::Integer, which::Integer, cand::Ptr{Cvoid}, B::Integer,
+                          ld::Integer = n; device::Integer = 0, stream::Ptr{Cvoid} = C_NULL)
+    agree = Vector{Int64}(undef, B); pairs = Vector{Int64}(undef, B); total = Ref{Int64}(0)
+    check(ccall((:pmdi_psm_score_device, LIB), Cint,
+                (Int32, Ptr{Cvoid}, Int64, Int32, Int64, Int32, Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ref{Int64}, Ptr{Cvoid}),
+                device, counts, S, K, n, which - 1, cand, B, ld, agree, pairs, total, stream))
+    return agree, pairs, total[], S * (which == K + 1 ? K : 1)
+end
+binder(agree, pairs, total, D) = [Float64((big(D) * q + total - 2 * big(a)) // big(D)) for (a, q) in zip(agree, pairs)]
+function pear(agree, pairs, total, D, n)
+    P = big(n) * (n - 1) ÷ 2
+    map(zip(agree, pairs)) do (a, q)
+        den = (big(D) * q + total) * P - 2 * big(q) * total
+        den == 0 ? NaN : Float64(2 * (big(a) * P - big(q) * total) // den)
+    end
+end
+
 # ---- the cluster plugin protocol on the device (unit-level entry points) ----------------------
 # calc_logprob / cluster_add! / calc_logmarginal for a batch of stand-alone clusters of dataset k;
 # see pmdi_clusters_new, pmdi_cluster_add, pmdi_calc_logprob, pmdi_calc_logmarginal in the header.

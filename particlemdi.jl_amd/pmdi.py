@@ -112,7 +112,7 @@ def pmdi(dataFiles, dataTypes, N, particles, rho, iter, outputFile, thin=1, feat
 
 
 def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=0, thin=1, featureSelect=False,
-                seed=0, device=0, q1_mode=0, q2_mode=0, summary=False):
+                seed=0, device=0, q1_mode=0, q2_mode=0, summary=False, final_allocations=False):
     """`n_chains` independent chains of particleMDI on one MI355X, pooled on the device: runs `iter` iterations of every
     chain, discards the first `burnin`, adds every `thin`-th one after that (psm.retained_iterations) of every chain to one
     streaming accumulator (psm.PsmAccumulator) and returns its psm.PsmCounts -- the device-resident posterior-similarity
@@ -121,8 +121,10 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     summary=True: a second accumulator (summary.SummaryAccumulator) takes the same retained iterations and the call returns
     (counts, summary.PosteriorSummary): the Phi matrix, the cluster-count histogram, R-hat of M, Phi and the cluster counts
     over the chains, a trace row per retained iteration and, with featureSelect=True, the feature-selection probabilities.
-    Its rows are the ones summary.get_phi / get_nclust / get_feature_select_probs keep with burnin + 1 in a file of pmdi()."""
-    from .psm import PsmAccumulator, retained_iterations
+    Its rows are the ones summary.get_phi / get_nclust / get_feature_select_probs keep with burnin + 1 in a file of pmdi().
+    final_allocations=True: the chains' last allocations are copied to an int32 CUDA tensor (n_chains, K, n) of 0-based labels
+    before the handles close and appended to the returned tuple -- the candidates of psm.best_sampled_allocation."""
+    from .psm import PsmAccumulator, _DeviceInt32View, retained_iterations
     from .summary import SummaryAccumulator
     K, n_obs, names = _check_arguments(dataFiles, dataTypes, N, particles, rho)
     _need(n_chains >= 1, "n_chains must be >= 1")
@@ -140,9 +142,13 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
         g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ)
         g.results()                      # synchronises; raises on a kernel-side error of any chain
         counts = acc.counts(names=names)   # (the view keeps the accumulator alive)
-        if summ is None:
-            return counts
-        return counts, summ.summary(names=names, feature_D=sweeper.D)
+        out = (counts,) if summ is None else (counts, summ.summary(names=names, feature_D=sweeper.D))
+        if final_allocations:
+            import torch
+            dev = torch.device("cuda", int(device))
+            out += (torch.as_tensor(_DeviceInt32View(g, g.view().s, (n_chains, K, n_obs)), device=dev).clone(),)
+            torch.cuda.synchronize(dev)      # the copy is done before the chains' memory goes
+        return out[0] if len(out) == 1 else out
     finally:
         if summ is not None:
             summ.close()

@@ -9,6 +9,10 @@ Chains are independent, so this is the ONLY collective of the path (SURVEY.md se
 What a user wants from that matrix comes next in the same file of the reference: get_consensus_allocations
 (consensus_map.jl:92-105) = cutree(hclust(1 .- Symmetric(psm, :L))), here on the device (hclust, cutree,
 get_consensus_allocations below; include/pmdi_hip.h states the tie rule).
+
+The reference stops there, with k or h left to the caller.  score_allocations ranks candidate clusterings by Binder's loss
+and by the posterior expected adjusted Rand index against the device-resident counts (pmdi_psm_score_device);
+select_consensus_allocations picks the cut and the linkage with it, best_sampled_allocation one of the chains' own states.
 """
 import numpy as np
 
@@ -333,6 +337,165 @@ def get_consensus_allocations(psm, k=None, h=None, linkage="ward", orderby=0, de
             torch.device("cuda", 0 if device is None else int(device)))
         hc = hclust(1.0 - t, linkage)
     return cutree(hc, k=k, h=h)
+
+
+class AllocationScores:
+    """What score_allocations returns, all exact integers (include/pmdi_hip.h, pmdi_psm_score_device): per candidate
+    `agree` = sum_{i>j} [c_i == c_j] w_ij and `pairs` = sum_{i>j} [c_i == c_j] (int64 numpy, (B,)), `total` = sum_{i>j} w_ij,
+    `D` = the divisor of the scored matrix (S, or S K for "Overall"), `n` observations.  binder() and pear() form each
+    criterion from Python integers and divide once."""
+
+    def __init__(self, agree, pairs, total, D, n):
+        self.agree, self.pairs, self.total, self.D, self.n = agree, pairs, int(total), int(D), int(n)
+
+    def binder(self):
+        """Binder's loss sum_{i>j} |[c_i == c_j] - p_ij| = (D pairs + total - 2 agree) / D, float64 (B,); lower is better."""
+        D, tot = self.D, self.total
+        return np.array([(D * int(q) + tot - 2 * int(a)) / D for a, q in zip(self.agree, self.pairs)], dtype=np.float64)
+
+    def pear(self):
+        """The posterior expected adjusted Rand index (Fritsch & Ickstadt 2009),
+        2 (agree P - pairs total) / ((D pairs + total) P - 2 pairs total) with P = n (n - 1) / 2, float64 (B,); NaN where
+        the denominator is 0; higher is better."""
+        D, tot, P = self.D, self.total, self.n * (self.n - 1) // 2
+        out = np.full(len(self.agree), np.nan, dtype=np.float64)
+        for b, (a, q) in enumerate(zip(self.agree, self.pairs)):
+            a, q = int(a), int(q)
+            den = (D * q + tot) * P - 2 * q * tot
+            if den != 0:
+                out[b] = 2 * (a * P - q * tot) / den
+        return out
+
+    def criterion(self, name):
+        if name not in ("pear", "binder"):
+            raise ValueError(f"criterion {name!r} is not 'pear' or 'binder'")
+        return self.pear() if name == "pear" else self.binder()
+
+
+def _argbest(values, criterion):
+    """The tie rule of select_consensus_allocations / best_sampled_allocation: the best double wins (highest PEAR, lowest
+    Binder), the earliest candidate among equal doubles, NaN candidates are skipped; all NaN raises ValueError."""
+    best = -1
+    for b, v in enumerate(values):
+        if v != v:
+            continue
+        if best < 0 or (v > values[best] if criterion == "pear" else v < values[best]):
+            best = b
+    if best < 0:
+        raise ValueError(f"every candidate's {criterion} is NaN (a single cluster against an all-ones matrix has no adjusted Rand index)")
+    return best
+
+
+def _which_matrix(psm, orderby, who):
+    K = psm.counts.shape[0]
+    n_mat = K + (1 if K > 1 else 0)
+    which = (n_mat if orderby == 0 else int(orderby)) - 1
+    if not 0 <= which < n_mat:
+        raise ValueError(f"{who}: orderby={orderby}: there are {n_mat} matrices")
+    return which
+
+
+def score_allocations(psm, candidates, orderby=0, ld=None):
+    """Candidate clusterings scored against a PsmCounts on the MI355X (pmdi_psm_score_device): the counts never leave the
+    device and no n x n temporary is made.  candidates: B clusterings of the n observations, labels of any value -- a CUDA
+    int32 tensor (B, n) or a strided view of one (unit stride along n, e.g. draws[:, k, :] of the resident (C, K, n) layout,
+    scored in place), or a numpy / int64 array (uploaded once as int32).  ld overrides the element stride between
+    candidates.  orderby as in get_consensus_allocations: 1-based, 0 = the last matrix ("Overall" when K > 1).  Returns
+    AllocationScores.  There is no CPU path: without a device this raises."""
+    import ctypes as C
+    import torch
+    from ._lib import _check, _ptr, lib
+    if not isinstance(psm, PsmCounts):
+        raise ValueError("score_allocations needs a PsmCounts (the device-resident counts)")
+    cnt = psm.counts
+    if not cnt.is_cuda or cnt.dtype != torch.int32 or cnt.dim() != 3 or cnt.shape[1] != cnt.shape[2]:
+        raise ValueError("score_allocations needs int32 CUDA counts (K, n, n)")
+    which = _which_matrix(psm, orderby, "score_allocations")
+    cnt = cnt.contiguous()
+    K, n, _ = cnt.shape
+    if not (isinstance(candidates, torch.Tensor) and candidates.is_cuda):
+        arr = np.asarray(candidates.cpu() if isinstance(candidates, torch.Tensor) else candidates)
+        if arr.ndim != 2 or not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError("score_allocations: candidates must be an integer array (B, n)")
+        if arr.size and (arr.min() < -2**31 or arr.max() >= 2**31):
+            raise ValueError("score_allocations: labels must fit int32")
+        candidates = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.int32)).to(cnt.device)
+    cand = candidates
+    if cand.dim() != 2 or cand.shape[1] != n or cand.shape[0] < 1:
+        raise ValueError(f"score_allocations: candidates {tuple(cand.shape)}, the counts hold n={n}")
+    if cand.device != cnt.device:
+        raise ValueError("score_allocations: candidates and counts are on different devices")
+    if cand.dtype != torch.int32:
+        cand = cand.to(torch.int32)
+    B = cand.shape[0]
+    if ld is None:
+        if (n > 1 and cand.stride(1) != 1) or (B > 1 and cand.stride(0) < n):
+            cand = cand.contiguous()
+        ld = cand.stride(0) if B > 1 else n
+    agree, pairs, total = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    st = torch.cuda.current_stream(cnt.device)
+    _check(lib().pmdi_psm_score_device(cnt.device.index or 0, C.c_void_p(cnt.data_ptr()), int(psm.S), K, n, which,
+                                       C.c_void_p(cand.data_ptr()), B, int(ld), _ptr(agree), _ptr(pairs), _ptr(total),
+                                       C.c_void_p(st.cuda_stream)))
+    return AllocationScores(agree, pairs, total[0], psm.S * (K if which == K else 1), n)
+
+
+def select_consensus_allocations(psm, k=range(2, 21), linkage=("ward",), orderby=0, criterion="pear"):
+    """Which cut of which dendrogram: for every linkage given, one psm_distance_device + hclust of the chosen matrix and one
+    cutree per k (k <= n), then ONE score_allocations call over all the cuts.  Returns (labels, table): the winning cut
+    (int64 labels 1.., as cutree gives them) and the rows (linkage, k, binder, pear) in candidate order -- linkages in the
+    order given, k ascending.  criterion "pear" (highest wins) or "binder" (lowest wins); among equal doubles the earliest
+    candidate wins, NaN PEAR candidates are skipped, all NaN raises ValueError."""
+    if criterion not in ("pear", "binder"):
+        raise ValueError(f"criterion {criterion!r} is not 'pear' or 'binder'")
+    if not isinstance(psm, PsmCounts):
+        raise ValueError("select_consensus_allocations needs a PsmCounts (the device-resident counts)")
+    which = _which_matrix(psm, orderby, "select_consensus_allocations")
+    n = psm.counts.shape[1]
+    linkages = [linkage] if isinstance(linkage, str) else list(linkage)
+    ks = sorted({int(x) for x in ([k] if np.isscalar(k) else k) if 1 <= int(x) <= n})
+    if not linkages or not ks:
+        raise ValueError("select_consensus_allocations: no candidate (no linkage, or no k in 1..n)")
+    cuts, rows = [], []
+    for lk in linkages:
+        hc = hclust(psm_distance_device(psm.counts, psm.S, which), lk, overwrite=True)
+        for kk in ks:
+            cuts.append(cutree(hc, k=kk))
+            rows.append((lk, kk))
+    sc = score_allocations(psm, np.stack(cuts), orderby=orderby)
+    binder, pear = sc.binder(), sc.pear()
+    best = _argbest(pear if criterion == "pear" else binder, criterion)
+    return cuts[best], [(lk, kk, float(binder[b]), float(pear[b])) for b, (lk, kk) in enumerate(rows)]
+
+
+def best_sampled_allocation(psm, draws, orderby=0, criterion="pear"):
+    """Which of the chains' own clusterings: draws is a CUDA int32 tensor (C, K, n) of 0-based labels, the resident layout
+    (pmdi_pooled(..., final_allocations=True)).  For orderby = dataset k the candidates are draws[:, k, :], scored in place
+    (ld = K n, no copy); for the "Overall" matrix all C K rows are.  Returns (labels, (chain, dataset), scores): the winner
+    renumbered 1.. by first appearance as cutree does (int64), its index, and the AllocationScores of all candidates in
+    (chain, dataset) order.  Tie rule of select_consensus_allocations."""
+    import torch
+    if criterion not in ("pear", "binder"):
+        raise ValueError(f"criterion {criterion!r} is not 'pear' or 'binder'")
+    if not isinstance(psm, PsmCounts):
+        raise ValueError("best_sampled_allocation needs a PsmCounts (the device-resident counts)")
+    K, n = psm.counts.shape[0], psm.counts.shape[1]
+    if not (isinstance(draws, torch.Tensor) and draws.is_cuda and draws.dtype == torch.int32 and draws.dim() == 3
+            and tuple(draws.shape[1:]) == (K, n) and draws.shape[0] >= 1):
+        raise ValueError(f"best_sampled_allocation needs a CUDA int32 tensor (C, {K}, {n}) of 0-based labels")
+    which = _which_matrix(psm, orderby, "best_sampled_allocation")
+    draws = draws.contiguous()
+    if which < K:
+        sc = score_allocations(psm, draws[:, which, :], orderby=orderby, ld=K * n)
+    else:
+        sc = score_allocations(psm, draws.view(-1, n), orderby=orderby, ld=n)
+    best = _argbest(sc.criterion(criterion), criterion)
+    chain, dataset = (best, which) if which < K else divmod(best, K)
+    raw = draws[chain, dataset].cpu().numpy()
+    _, first, inverse = np.unique(raw, return_index=True, return_inverse=True)
+    rank = np.empty(len(first), dtype=np.int64)
+    rank[np.argsort(first)] = np.arange(1, len(first) + 1)
+    return rank[inverse.reshape(-1)], (int(chain), int(dataset)), sc
 
 
 def generate_psm(outputFile, burnin=0, thin=1, host=False, device=None):
