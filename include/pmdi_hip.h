@@ -310,6 +310,56 @@ int pmdi_psm_score_device(int32_t device, const int32_t *counts, int64_t S, int3
                           int64_t *agree_out /* host, B */, int64_t *pairs_out /* host, B */, int64_t *total_out /* host, 1 */,
                           void *stream);
 
+/* ---- per-observation scores and a Binder descent -------------------------------------------------------------------
+ * Both rest on the affinity of observation i to a group g, A_i(g) = sum_{j in g, j != i} w_ij.  counts, S, K, n, which, w_ij
+ * and D are those of pmdi_psm_score_device: only counts[k][i][j] with i > j is read, w_ij := w_ji for i < j, the diagonal
+ * counts as D (p_ii = 1) and is never read; a stale or garbage upper triangle or diagonal changes nothing.
+ *
+ * pmdi_psm_rowscore_device: cand as in pmdi_psm_score_device (device int32, candidate b at cand + b ld, ld >= n, any label
+ * values, compared for equality only).  For every candidate b and observation i
+ *   own_out[b n + i]  = sum_{j != i, c_j == c_i} w_ij            (int64)
+ *   size_out[b n + i] = #{j : c_j == c_i}, i itself included, so >= 1  (int32)
+ * and once per call rowtotal_out[i] = sum_{j != i} w_ij (int64).  All three are DEVICE arrays ([B][n], [B][n], [n]; B n is
+ * 3 x 10^7 at n = 10 000, B = 3 072) and every element of them is written by the call, whatever they held before; the call is
+ * asynchronous on `stream` and allocates nothing (no n x n temporary: the sums are formed tile by tile).  Integers, exact in
+ * any summation order.  From them, per observation, with p = w / D:
+ *   the Wade-Ghahramani (2018) lower bound on the posterior expected variation of information of candidate b,
+ *     (1/n) sum_i [ log2 size_i + log2 (rowtotal_i + D) + log2 D - 2 log2 (own_i + D) ],
+ *   and the mean posterior similarity of i to the members of its own cluster, (own_i + D) / (D size_i).
+ * PMDI_E_ARG, before any device use: K outside 1..PMDI_KMAX; which outside 0..K, or which == K with K == 1; n < 1 or
+ * n > 65535; B < 1; ld < n; S < 1; a null pointer; D (n - 1) >= 2^62 (own and rowtotal stay inside int64).
+ * n = 1: own = 0, size = 1, rowtotal = 0.  A count above S is a caller error and is not checked.  Stateless.
+ *
+ * pmdi_psm_refine_device: a coordinate descent of Binder's loss from each of B start clusterings (device int32, start b at
+ * start + b ld).  A start label IS the slot of its group and must lie in 0..PMDI_REFINE_GMAX-1 (renumber by first appearance
+ * to get there); a label outside raises a device flag and the call returns PMDI_E_DATA with the outputs undefined.
+ * One sweep visits i = 0..n-1 in index order.  For the current i:
+ *   1. i is taken out of its group;
+ *   2. every live group g has gain(g) = 2 A_i(g) - D |g| (int64; |g| without i);
+ *   3. a new singleton has gain 0 and takes the lowest free slot;
+ *   4. it is offered only if i was not already alone and fewer than PMDI_REFINE_GMAX groups are live;
+ *   5. the options are ranked: i's current group (its own singleton if it was alone), the other live groups by ascending
+ *      slot, the new singleton;
+ *   6. the first option with the largest gain wins.
+ * So i moves only to something strictly better, and D x Binder's loss falls by gain(new) - gain(current) > 0, an integer: the
+ * descent is the same on every run.  Sweeps repeat until one makes no move or max_sweeps (>= 1) are done.
+ * labels_out: DEVICE int32 [B][n], the final slots.  moves_out (int64, all moves of the start) and sweeps_out (int32, sweeps
+ * performed, a last one without a move included) are HOST arrays of B; a start has converged iff its last sweep made no
+ * move: always when sweeps < max_sweeps; when all max_sweeps were used, iff a call with max_sweeps - 1 makes as many moves
+ * (for max_sweeps = 1, iff moves = 0).  One more sweep from the result (0 moves, 1 sweep) tells a fixed point.  The call allocates an n x n uint32 work matrix (w for the chosen
+ * matrix, mirrored; 0.4 GB at n = 10 000), frees it before it returns and therefore SYNCHRONISES `stream`.
+ * PMDI_E_ARG, before any device use: the conditions of pmdi_psm_rowscore_device except its last; D > 2^31 - 1;
+ * max_sweeps < 1.  n = 1: no move, one sweep.  Stateless. */
+#define PMDI_REFINE_GMAX 4096   /* slots of one start: what one workgroup's LDS holds in 64-bit bins plus sizes */
+int pmdi_psm_rowscore_device(int32_t device, const int32_t *counts, int64_t S, int32_t K, int64_t n, int32_t which,
+                             const int32_t *cand, int64_t B, int64_t ld,
+                             int64_t *own_out /* device, B n */, int32_t *size_out /* device, B n */,
+                             int64_t *rowtotal_out /* device, n */, void *stream);
+int pmdi_psm_refine_device(int32_t device, const int32_t *counts, int64_t S, int32_t K, int64_t n, int32_t which,
+                           const int32_t *start, int64_t B, int64_t ld, int32_t max_sweeps,
+                           int32_t *labels_out /* device, B n */, int64_t *moves_out /* host, B */,
+                           int32_t *sweeps_out /* host, B */, void *stream);
+
 /* ---- device-resident Gibbs chains -----------------------------------------
  * Everything pmdi() does per iteration AROUND the sweep, for every chain of the handle, without leaving the
  * device: shuffle!(order_obs) (src/pmdi.jl:172), update_M!, update_gamma!, Pi, update_Phi!, update_Z, update_v

@@ -5,13 +5,13 @@ with `__graft_entry__.load_package()` which registers it as `particlemdi_jl_amd`
 """
 from ._lib import (  # noqa: F401
     ABI_VERSION, CATEGORICAL, EXPORTS, GAUSSIAN, KIND_BY_NAME, LIB_PATH, NEGBINOM,
-    ClusterBatch, Comm, CsvWriter, Gibbs, format_float64, read_allocations, PmdiError, Sweeper, build, lib,
+    ClusterBatch, Comm, CsvWriter, Gibbs, format_float64, read_allocations, PmdiError, REFINE_GMAX, Sweeper, build, lib,
     STEP_ALIGN, STEP_BEGIN, STEP_FEATSEL, STEP_HYPERS, STEP_SWEEP,
 )
 from .pmdi import pmdi_pooled  # noqa: F401,E402    (not pmdi(): the name is the submodule's)
 from .psm import (  # noqa: F401,E402
-    AllocationScores, PsmAccumulator, PsmCounts, best_sampled_allocation, retained_iterations, score_allocations,
-    select_consensus_allocations,
+    AllocationRowScores, AllocationScores, PsmAccumulator, PsmCounts, best_sampled_allocation, refine_allocations,
+    retained_iterations, row_scores, score_allocations, search_consensus_allocation, select_consensus_allocations,
 )
 from .summary import (  # noqa: F401,E402
     PosteriorSummary, SummaryAccumulator, get_feature_select_probs, get_nclust, get_phi,

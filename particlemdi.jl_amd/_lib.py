@@ -12,7 +12,7 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("PMDI_LIB_PATH") or os.path.join(_PKG, "libpmdi_hip.so")   # override: A/B builds only
-_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_summary.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_api.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
+_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_summary.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_api.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
 _HEADERS = [os.path.join(_PKG, "csrc", "pmdi_internal.h"), os.path.join(_PKG, "csrc", "pmdi_device.h"),
             os.path.join(_PKG, "csrc", "pmdi_sweep_body.h"), os.path.join(_PKG, "csrc", "pmdi_sweep2_body.h"),
             os.path.join(_PKG, "csrc", "pmdi_arith.h"),
@@ -24,6 +24,7 @@ KIND_BY_NAME = {"gaussian": GAUSSIAN, "categorical": CATEGORICAL, "negbinom": NE
                 "NegBinomCluster": NEGBINOM}
 ABI_VERSION = 2
 KMAX = 8
+REFINE_GMAX = 4096      # PMDI_REFINE_GMAX of include/pmdi_hip.h
 
 EXPORTS = [
     "pmdi_create", "pmdi_destroy", "pmdi_last_error", "pmdi_abi_version", "pmdi_sweep",
@@ -42,7 +43,7 @@ EXPORTS = [
     "pmdi_psm_acc_merge", "pmdi_psm_acc_samples", "pmdi_psm_acc_counts", "pmdi_gibbs_run",
     "pmdi_summary_create", "pmdi_summary_destroy", "pmdi_summary_reset", "pmdi_summary_add_gibbs", "pmdi_summary_add_arrays",
     "pmdi_summary_samples", "pmdi_summary_get", "pmdi_gibbs_run2",
-    "pmdi_psm_score_device",
+    "pmdi_psm_score_device", "pmdi_psm_rowscore_device", "pmdi_psm_refine_device",
 ]
 
 
@@ -203,6 +204,10 @@ def lib():
     L.pmdi_hclust_device.argtypes = [i32, vp, i32, i64, i32, vp, vp, vp, vp]
     L.pmdi_psm_score_device.restype = C.c_int
     L.pmdi_psm_score_device.argtypes = [i32, vp, i64, i32, i64, i32, vp, i64, i64, vp, vp, vp, vp]
+    L.pmdi_psm_rowscore_device.restype = C.c_int
+    L.pmdi_psm_rowscore_device.argtypes = [i32, vp, i64, i32, i64, i32, vp, i64, i64, vp, vp, vp, vp]
+    L.pmdi_psm_refine_device.restype = C.c_int
+    L.pmdi_psm_refine_device.argtypes = [i32, vp, i64, i32, i64, i32, vp, i64, i64, i32, vp, vp, vp, vp]
     L.pmdi_cutree.restype = C.c_int
     L.pmdi_cutree.argtypes = [i64, vp, vp, i64, dbl, vp]
     L.pmdi_psm_acc_create.restype = C.c_int

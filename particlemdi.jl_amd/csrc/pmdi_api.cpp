@@ -982,6 +982,72 @@ int pmdi_psm_score_device(int32_t device, const int32_t *counts, int64_t S, int3
     return PMDI_OK;
 }
 
+// the conditions pmdi_psm_score_device, pmdi_psm_rowscore_device and pmdi_psm_refine_device share; 0 or PMDI_E_ARG
+static int psm_shared_args(const char *who, int64_t S, int32_t K, int64_t n, int32_t which, int64_t B, int64_t ld)
+{
+    if (K < 1 || K > PMDI_KMAX || S < 1 || n < 1 || n > 65535 || B < 1 || ld < n)
+        return fail(PMDI_E_ARG, "%s: S=%lld K=%d n=%lld B=%lld ld=%lld out of range (K <= %d, n <= 65535, ld >= n)", who,
+                    (long long)S, K, (long long)n, (long long)B, (long long)ld, PMDI_KMAX);
+    if (which < 0 || which > K || (which == K && K == 1))
+        return fail(PMDI_E_ARG, "%s: which=%d, but there are %d matrices (the Overall one only for K > 1)", who, which, K + (K > 1));
+    return PMDI_OK;
+}
+
+int pmdi_psm_rowscore_device(int32_t device, const int32_t *counts, int64_t S, int32_t K, int64_t n, int32_t which,
+                             const int32_t *cand, int64_t B, int64_t ld, int64_t *own_out, int32_t *size_out, int64_t *rowtotal_out,
+                             void *stream)
+{
+    if (!counts || !cand || !own_out || !size_out || !rowtotal_out) return fail(PMDI_E_ARG, "pmdi_psm_rowscore_device: null argument");
+    const int rc = psm_shared_args("pmdi_psm_rowscore_device", S, K, n, which, B, ld);
+    if (rc) return rc;
+    const unsigned __int128 D = (unsigned __int128)S * (unsigned)(which == K ? K : 1);
+    if (D * (unsigned __int128)(n - 1) >= ((unsigned __int128)1 << 62))       // own and rowtotal stay inside int64
+        return fail(PMDI_E_ARG, "pmdi_psm_rowscore_device: S=%lld with n=%lld: D (n - 1) >= 2^62", (long long)S, (long long)n);
+    HIP_TRY(hipSetDevice(device));
+    const hipError_t e = pmdi_launch_psm_rowscore(counts, K, n, which, D > ((unsigned __int128)1 << 22) ? 1 : 0, cand, B, ld,
+                                                  (unsigned long long *)own_out, size_out, (unsigned long long *)rowtotal_out,
+                                                  (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "psm-rowscore launch: %s", hipGetErrorString(e));
+    return PMDI_OK;
+}
+
+static_assert(PMDI_REFINE_GMAX == PMDI_REFINE_GMAX_I, "the header's slot count is the kernels'");
+
+int pmdi_psm_refine_device(int32_t device, const int32_t *counts, int64_t S, int32_t K, int64_t n, int32_t which,
+                           const int32_t *start, int64_t B, int64_t ld, int32_t max_sweeps, int32_t *labels_out, int64_t *moves_out,
+                           int32_t *sweeps_out, void *stream)
+{
+    if (!counts || !start || !labels_out || !moves_out || !sweeps_out) return fail(PMDI_E_ARG, "pmdi_psm_refine_device: null argument");
+    const int rc = psm_shared_args("pmdi_psm_refine_device", S, K, n, which, B, ld);
+    if (rc) return rc;
+    const unsigned __int128 D = (unsigned __int128)S * (unsigned)(which == K ? K : 1);
+    if (D > 2147483647u)                             // a w fits the uint32 work matrix and a gain fits int64 with room to spare
+        return fail(PMDI_E_ARG, "pmdi_psm_refine_device: S=%lld: D > 2^31 - 1", (long long)S);
+    if (max_sweeps < 1) return fail(PMDI_E_ARG, "pmdi_psm_refine_device: max_sweeps=%d < 1", max_sweeps);
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    struct Scratch {
+        void *p = nullptr;
+        ~Scratch() { if (p) (void)hipFree(p); }
+    } work, out;
+    const size_t out_bytes = (size_t)B * 12 + 8;     // B moves, B sweeps, the flag
+    HIP_TRY(hipMalloc(&work.p, (size_t)n * (size_t)n * 4));
+    HIP_TRY(hipMalloc(&out.p, out_bytes));
+    HIP_TRY(hipMemsetAsync(out.p, 0, out_bytes, st));
+    long long *d_moves = (long long *)out.p;
+    int *d_sweeps = (int *)((char *)out.p + (size_t)B * 8), *d_flag = d_sweeps + B;
+    const hipError_t e = pmdi_launch_psm_refine(counts, K, n, which, (long long)D, D * (unsigned __int128)n >= ((unsigned __int128)1 << 32) ? 1 : 0,
+                                                (unsigned *)work.p, start, B, ld, max_sweeps, labels_out, d_moves, d_sweeps, d_flag, st);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "psm-refine launch: %s", hipGetErrorString(e));
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(moves_out, d_moves, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(sweeps_out, d_sweeps, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&bad, d_flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));               // the work matrix is freed on return
+    if (bad) return fail(PMDI_E_DATA, "pmdi_psm_refine_device: a start label outside 0..%d", PMDI_REFINE_GMAX - 1);
+    return PMDI_OK;
+}
+
 int pmdi_psm_acc_destroy(pmdi_psm_acc *a)
 {
     if (!a) return PMDI_OK;

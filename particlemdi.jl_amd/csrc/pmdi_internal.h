@@ -239,6 +239,15 @@ hipError_t pmdi_launch_psm_acc_merge(int *a, const int *b, int K, long long n, h
 // candidates scored against the counts (pmdi_psm_score.hip): out = B agree, B pairs, 1 total, zeroed by the caller; wide: D > 2^22
 hipError_t pmdi_launch_psm_score(const int *counts, int K, long long n, int which, int wide, const int *cand, long long B, long long ld,
                                  unsigned long long *out, hipStream_t stream);
+// per-observation scores (pmdi_psm_rowscore.hip): own [B][n], size [B][n], rowtotal [n], every element written once; wide: D > 2^22
+hipError_t pmdi_launch_psm_rowscore(const int *counts, int K, long long n, int which, int wide, const int *cand, long long B, long long ld,
+                                    unsigned long long *own, int *size, unsigned long long *rowtotal, hipStream_t stream);
+// Binder descent (pmdi_psm_refine.hip): W = n x n uint32 work space; labels [B][n], moves [B], sweeps [B], flag [1] (zeroed by the
+// caller) on the device; wide: D n >= 2^32
+#define PMDI_REFINE_GMAX_I 4096      // PMDI_REFINE_GMAX of include/pmdi_hip.h: 4096 x (8 + 4) bytes of one workgroup's LDS
+hipError_t pmdi_launch_psm_refine(const int *counts, int K, long long n, int which, long long D, int wide, unsigned *W, const int *start,
+                                  long long B, long long ld, int max_sweeps, int *labels, long long *moves, int *sweeps, int *flag,
+                                  hipStream_t stream);
 
 // One add of the streaming summary accumulator (pmdi_summary.hip): the source arrays in the GibbsArgs layouts, the
 // accumulator's state, and this add's trace row.

@@ -445,6 +445,32 @@ function pear(agree, pairs, total, D, n)
     end
 end
 
+# ---- per-observation scores and the Binder descent (pmdi_psm_rowscore_device, pmdi_psm_refine_device; not executed, as above) ----
+# own, size, rowtotal: device pointers to Int64 [B][n], Int32 [B][n], Int64 [n] that the call fills (asynchronous on stream).
+function psm_rowscore_device(counts::Ptr{Cvoid}, S::Integer, K::Integer, n::Integer, which::Integer, cand::Ptr{Cvoid}, B::Integer,
+                             own::Ptr{Cvoid}, size::Ptr{Cvoid}, rowtotal::Ptr{Cvoid}, ld::Integer = n;
+                             device::Integer = 0, stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:pmdi_psm_rowscore_device, LIB), Cint,
+                (Int32, Ptr{Cvoid}, Int64, Int32, Int64, Int32, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                device, counts, S, K, n, which - 1, cand, B, ld, own, size, rowtotal, stream))
+    return S * (which == K + 1 ? K : 1)
+end
+# own, size: one candidate's rows copied to the host; the Wade-Ghahramani bound and the per-observation confidence
+vi_bound(own, size, rowtotal, D) =
+    sum(log2.(Float64.(size)) .+ log2.(Float64.(rowtotal .+ D)) .+ log2(Float64(D)) .- 2 .* log2.(Float64.(own .+ D))) / length(own)
+confidence(own, size, D) = Float64.(own .+ D) ./ Float64.(D .* size)
+const REFINE_GMAX = 4096
+# start: device pointer to Int32 slot labels 0..REFINE_GMAX-1, start b at start + b * ld; labels: device Int32 [B][n], filled.
+# Returns (moves, sweeps) per start; synchronises.
+function psm_refine_device(counts::Ptr{Cvoid}, S::Integer, K::Integer, n::Integer, which::Integer, start::Ptr{Cvoid}, B::Integer,
+                           labels::Ptr{Cvoid}, ld::Integer = n; max_sweeps::Integer = 64, device::Integer = 0, stream::Ptr{Cvoid} = C_NULL)
+    moves = Vector{Int64}(undef, B); sweeps = Vector{Int32}(undef, B)
+    check(ccall((:pmdi_psm_refine_device, LIB), Cint,
+                (Int32, Ptr{Cvoid}, Int64, Int32, Int64, Int32, Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Ptr{Cvoid}),
+                device, counts, S, K, n, which - 1, start, B, ld, max_sweeps, labels, moves, sweeps, stream))
+    return moves, sweeps
+end
+
 # ---- the cluster plugin protocol on the device (unit-level entry points) ----------------------
 # calc_logprob / cluster_add! / calc_logmarginal for a batch of stand-alone clusters of dataset k;
 # see pmdi_clusters_new, pmdi_cluster_add, pmdi_calc_logprob, pmdi_calc_logmarginal in the header.

@@ -13,6 +13,10 @@ get_consensus_allocations below; include/pmdi_hip.h states the tie rule).
 The reference stops there, with k or h left to the caller.  score_allocations ranks candidate clusterings by Binder's loss
 and by the posterior expected adjusted Rand index against the device-resident counts (pmdi_psm_score_device);
 select_consensus_allocations picks the cut and the linkage with it, best_sampled_allocation one of the chains' own states.
+
+row_scores keeps those sums per observation (pmdi_psm_rowscore_device): how firmly each observation sits in its cluster, and
+the variation-of-information bound of Wade & Ghahramani (2018).  refine_allocations is a coordinate descent of Binder's loss
+from given starts (pmdi_psm_refine_device); search_consensus_allocation runs it from every cut and selects by VI, Binder or PEAR.
 """
 import numpy as np
 
@@ -466,6 +470,200 @@ def select_consensus_allocations(psm, k=range(2, 21), linkage=("ward",), orderby
     binder, pear = sc.binder(), sc.pear()
     best = _argbest(pear if criterion == "pear" else binder, criterion)
     return cuts[best], [(lk, kk, float(binder[b]), float(pear[b])) for b, (lk, kk) in enumerate(rows)]
+
+
+def _device_candidates(cnt, candidates, ld, who):
+    """The candidates of score_allocations as an int32 CUDA tensor (B, n) on the counts' device and the element stride between
+    them: numpy / host integer arrays are uploaded once, a CUDA tensor or a strided view of one (unit stride along n) is used
+    in place."""
+    import torch
+    n = cnt.shape[1]
+    if not (isinstance(candidates, torch.Tensor) and candidates.is_cuda):
+        arr = np.asarray(candidates.cpu() if isinstance(candidates, torch.Tensor) else candidates)
+        if arr.ndim != 2 or not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError(f"{who}: candidates must be an integer array (B, n)")
+        if arr.size and (arr.min() < -2**31 or arr.max() >= 2**31):
+            raise ValueError(f"{who}: labels must fit int32")
+        candidates = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.int32)).to(cnt.device)
+    cand = candidates
+    if cand.dim() != 2 or cand.shape[1] != n or cand.shape[0] < 1:
+        raise ValueError(f"{who}: candidates {tuple(cand.shape)}, the counts hold n={n}")
+    if cand.device != cnt.device:
+        raise ValueError(f"{who}: candidates and counts are on different devices")
+    if cand.dtype != torch.int32:
+        cand = cand.to(torch.int32)
+    B = cand.shape[0]
+    if ld is None:
+        if (n > 1 and cand.stride(1) != 1) or (B > 1 and cand.stride(0) < n):
+            cand = cand.contiguous()
+        ld = cand.stride(0) if B > 1 else n
+    return cand, int(ld)
+
+
+def _checked_counts(psm, who):
+    import torch
+    if not isinstance(psm, PsmCounts):
+        raise ValueError(f"{who} needs a PsmCounts (the device-resident counts)")
+    cnt = psm.counts
+    if not cnt.is_cuda or cnt.dtype != torch.int32 or cnt.dim() != 3 or cnt.shape[1] != cnt.shape[2]:
+        raise ValueError(f"{who} needs int32 CUDA counts (K, n, n)")
+    return cnt.contiguous()
+
+
+class AllocationRowScores:
+    """What row_scores returns, all exact integers (include/pmdi_hip.h, pmdi_psm_rowscore_device): per candidate b and
+    observation i `own[b, i]` = sum_{j != i, c_j == c_i} w_ij and `size[b, i]` = the size of i's cluster (int64 numpy, (B, n)),
+    `rowtotal[i]` = sum_{j != i} w_ij (int64, (n,)), `D` = the divisor of the scored matrix (S, or S K for "Overall"), `n`
+    observations.  With p_ij = w_ij / D and p_ii = 1: own + D = D sum_j [c_j == c_i] p_ij and rowtotal + D = D sum_j p_ij."""
+
+    def __init__(self, own, size, rowtotal, D, n):
+        self.own, self.size, self.rowtotal, self.D, self.n = own, size, rowtotal, int(D), int(n)
+
+    def vi(self):
+        """The lower bound of Wade & Ghahramani (2018) on the posterior expected variation of information,
+        (1/n) sum_i [log2 size_i + log2 (rowtotal_i + D) + log2 D - 2 log2 (own_i + D)], float64 (B,); lower is better.
+        Float64 throughout: every integer goes to the nearest double, the sum over i is math.fsum, one division by n."""
+        import math
+        D = self.D
+        fixed = np.log2((np.asarray(self.rowtotal, dtype=np.int64) + D).astype(np.float64))
+        log_d = np.log2(np.float64(D))
+        out = np.zeros(len(self.own), dtype=np.float64)
+        for b in range(len(self.own)):
+            terms = np.log2(np.asarray(self.size[b], dtype=np.int64).astype(np.float64)) + fixed + log_d \
+                - 2.0 * np.log2((np.asarray(self.own[b], dtype=np.int64) + D).astype(np.float64))
+            out[b] = math.fsum(terms.tolist()) / self.n
+        return out
+
+    def confidence(self):
+        """(own_i + D) / (D size_i), float64 (B, n): the mean posterior similarity of i to the members of its own cluster
+        (itself included, p_ii = 1), in [0, 1]."""
+        num = (np.asarray(self.own, dtype=np.int64) + self.D).astype(np.float64)
+        return num / (np.asarray(self.size, dtype=np.int64) * self.D).astype(np.float64)
+
+
+def row_scores(psm, candidates, orderby=0, ld=None, max_bytes=1 << 30):
+    """Per-observation scores of candidate clusterings against a PsmCounts on the MI355X (pmdi_psm_rowscore_device): the
+    counts never leave the device and no n x n temporary is made.  psm, candidates, orderby and ld as in score_allocations.
+    The candidates are processed in slabs so that the device result buffers (12 bytes per candidate and observation) stay
+    under max_bytes; each slab comes to the host as it is finished.  Returns AllocationRowScores.  There is no CPU path."""
+    import ctypes as C
+    import torch
+    from ._lib import _check, lib
+    cnt = _checked_counts(psm, "row_scores")
+    which = _which_matrix(psm, orderby, "row_scores")
+    K, n, _ = cnt.shape
+    cand, ld = _device_candidates(cnt, candidates, ld, "row_scores")
+    B = cand.shape[0]
+    slab = int(max(1, min(B, int(max_bytes) // (12 * n))))
+    own, size = np.zeros((B, n), dtype=np.int64), np.zeros((B, n), dtype=np.int64)
+    d_own = torch.empty((slab, n), dtype=torch.int64, device=cnt.device)
+    d_size = torch.empty((slab, n), dtype=torch.int32, device=cnt.device)
+    d_tot = torch.empty((n,), dtype=torch.int64, device=cnt.device)
+    st = torch.cuda.current_stream(cnt.device)
+    for at in range(0, B, slab):
+        nb = min(slab, B - at)
+        _check(lib().pmdi_psm_rowscore_device(cnt.device.index or 0, C.c_void_p(cnt.data_ptr()), int(psm.S), K, n, which,
+                                              C.c_void_p(cand.data_ptr() + 4 * at * ld), nb, ld, C.c_void_p(d_own.data_ptr()),
+                                              C.c_void_p(d_size.data_ptr()), C.c_void_p(d_tot.data_ptr()), C.c_void_p(st.cuda_stream)))
+        own[at:at + nb] = d_own[:nb].cpu().numpy()
+        size[at:at + nb] = d_size[:nb].cpu().numpy()
+    return AllocationRowScores(own, size, d_tot.cpu().numpy(), psm.S * (K if which == K else 1), n)
+
+
+def _first_appearance(rows, base):
+    """Every row of an integer array (B, n) renumbered base, base + 1, .. in order of first appearance (what cutree does
+    with base = 1); int64, and the number of distinct labels of every row."""
+    rows = np.asarray(rows)
+    out = np.zeros(rows.shape, dtype=np.int64)
+    distinct = np.zeros(len(rows), dtype=np.int64)
+    for b, raw in enumerate(rows):
+        _, first, inverse = np.unique(raw, return_index=True, return_inverse=True)
+        rank = np.empty(len(first), dtype=np.int64)
+        rank[np.argsort(first)] = np.arange(base, base + len(first))
+        out[b], distinct[b] = rank[inverse.reshape(-1)], len(first)
+    return out, distinct
+
+
+def refine_allocations(psm, starts, orderby=0, max_sweeps=64):
+    """A coordinate descent of Binder's loss from each start clustering, on the MI355X (pmdi_psm_refine_device; the visiting
+    order, the gains and the tie rule are in include/pmdi_hip.h): sweeps over i = 0..n-1 in which i moves to the group, or
+    to a new singleton, that lowers the loss most, until a sweep makes no move or max_sweeps are done.  Integer gains: the
+    same result on every run.  starts: (B, n) integer labels of any value, numpy or a CUDA tensor; every row is renumbered
+    0.. by first appearance first and may hold at most REFINE_GMAX (4096) distinct labels (ValueError otherwise).
+    Returns (labels, info): labels int64 (B, n) renumbered 1.. by first appearance as cutree does; info = {"moves": int64
+    (B,), "sweeps": int64 (B,), "converged": bool (B,)}, converged = the last sweep made no move.  There is no CPU path."""
+    import ctypes as C
+    import torch
+    from ._lib import REFINE_GMAX, _check, _ptr, lib
+    cnt = _checked_counts(psm, "refine_allocations")
+    which = _which_matrix(psm, orderby, "refine_allocations")
+    K, n, _ = cnt.shape
+    arr = np.asarray(starts.cpu() if isinstance(starts, torch.Tensor) else starts)
+    if arr.ndim != 2 or arr.shape[1] != n or arr.shape[0] < 1 or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(f"refine_allocations: starts must be an integer array (B, {n})")
+    if int(max_sweeps) < 1:
+        raise ValueError("refine_allocations: max_sweeps must be at least 1")
+    slots, distinct = _first_appearance(arr, 0)
+    if distinct.max() > REFINE_GMAX:
+        raise ValueError(f"refine_allocations: a start has {int(distinct.max())} distinct labels, at most {REFINE_GMAX} fit")
+    B = arr.shape[0]
+    st = torch.cuda.current_stream(cnt.device)
+
+    def run(d_start, nb, sweeps_cap):
+        d_out = torch.empty((nb, n), dtype=torch.int32, device=cnt.device)
+        moves, sweeps = np.zeros(nb, dtype=np.int64), np.zeros(nb, dtype=np.int32)
+        _check(lib().pmdi_psm_refine_device(cnt.device.index or 0, C.c_void_p(cnt.data_ptr()), int(psm.S), K, n, which,
+                                            C.c_void_p(d_start.data_ptr()), nb, n, int(sweeps_cap), C.c_void_p(d_out.data_ptr()),
+                                            _ptr(moves), _ptr(sweeps), C.c_void_p(st.cuda_stream)))
+        return d_out, moves, sweeps
+
+    d_start = torch.from_numpy(slots.astype(np.int32)).to(cnt.device)
+    d_out, moves, sweeps = run(d_start, B, max_sweeps)
+    converged = sweeps < int(max_sweeps)
+    capped = np.flatnonzero(~converged)
+    if len(capped):                 # all sweeps used: the last one made no move iff a run one sweep shorter made as many moves
+        fewer = np.zeros(len(capped), dtype=np.int64)
+        if int(max_sweeps) > 1:
+            _, fewer, _ = run(d_start[torch.from_numpy(capped).to(cnt.device)].contiguous(), len(capped), int(max_sweeps) - 1)
+        converged[capped] = moves[capped] == fewer
+    labels, _ = _first_appearance(d_out.cpu().numpy(), 1)
+    return labels, {"moves": moves, "sweeps": sweeps.astype(np.int64), "converged": converged}
+
+
+def search_consensus_allocation(psm, k=range(2, 21), linkage=("ward",), orderby=0, criterion="vi", refine=True, max_sweeps=64):
+    """select_consensus_allocations with a search and a third criterion: the candidates are the cuts k of every linkage (formed
+    exactly as there) and, with refine=True, after all the cuts the refine_allocations form of each cut in the same order.
+    All candidates are scored by ONE score_allocations and ONE row_scores call.  Returns (labels, table): the winner (int64
+    labels 1..) and the rows (source, linkage, k, n_clusters, binder, pear, vi) in candidate order, source "cut" or "refined".
+    criterion "vi" (AllocationRowScores.vi, lowest wins), "binder" (lowest) or "pear" (highest); among equal doubles the
+    earliest candidate wins, NaN candidates are skipped, all NaN raises ValueError."""
+    if criterion not in ("vi", "binder", "pear"):
+        raise ValueError(f"criterion {criterion!r} is not 'vi', 'binder' or 'pear'")
+    if not isinstance(psm, PsmCounts):
+        raise ValueError("search_consensus_allocation needs a PsmCounts (the device-resident counts)")
+    which = _which_matrix(psm, orderby, "search_consensus_allocation")
+    n = psm.counts.shape[1]
+    linkages = [linkage] if isinstance(linkage, str) else list(linkage)
+    ks = sorted({int(x) for x in ([k] if np.isscalar(k) else k) if 1 <= int(x) <= n})
+    if not linkages or not ks:
+        raise ValueError("search_consensus_allocation: no candidate (no linkage, or no k in 1..n)")
+    cuts, rows = [], []
+    for lk in linkages:
+        hc = hclust(psm_distance_device(psm.counts, psm.S, which), lk, overwrite=True)
+        for kk in ks:
+            cuts.append(cutree(hc, k=kk))
+            rows.append(("cut", lk, kk))
+    cand = np.stack(cuts)
+    if refine:
+        refined, _ = refine_allocations(psm, cand, orderby=orderby, max_sweeps=max_sweeps)
+        cand = np.concatenate([cand, refined])
+        rows += [("refined", lk, kk) for _, lk, kk in rows]
+    sc = score_allocations(psm, cand, orderby=orderby)
+    binder, pear, vi = sc.binder(), sc.pear(), row_scores(psm, cand, orderby=orderby).vi()
+    best = _argbest({"vi": vi, "binder": binder, "pear": pear}[criterion], criterion)
+    table = [(src, lk, kk, int(len(np.unique(cand[b]))), float(binder[b]), float(pear[b]), float(vi[b]))
+             for b, (src, lk, kk) in enumerate(rows)]
+    return cand[best].astype(np.int64), table
 
 
 def best_sampled_allocation(psm, draws, orderby=0, criterion="pear"):
