@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("PMDI_LIB_PATH") or os.path.join(_PKG, "libpmdi_hip.so
 _SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_summary.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_api.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
 _HEADERS = [os.path.join(_PKG, "csrc", "pmdi_internal.h"), os.path.join(_PKG, "csrc", "pmdi_device.h"),
             os.path.join(_PKG, "csrc", "pmdi_sweep_body.h"), os.path.join(_PKG, "csrc", "pmdi_sweep2_body.h"),
-            os.path.join(_PKG, "csrc", "pmdi_arith.h"),
+            os.path.join(_PKG, "csrc", "pmdi_arith.h"), os.path.join(_PKG, "csrc", "pmdi_psm_device.h"),
             os.path.join(_ROOT, "include", "pmdi_hip.h")]
 
 GAUSSIAN, CATEGORICAL, NEGBINOM = 0, 1, 2

@@ -75,6 +75,15 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
 };
 
+// device memory of one call, freed on return
+struct Scratch {
+    void *p = nullptr;
+    ~Scratch() { if (p) (void)hipFree(p); }
+};
+
+// the divisor of the `which` matrix of counts (pmdi_psm_*_device): S, or S K for the Overall one
+unsigned __int128 psm_divisor(int64_t S, int32_t K, int32_t which) { return (unsigned __int128)S * (unsigned)(which == K ? K : 1); }
+
 // fills the arena offsets of one dataset; returns the per-chain stride
 size_t layout_arena(DsetDev &d, int N, int P, long long cap, long long n_rows_sstar, bool sweep_state)
 {
@@ -123,6 +132,21 @@ int pmdi_set_error(int code, const char *fmt, ...)
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return code;
+}
+
+// the conditions the functions that take a `which` matrix of counts share; 0 or PMDI_E_ARG.
+// cand: the function takes B candidates ld labels apart and sums over at most PMDI_KMAX datasets; pmdi_psm_distance_device
+// (pmdi_hclust.hip) does neither and keeps its own wording of the range
+int pmdi_psm_shared_args(const char *who, int64_t S, int32_t K, int64_t n, int32_t which, bool cand, int64_t B, int64_t ld)
+{
+    if (cand && (K < 1 || K > PMDI_KMAX || S < 1 || n < 1 || n > 65535 || B < 1 || ld < n))
+        return fail(PMDI_E_ARG, "%s: S=%lld K=%d n=%lld B=%lld ld=%lld out of range (K <= %d, n <= 65535, ld >= n)", who,
+                    (long long)S, K, (long long)n, (long long)B, (long long)ld, PMDI_KMAX);
+    if (!cand && (S < 1 || K < 1 || n < 1 || n > 65535))
+        return fail(PMDI_E_ARG, "%s: S=%lld K=%d n=%lld out of range (n <= 65535)", who, (long long)S, K, (long long)n);
+    if (which < 0 || which > K || (which == K && K == 1))
+        return fail(PMDI_E_ARG, "%s: which=%d, but there are %d matrices (the Overall one only for K > 1)", who, which, K + (K > 1));
+    return PMDI_OK;
 }
 
 struct pmdi_handle {
@@ -948,14 +972,10 @@ int pmdi_psm_score_device(int32_t device, const int32_t *counts, int64_t S, int3
                           void *stream)
 {
     if (!counts || !cand || !agree_out || !pairs_out || !total_out) return fail(PMDI_E_ARG, "pmdi_psm_score_device: null argument");
-    if (K < 1 || K > PMDI_KMAX || S < 1 || n < 1 || n > 65535 || B < 1 || ld < n)
-        return fail(PMDI_E_ARG, "pmdi_psm_score_device: S=%lld K=%d n=%lld B=%lld ld=%lld out of range (K <= %d, n <= 65535, ld >= n)",
-                    (long long)S, K, (long long)n, (long long)B, (long long)ld, PMDI_KMAX);
-    if (which < 0 || which > K || (which == K && K == 1))
-        return fail(PMDI_E_ARG, "pmdi_psm_score_device: which=%d, but there are %d matrices (the Overall one only for K > 1)", which,
-                    K + (K > 1));
+    const int rc = pmdi_psm_shared_args("pmdi_psm_score_device", S, K, n, which, true, B, ld);
+    if (rc) return rc;
     const unsigned __int128 P = (unsigned __int128)(n * (n - 1) / 2);
-    const unsigned __int128 D = (unsigned __int128)S * (unsigned)(which == K ? K : 1);
+    const unsigned __int128 D = psm_divisor(S, K, which);
     if (D * P >= ((unsigned __int128)1 << 62))       // D pairs + total and every other sum of the criteria stay inside int64
         return fail(PMDI_E_ARG, "pmdi_psm_score_device: S=%lld with n=%lld: D n (n - 1) / 2 >= 2^62", (long long)S, (long long)n);
     if (n == 1) {                                    // no pairs
@@ -965,10 +985,7 @@ int pmdi_psm_score_device(int32_t device, const int32_t *counts, int64_t S, int3
     }
     HIP_TRY(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
-    struct Scratch {
-        void *p = nullptr;
-        ~Scratch() { if (p) (void)hipFree(p); }
-    } out;
+    Scratch out;
     const size_t bytes = ((size_t)2 * B + 1) * sizeof(unsigned long long);
     HIP_TRY(hipMalloc(&out.p, bytes));
     HIP_TRY(hipMemsetAsync(out.p, 0, bytes, st));
@@ -982,25 +999,14 @@ int pmdi_psm_score_device(int32_t device, const int32_t *counts, int64_t S, int3
     return PMDI_OK;
 }
 
-// the conditions pmdi_psm_score_device, pmdi_psm_rowscore_device and pmdi_psm_refine_device share; 0 or PMDI_E_ARG
-static int psm_shared_args(const char *who, int64_t S, int32_t K, int64_t n, int32_t which, int64_t B, int64_t ld)
-{
-    if (K < 1 || K > PMDI_KMAX || S < 1 || n < 1 || n > 65535 || B < 1 || ld < n)
-        return fail(PMDI_E_ARG, "%s: S=%lld K=%d n=%lld B=%lld ld=%lld out of range (K <= %d, n <= 65535, ld >= n)", who,
-                    (long long)S, K, (long long)n, (long long)B, (long long)ld, PMDI_KMAX);
-    if (which < 0 || which > K || (which == K && K == 1))
-        return fail(PMDI_E_ARG, "%s: which=%d, but there are %d matrices (the Overall one only for K > 1)", who, which, K + (K > 1));
-    return PMDI_OK;
-}
-
 int pmdi_psm_rowscore_device(int32_t device, const int32_t *counts, int64_t S, int32_t K, int64_t n, int32_t which,
                              const int32_t *cand, int64_t B, int64_t ld, int64_t *own_out, int32_t *size_out, int64_t *rowtotal_out,
                              void *stream)
 {
     if (!counts || !cand || !own_out || !size_out || !rowtotal_out) return fail(PMDI_E_ARG, "pmdi_psm_rowscore_device: null argument");
-    const int rc = psm_shared_args("pmdi_psm_rowscore_device", S, K, n, which, B, ld);
+    const int rc = pmdi_psm_shared_args("pmdi_psm_rowscore_device", S, K, n, which, true, B, ld);
     if (rc) return rc;
-    const unsigned __int128 D = (unsigned __int128)S * (unsigned)(which == K ? K : 1);
+    const unsigned __int128 D = psm_divisor(S, K, which);
     if (D * (unsigned __int128)(n - 1) >= ((unsigned __int128)1 << 62))       // own and rowtotal stay inside int64
         return fail(PMDI_E_ARG, "pmdi_psm_rowscore_device: S=%lld with n=%lld: D (n - 1) >= 2^62", (long long)S, (long long)n);
     HIP_TRY(hipSetDevice(device));
@@ -1018,18 +1024,15 @@ int pmdi_psm_refine_device(int32_t device, const int32_t *counts, int64_t S, int
                            int32_t *sweeps_out, void *stream)
 {
     if (!counts || !start || !labels_out || !moves_out || !sweeps_out) return fail(PMDI_E_ARG, "pmdi_psm_refine_device: null argument");
-    const int rc = psm_shared_args("pmdi_psm_refine_device", S, K, n, which, B, ld);
+    const int rc = pmdi_psm_shared_args("pmdi_psm_refine_device", S, K, n, which, true, B, ld);
     if (rc) return rc;
-    const unsigned __int128 D = (unsigned __int128)S * (unsigned)(which == K ? K : 1);
+    const unsigned __int128 D = psm_divisor(S, K, which);
     if (D > 2147483647u)                             // a w fits the uint32 work matrix and a gain fits int64 with room to spare
         return fail(PMDI_E_ARG, "pmdi_psm_refine_device: S=%lld: D > 2^31 - 1", (long long)S);
     if (max_sweeps < 1) return fail(PMDI_E_ARG, "pmdi_psm_refine_device: max_sweeps=%d < 1", max_sweeps);
     HIP_TRY(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
-    struct Scratch {
-        void *p = nullptr;
-        ~Scratch() { if (p) (void)hipFree(p); }
-    } work, out;
+    Scratch work, out;
     const size_t out_bytes = (size_t)B * 12 + 8;     // B moves, B sweeps, the flag
     HIP_TRY(hipMalloc(&work.p, (size_t)n * (size_t)n * 4));
     HIP_TRY(hipMalloc(&out.p, out_bytes));

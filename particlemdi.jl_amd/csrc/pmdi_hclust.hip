@@ -13,8 +13,10 @@
 #include <vector>
 
 #include "../../include/pmdi_hip.h"
+#include "pmdi_psm_device.h"
 
 int pmdi_set_error(int code, const char *fmt, ...);   // pmdi_api.cpp
+int pmdi_psm_shared_args(const char *who, int64_t S, int32_t K, int64_t n, int32_t which, bool cand, int64_t B, int64_t ld);   // pmdi_api.cpp
 
 namespace {
 
@@ -33,10 +35,10 @@ __global__ void pmdi_psm_distance_kernel(const int *__restrict__ counts, double 
     double d = 0.0;
     if (r != c) {
         if (which < K) {
-            d = 1.0 - (double)counts[((long long)which * n + r) * n + c] / S;
+            d = 1.0 - (double)psm_count(counts, which, n, r, c) / S;
         } else {
             double o = 0.0;
-            for (int k = 0; k < K; ++k) o += ((double)counts[((long long)k * n + r) * n + c] / S) / (double)K;
+            for (int k = 0; k < K; ++k) o += ((double)psm_count(counts, k, n, r, c) / S) / (double)K;
             d = 1.0 - o;
         }
     }
@@ -215,11 +217,8 @@ int pmdi_psm_distance_device(int32_t device, const int32_t *counts, int64_t S, i
                              double *dist_out, void *stream)
 {
     if (!counts || !dist_out) return pmdi_set_error(PMDI_E_ARG, "pmdi_psm_distance_device: null argument");
-    if (S < 1 || K < 1 || n < 1 || n > 65535)
-        return pmdi_set_error(PMDI_E_ARG, "pmdi_psm_distance_device: S=%lld K=%d n=%lld out of range (n <= 65535)", (long long)S, K, (long long)n);
-    if (which < 0 || which > K || (which == K && K == 1))
-        return pmdi_set_error(PMDI_E_ARG, "pmdi_psm_distance_device: which=%d, but there are %d matrices (the Overall one only for K > 1)",
-                              which, K + (K > 1));
+    const int rc = pmdi_psm_shared_args("pmdi_psm_distance_device", S, K, n, which, false, 0, 0);
+    if (rc) return rc;
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     hipLaunchKernelGGL(pmdi_psm_distance_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), 0, (hipStream_t)stream,

@@ -21,21 +21,12 @@
 #include <hip/hip_runtime.h>
 
 #include "pmdi_internal.h"
+#include "pmdi_psm_device.h"
 
 namespace {
 
 #define PSM_REFINE_G PMDI_REFINE_GMAX_I
 #define PSM_REFINE_THREADS 1024
-
-__device__ __forceinline__ void psm_refine_tile_pair(unsigned p, int &bi, int &bj)        // psm_score_tile_pair of pmdi_psm_score.hip
-{
-    int b = (int)((sqrtf(8.0f * (float)p + 1.0f) - 1.0f) * 0.5f);
-    while ((unsigned)b * (unsigned)(b + 1) / 2u > p) --b;
-    while ((unsigned)(b + 1) * (unsigned)(b + 2) / 2u <= p) ++b;
-    b = __builtin_amdgcn_readfirstlane(b);
-    bi = b;
-    bj = (int)(p - (unsigned)b * (unsigned)(b + 1) / 2u);
-}
 
 __global__ void __launch_bounds__(256) psm_refine_build_kernel(const int *__restrict__ counts, int K, long long n, int which,
                                                                unsigned n_tile_pairs, unsigned *__restrict__ W)
@@ -43,16 +34,16 @@ __global__ void __launch_bounds__(256) psm_refine_build_kernel(const int *__rest
     __shared__ unsigned t[64][65];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int k_lo = which < K ? which : 0, k_hi = which < K ? which + 1 : K;
+    int k_lo, k_hi;
+    psm_k_range(which, K, k_lo, k_hi);
     for (unsigned p = blockIdx.x; p < n_tile_pairs; p += gridDim.x) {
         int bi, bj;
-        psm_refine_tile_pair(p, bi, bj);
+        psm_tile_pair_uniform(p, bi, bj);
         const long long i0 = (long long)bi * 64, j0 = (long long)bj * 64;
         for (int rr = wave; rr < 64; rr += 4) {
             const long long i = i0 + rr, j = j0 + lane;
             unsigned w = 0;
-            if (i < n && j < i)
-                for (int k = k_lo; k < k_hi; ++k) w += (unsigned)counts[((size_t)k * n + i) * n + j];
+            if (i < n && j < i) w = psm_w<unsigned>(counts, k_lo, k_hi, n, i, j);
             t[rr][lane] = w;
             if (i < n && j <= i) W[(size_t)i * n + j] = w;                      // the lower half and the diagonal (0)
         }
@@ -191,8 +182,7 @@ hipError_t pmdi_launch_psm_refine(const int *counts, int K, long long n, int whi
                                   long long B, long long ld, int max_sweeps, int *labels, long long *moves, int *sweeps, int *flag,
                                   hipStream_t stream)
 {
-    const long long T = (n + 63) / 64;
-    const unsigned tile_pairs = (unsigned)(T * (T + 1) / 2);
+    const unsigned tile_pairs = psm_tile_pairs(n, 64);
     hipLaunchKernelGGL(psm_refine_build_kernel, dim3(tile_pairs < 8192u ? tile_pairs : 8192u), dim3(256), 0, stream, counts, K, n, which,
                        tile_pairs, W);
     hipError_t e = hipGetLastError();

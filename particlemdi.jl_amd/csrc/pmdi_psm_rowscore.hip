@@ -20,15 +20,9 @@
 #include <hip/hip_runtime.h>
 
 #include "pmdi_internal.h"
+#include "pmdi_psm_device.h"
 
 namespace {
-
-#define PSM_ROW_LDL 65        // ints per label row (as PSM_SCORE_LDL)
-
-template <typename WT>
-struct alignas(16) PsmRowW4 {
-    WT v[4];
-};
 
 // w rows are padded by 16 bytes: the 16-byte reads of four consecutive w stay aligned, and the turned-round staging of a
 // mirrored tile (a wave writes one COLUMN) is a 4-way bank conflict, not a 32-way one
@@ -36,7 +30,7 @@ template <typename WT>
 struct PsmRowShape {
     static constexpr int WS = 64 + 16 / (int)sizeof(WT);                   // 68 (32-bit) or 66 (64-bit) elements per row
     static constexpr int W_BYTES = 64 * WS * (int)sizeof(WT);              // 17 408 or 33 792
-    static constexpr int L_BYTES = 64 * PSM_ROW_LDL * 4;                   // 16 640
+    static constexpr int L_BYTES = 64 * PSM_LDL * 4;                   // 16 640
     static constexpr int BYTES = W_BYTES + L_BYTES;                        // >= 64 * 65 * 8 = 33 280: the output staging fits
 };
 
@@ -55,17 +49,19 @@ __global__ void __launch_bounds__(256) psm_rowscore_kernel(const int *__restrict
     constexpr int WS = PsmRowShape<WT>::WS;
     __shared__ __attribute__((aligned(16))) unsigned char smem[PsmRowShape<WT>::BYTES];
     WT(*wt)[WS] = (WT(*)[WS])smem;
-    int(*cl)[PSM_ROW_LDL] = (int(*)[PSM_ROW_LDL])(smem + PsmRowShape<WT>::W_BYTES);
+    int(*cl)[PSM_LDL] = (int(*)[PSM_LDL])(smem + PsmRowShape<WT>::W_BYTES);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const long long b0 = (long long)blockIdx.x * 64;
     const int bi = blockIdx.y;
     const int T = (int)((n + 63) / 64);
     const long long i0 = (long long)bi * 64;
-    const int k_lo = which < K ? which : 0, k_hi = which < K ? which + 1 : K;
+    int k_lo, k_hi;
+    psm_k_range(which, K, k_lo, k_hi);
     const int r0 = wave * 16;
 
     // the row labels, once: through the column-label buffer into registers
+    // (psm_stage_labels' loop, spelled out: through the function this one read costs the kernel two more VGPRs)
 #pragma unroll 4
     for (int e = 0; e < 16; ++e) {
         const int b = wave + 4 * e;
@@ -93,8 +89,7 @@ __global__ void __launch_bounds__(256) psm_rowscore_kernel(const int *__restrict
             for (int rr = wave; rr < 64; rr += 4) {
                 const long long i = i0 + rr, j = j0 + lane;
                 WT w = 0;
-                if (i < n)
-                    for (int k = k_lo; k < k_hi; ++k) w += (WT)(unsigned)counts[((size_t)k * n + i) * n + j];
+                if (i < n) w = psm_w<WT>(counts, k_lo, k_hi, n, i, j);
                 wt[rr][lane] = w;
             }
         } else if (bj > bi) {                                      // the mirror image: stored row j, columns i0..
@@ -102,29 +97,19 @@ __global__ void __launch_bounds__(256) psm_rowscore_kernel(const int *__restrict
             for (int rr = wave; rr < 64; rr += 4) {
                 const long long j = j0 + rr, i = i0 + lane;
                 WT w = 0;
-                if (j < n && i < n)
-                    for (int k = k_lo; k < k_hi; ++k) w += (WT)(unsigned)counts[((size_t)k * n + j) * n + i];
+                if (j < n && i < n) w = psm_w<WT>(counts, k_lo, k_hi, n, j, i);
                 wt[lane][rr] = w;
             }
         } else {                                                   // the diagonal tile: both halves from below the diagonal
             for (int rr = wave; rr < 64; rr += 4) {
                 const long long i = i0 + rr, j = j0 + lane;
                 WT w = 0;
-                if (i < n && j < n && i != j) {
-                    const long long a = i > j ? i : j, b = i > j ? j : i;
-                    for (int k = k_lo; k < k_hi; ++k) w += (WT)(unsigned)counts[((size_t)k * n + a) * n + b];
-                }
+                if (i < n && j < n && i != j) w = psm_w<WT>(counts, k_lo, k_hi, n, i > j ? i : j, i > j ? j : i);
                 wt[rr][lane] = w;
             }
         }
         // the column labels: a wave reads 64 consecutive labels of one candidate
-#pragma unroll 4
-        for (int e = 0; e < 16; ++e) {
-            const int b = wave + 4 * e;
-            int cv = 0;
-            if (b0 + b < B && j0 + lane < n) cv = cand[(size_t)(b0 + b) * ld + j0 + lane];
-            cl[lane][b] = cv;
-        }
+        psm_stage_labels<false>(cand, B, ld, b0, n, wave, lane, cl, j0);
         __syncthreads();
         if (want_total && tid < 64) {                              // one row per thread, columns rotated: no bank conflict
             unsigned long long t = 0;
@@ -144,17 +129,7 @@ __global__ void __launch_bounds__(256) psm_rowscore_kernel(const int *__restrict
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj) cj[jj] = cl[j + jj][lane];
 #pragma unroll
-                    for (int r = 0; r < 8; ++r) {
-                        PsmRowW4<WT> w4 = *(const PsmRowW4<WT> *)&wt[r0 + rb * 8 + r][j];
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) asm volatile("" : "+v"(w4.v[jj]));     // one wide LDS read, not four guarded ones
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) {
-                            const bool eq = ri[rb * 8 + r] == cj[jj];
-                            a[r] += eq ? w4.v[jj] : (WT)0;
-                            cnt[rb * 8 + r] += eq ? 1 : 0;
-                        }
-                    }
+                    for (int r = 0; r < 8; ++r) psm_cmp_add4(&wt[r0 + rb * 8 + r][j], ri[rb * 8 + r], cj, a[r], cnt[rb * 8 + r]);
                 }
 #pragma unroll
                 for (int r = 0; r < 8; ++r) own[rb * 8 + r] += a[r];
@@ -176,7 +151,7 @@ __global__ void __launch_bounds__(256) psm_rowscore_kernel(const int *__restrict
     if (want_total && tid < 64 && i0 + tid < n) rowtotal_out[i0 + tid] = rtot;
 
     // out through LDS, [candidate][row]: a wave then writes 64 consecutive rows of one candidate
-    unsigned long long(*ob)[PSM_ROW_LDL] = (unsigned long long(*)[PSM_ROW_LDL])smem;
+    unsigned long long(*ob)[PSM_LDL] = (unsigned long long(*)[PSM_LDL])smem;
 #pragma unroll
     for (int r = 0; r < 16; ++r) ob[lane][r0 + r] = own[r];
     __syncthreads();
@@ -185,7 +160,7 @@ __global__ void __launch_bounds__(256) psm_rowscore_kernel(const int *__restrict
         if (b0 + b < B && i0 + lane < n) own_out[(size_t)(b0 + b) * n + i0 + lane] = ob[b][lane];
     }
     __syncthreads();
-    int(*sb)[PSM_ROW_LDL] = (int(*)[PSM_ROW_LDL])smem;
+    int(*sb)[PSM_LDL] = (int(*)[PSM_LDL])smem;
 #pragma unroll
     for (int r = 0; r < 16; ++r) sb[lane][r0 + r] = cnt[r];
     __syncthreads();

@@ -20,27 +20,9 @@
 #include <hip/hip_runtime.h>
 
 #include "pmdi_internal.h"
+#include "pmdi_psm_device.h"
 
 namespace {
-
-// psm_acc_tile_pair of pmdi_psm_acc.hip: tile pair p = bi (bi + 1) / 2 + bj, 0 <= bj <= bi; p < 2^20 (n <= 65535), where
-// the float square root is within one of the answer and the two loops make it exact.
-__device__ __forceinline__ void psm_score_tile_pair(unsigned p, int &bi, int &bj)
-{
-    int b = (int)((sqrtf(8.0f * (float)p + 1.0f) - 1.0f) * 0.5f);
-    while ((unsigned)b * (unsigned)(b + 1) / 2u > p) --b;
-    while ((unsigned)(b + 1) * (unsigned)(b + 2) / 2u <= p) ++b;
-    b = __builtin_amdgcn_readfirstlane(b);               // p is workgroup-uniform; the float detour left b in a vector register
-    bi = b;
-    bj = (int)(p - (unsigned)b * (unsigned)(b + 1) / 2u);
-}
-
-#define PSM_SCORE_LDL 65        // ints per label row
-
-template <typename WT>
-struct alignas(16) PsmScoreW4 {
-    WT v[4];
-};
 
 // WT = unsigned: the caller guarantees D = S (or S K for the Overall matrix) <= 2^22, so that
 //   * a staged w (at most D when the counts are what they claim to be) fits 32 bits, and
@@ -56,42 +38,31 @@ __global__ void __launch_bounds__(256) psm_score_kernel(const int *__restrict__ 
                                                         unsigned long long *__restrict__ pairs_out, unsigned long long *__restrict__ total_out)
 {
     __shared__ __attribute__((aligned(16))) WT wt[64][64];
-    __shared__ int rl[64][PSM_SCORE_LDL];
-    __shared__ int cl[64][PSM_SCORE_LDL];
+    __shared__ int rl[64][PSM_LDL];
+    __shared__ int cl[64][PSM_LDL];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave-uniform, and known to be: rows and branches go scalar
     const long long b0 = (long long)blockIdx.x * 64;
-    const int k_lo = which < K ? which : 0, k_hi = which < K ? which + 1 : K;
+    int k_lo, k_hi;
+    psm_k_range(which, K, k_lo, k_hi);
     unsigned long long agree = 0, tot = 0;
     unsigned npair = 0;
 
     for (unsigned p = blockIdx.y; p < n_tile_pairs; p += gridDim.y) {
         int bi, bj;
-        psm_score_tile_pair(p, bi, bj);
+        psm_tile_pair_uniform(p, bi, bj);
         const long long i0 = (long long)bi * 64, j0 = (long long)bj * 64;
         // the w tile: a wave reads 64 consecutive ints of one row
 #pragma unroll 4
         for (int rr = wave; rr < 64; rr += 4) {
             const long long i = i0 + rr, j = j0 + lane;
             WT w = 0;
-            if (i < n && j < i)
-                for (int k = k_lo; k < k_hi; ++k) w += (WT)(unsigned)counts[((size_t)k * n + i) * n + j];
+            if (i < n && j < i) w = psm_w<WT>(counts, k_lo, k_hi, n, i, j);
             wt[rr][lane] = w;
             tot += w;
         }
         // the labels: a wave reads 64 consecutive labels of one candidate, twice (the tile's rows, the tile's columns)
-#pragma unroll 4
-        for (int e = 0; e < 16; ++e) {
-            const int b = wave + 4 * e;
-            int rv = 0, cv = 0;
-            if (b0 + b < B) {
-                const int *row = cand + (size_t)(b0 + b) * ld;
-                if (i0 + lane < n) rv = row[i0 + lane];
-                if (j0 + lane < n) cv = row[j0 + lane];
-            }
-            rl[lane][b] = rv;
-            cl[lane][b] = cv;
-        }
+        psm_stage_labels<true>(cand, B, ld, b0, n, wave, lane, rl, i0, cl, j0);
         __syncthreads();
 #pragma unroll 1
         for (int rb = 0; rb < 2; ++rb) {
@@ -109,17 +80,7 @@ __global__ void __launch_bounds__(256) psm_score_kernel(const int *__restrict__ 
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj) cj[jj] = cl[j + jj][lane];
 #pragma unroll
-                    for (int r = 0; r < 8; ++r) {
-                        PsmScoreW4<WT> w4 = *(const PsmScoreW4<WT> *)&wt[r0 + r][j];
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) asm volatile("" : "+v"(w4.v[jj]));     // one wide LDS read, not four guarded ones
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) {
-                            const bool eq = ri[r] == cj[jj];
-                            a += eq ? w4.v[jj] : (WT)0;
-                            npair += eq ? 1u : 0u;
-                        }
-                    }
+                    for (int r = 0; r < 8; ++r) psm_cmp_add4(&wt[r0 + r][j], ri[r], cj, a, npair);
                 }
                 agree += a;
             } else {                                       // a diagonal tile, or the last rows of the matrix
@@ -165,8 +126,7 @@ __global__ void __launch_bounds__(256) psm_score_kernel(const int *__restrict__ 
 hipError_t pmdi_launch_psm_score(const int *counts, int K, long long n, int which, int wide, const int *cand, long long B, long long ld,
                                  unsigned long long *out, hipStream_t stream)
 {
-    const long long T = (n + 63) / 64;
-    const unsigned tile_pairs = (unsigned)(T * (T + 1) / 2);
+    const unsigned tile_pairs = psm_tile_pairs(n, 64);
     const long long slab = 1LL << 24;                // candidates per launch: 2^18 chunks in grid.x
     for (long long at = 0; at < B; at += slab) {
         const long long nb = B - at < slab ? B - at : slab;

@@ -399,6 +399,11 @@ def _which_matrix(psm, orderby, who):
     return which
 
 
+def _divisor(psm, K, which):
+    """D of the scored matrix: S, or S K for "Overall" (which == K)."""
+    return psm.S * (K if which == K else 1)
+
+
 def score_allocations(psm, candidates, orderby=0, ld=None):
     """Candidate clusterings scored against a PsmCounts on the MI355X (pmdi_psm_score_device): the counts never leave the
     device and no n x n temporary is made.  candidates: B clusterings of the n observations, labels of any value -- a CUDA
@@ -409,39 +414,17 @@ def score_allocations(psm, candidates, orderby=0, ld=None):
     import ctypes as C
     import torch
     from ._lib import _check, _ptr, lib
-    if not isinstance(psm, PsmCounts):
-        raise ValueError("score_allocations needs a PsmCounts (the device-resident counts)")
-    cnt = psm.counts
-    if not cnt.is_cuda or cnt.dtype != torch.int32 or cnt.dim() != 3 or cnt.shape[1] != cnt.shape[2]:
-        raise ValueError("score_allocations needs int32 CUDA counts (K, n, n)")
+    cnt = _checked_counts(psm, "score_allocations")
     which = _which_matrix(psm, orderby, "score_allocations")
-    cnt = cnt.contiguous()
     K, n, _ = cnt.shape
-    if not (isinstance(candidates, torch.Tensor) and candidates.is_cuda):
-        arr = np.asarray(candidates.cpu() if isinstance(candidates, torch.Tensor) else candidates)
-        if arr.ndim != 2 or not np.issubdtype(arr.dtype, np.integer):
-            raise ValueError("score_allocations: candidates must be an integer array (B, n)")
-        if arr.size and (arr.min() < -2**31 or arr.max() >= 2**31):
-            raise ValueError("score_allocations: labels must fit int32")
-        candidates = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.int32)).to(cnt.device)
-    cand = candidates
-    if cand.dim() != 2 or cand.shape[1] != n or cand.shape[0] < 1:
-        raise ValueError(f"score_allocations: candidates {tuple(cand.shape)}, the counts hold n={n}")
-    if cand.device != cnt.device:
-        raise ValueError("score_allocations: candidates and counts are on different devices")
-    if cand.dtype != torch.int32:
-        cand = cand.to(torch.int32)
+    cand, ld = _device_candidates(cnt, candidates, ld, "score_allocations")
     B = cand.shape[0]
-    if ld is None:
-        if (n > 1 and cand.stride(1) != 1) or (B > 1 and cand.stride(0) < n):
-            cand = cand.contiguous()
-        ld = cand.stride(0) if B > 1 else n
     agree, pairs, total = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64), np.zeros(1, dtype=np.int64)
     st = torch.cuda.current_stream(cnt.device)
     _check(lib().pmdi_psm_score_device(cnt.device.index or 0, C.c_void_p(cnt.data_ptr()), int(psm.S), K, n, which,
-                                       C.c_void_p(cand.data_ptr()), B, int(ld), _ptr(agree), _ptr(pairs), _ptr(total),
+                                       C.c_void_p(cand.data_ptr()), B, ld, _ptr(agree), _ptr(pairs), _ptr(total),
                                        C.c_void_p(st.cuda_stream)))
-    return AllocationScores(agree, pairs, total[0], psm.S * (K if which == K else 1), n)
+    return AllocationScores(agree, pairs, total[0], _divisor(psm, K, which), n)
 
 
 def select_consensus_allocations(psm, k=range(2, 21), linkage=("ward",), orderby=0, criterion="pear"):
@@ -567,7 +550,7 @@ def row_scores(psm, candidates, orderby=0, ld=None, max_bytes=1 << 30):
                                               C.c_void_p(d_size.data_ptr()), C.c_void_p(d_tot.data_ptr()), C.c_void_p(st.cuda_stream)))
         own[at:at + nb] = d_own[:nb].cpu().numpy()
         size[at:at + nb] = d_size[:nb].cpu().numpy()
-    return AllocationRowScores(own, size, d_tot.cpu().numpy(), psm.S * (K if which == K else 1), n)
+    return AllocationRowScores(own, size, d_tot.cpu().numpy(), _divisor(psm, K, which), n)
 
 
 def _first_appearance(rows, base):

@@ -248,3 +248,27 @@ def test_pooled_run_at_a_users_size(pkg):
     assert H.same_partition(fcluster(Z, 3, "maxclust"), z), "scipy's ward does not recover the planted partition: the input is too hard"
     got = psm.get_consensus_allocations(out, k=3)
     assert H.same_partition(got, z)
+
+
+def test_byte_compares_at_the_top_of_the_byte_range(pkg):
+    """Both wrappers of the shared byte-compare body (psm_count_kernel: counts = tile; psm_acc_kernel: counts += tile) at the
+    byte values where signedness or the padding bytes (255 for rows, 254 for columns) could bite: labels from {0, 127, 128,
+    254, 255}, n_labels = 0, S = 70 (crosses one 64-sample staging round), n = 130 (three 64-wide tile rows, the last with two
+    live rows).  The yardstick is a numpy count; exact integer equality."""
+    import torch
+    from particlemdi_jl_amd import psm
+    S, K, n = 70, 2, 130
+    rng = np.random.default_rng(5)
+    smp = np.array([0, 127, 128, 254, 255], dtype=np.uint8)[rng.integers(0, 5, size=(S, K, n))]
+    want = (smp[:, :, :, None] == smp[:, :, None, :]).sum(axis=0).astype(np.int32)          # (K, n, n)
+    dev = torch.from_numpy(smp).cuda()
+    got = psm.psm_counts_device(dev, 3, n).cpu().numpy()
+    assert got.dtype == np.int32 and got.shape == (K, n - 3, n)
+    assert np.array_equal(got, want[:, 3:, :])
+    acc = psm.PsmAccumulator(K, n, 0)
+    acc.add_samples(dev[:41])
+    acc.add_samples(dev[41:])
+    out = acc.counts()
+    assert out.S == S
+    _assert_full_counts(out.counts.cpu().numpy(), want, S)
+    acc.close()
