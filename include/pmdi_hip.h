@@ -500,6 +500,52 @@ int pmdi_summary_get(pmdi_summary *a, int64_t *nclust_hist, int64_t *nclust_sum,
 int pmdi_gibbs_run2(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ,
                     void *stream);
 
+/* ---- streaming fusion accumulator: which observations the datasets cluster alike, and how those cluster ----
+ * The third accumulator beside pmdi_psm_acc and pmdi_summary.  Datasets k and l are coupled through [s_ik == s_il] log(1 + Phi_kl)
+ * and the labels are aligned every iteration, so equal labels in two datasets mean the same cluster.  With samples[t][k][i] the
+ * label of observation i in dataset k in retained sample t, a group g = a set of two or more datasets, m0 its lowest member:
+ *   f_g(t, i)       = 1 iff samples[t][m][i] is the same for every member m of g ("i is fused across g in sample t")
+ *   fused[g][i]     = sum_t f_g(t, i)
+ *   counts[g][i][j] = sum_t f_g(t, i) f_g(t, j) [samples[t][m0][i] == samples[t][m0][j]]
+ * counts[g] is symmetric and its diagonal is fused[g], NOT S -- the one difference from the per-dataset counts; off the diagonal
+ * it is read like them (divisor S) by everything that takes a device int32 [K][n][n] with K = 1.  All arithmetic is integer:
+ * every result is exact.  The rules of pmdi_psm_acc hold: one device, not thread-safe, all calls of one accumulator on ONE
+ * stream, asynchronous except create / destroy.
+ *
+ * create: 2 <= K <= PMDI_KMAX, 1 <= n <= 65535, 0 <= n_labels <= 255 (as in pmdi_psm_acc_create: 1..64 selects the matrix-core
+ *   kernels); group_masks = n_groups bytes, bit k of a byte = dataset k is a member: n_groups >= 1, every mask with two or more
+ *   bits, none at or above K, no mask twice; or NULL (n_groups ignored): the K (K - 1) / 2 pairs in the order of Phi, (0,1),
+ *   (0,2), ..., (K-2,K-1).  All checked before the device is touched (PMDI_E_ARG); no usable device is PMDI_E_DEVICE, a failed
+ *   allocation PMDI_E_MEMORY.  with_matrix = 0 keeps fused only: G n int32 instead of G n n.
+ * add_samples: samples = device uint8 [S][K][n].  With matrices only the tiles with block-row >= block-column are computed and
+ *   fused is their diagonal; without, fused is summed directly.  Nothing of size S G n is written.
+ * add_gibbs: as pmdi_psm_acc_add_gibbs, with the same conditions on g (K, n, N against n_labels, device).
+ * merge: S += S and, with matrices, counts += counts (device int32 [G][n][n] of the same groups, only i >= j read; fused is
+ *   not read and may be NULL); without, fused += fused (device int32 [G][n]) and counts must be NULL.
+ * S is an int32 count: an add or merge that would take S past INT32_MAX is PMDI_E_ARG and adds nothing.
+ * groups: the number of groups and, when masks != NULL, their masks in order.
+ * counts: with matrices, mirrors the lower triangles into the upper ones and gathers the diagonals into fused if anything was
+ *   added since the last call.  *fused = device int32 [G][n], *counts = device int32 [G][n][n] or NULL without matrices (counts
+ *   itself may be NULL).  The pointers stay valid (and keep changing with later adds) until destroy.
+ * reset: everything zero, S = 0. */
+typedef struct pmdi_fusion pmdi_fusion;
+int pmdi_fusion_create(int32_t device, int32_t K, int64_t n, int32_t n_labels, int32_t n_groups, const uint8_t *group_masks,
+                       int32_t with_matrix, pmdi_fusion **out);
+int pmdi_fusion_destroy(pmdi_fusion *a);
+int pmdi_fusion_reset(pmdi_fusion *a, void *stream);
+int pmdi_fusion_add_samples(pmdi_fusion *a, const uint8_t *samples, int64_t S, void *stream);
+int pmdi_fusion_add_gibbs(pmdi_fusion *a, pmdi_gibbs *g, void *stream);
+int pmdi_fusion_merge(pmdi_fusion *a, const int32_t *fused, const int32_t *counts, int64_t S, void *stream);
+int64_t pmdi_fusion_samples(const pmdi_fusion *a);
+int pmdi_fusion_groups(const pmdi_fusion *a, int32_t *n_groups, uint8_t *masks);
+int pmdi_fusion_counts(pmdi_fusion *a, const int32_t **fused, const int32_t **counts, int64_t *S, void *stream);
+
+/* pmdi_gibbs_run2 with the third accumulator: after every retained local iteration acc, then summ, then fus get their add; any
+ * may be NULL, and pmdi_gibbs_run2(g, ..., acc, summ, stream) is pmdi_gibbs_run3(g, ..., acc, summ, NULL, stream).  All are
+ * checked against g and against their limits before the first iteration runs. */
+int pmdi_gibbs_run3(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ,
+                    pmdi_fusion *fus, void *stream);
+
 /* Device pointers of the resident state (zero-copy consumers; layouts of pmdi_sweep_device). */
 typedef struct {
     double *M, *gamma, *gamma0, *Phi, *vZ, *Pi, *log1p_phi, *feature_prob, *logweight;

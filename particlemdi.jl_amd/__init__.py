@@ -13,6 +13,7 @@ from .psm import (  # noqa: F401,E402
     AllocationRowScores, AllocationScores, PsmAccumulator, PsmCounts, best_sampled_allocation, refine_allocations,
     retained_iterations, row_scores, score_allocations, search_consensus_allocation, select_consensus_allocations,
 )
+from .fusion import FusionAccumulator, FusionCounts, fused_consensus_allocations  # noqa: F401,E402
 from .summary import (  # noqa: F401,E402
     PosteriorSummary, SummaryAccumulator, get_feature_select_probs, get_nclust, get_phi,
 )

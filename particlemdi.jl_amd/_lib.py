@@ -12,7 +12,7 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("PMDI_LIB_PATH") or os.path.join(_PKG, "libpmdi_hip.so")   # override: A/B builds only
-_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_summary.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_api.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
+_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_fusion.hip", "pmdi_summary.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_api.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
 _HEADERS = [os.path.join(_PKG, "csrc", "pmdi_internal.h"), os.path.join(_PKG, "csrc", "pmdi_device.h"),
             os.path.join(_PKG, "csrc", "pmdi_sweep_body.h"), os.path.join(_PKG, "csrc", "pmdi_sweep2_body.h"),
             os.path.join(_PKG, "csrc", "pmdi_arith.h"), os.path.join(_PKG, "csrc", "pmdi_psm_device.h"),
@@ -44,6 +44,8 @@ EXPORTS = [
     "pmdi_summary_create", "pmdi_summary_destroy", "pmdi_summary_reset", "pmdi_summary_add_gibbs", "pmdi_summary_add_arrays",
     "pmdi_summary_samples", "pmdi_summary_get", "pmdi_gibbs_run2",
     "pmdi_psm_score_device", "pmdi_psm_rowscore_device", "pmdi_psm_refine_device",
+    "pmdi_fusion_create", "pmdi_fusion_destroy", "pmdi_fusion_reset", "pmdi_fusion_add_samples", "pmdi_fusion_add_gibbs",
+    "pmdi_fusion_merge", "pmdi_fusion_samples", "pmdi_fusion_groups", "pmdi_fusion_counts", "pmdi_gibbs_run3",
 ]
 
 
@@ -229,6 +231,25 @@ def lib():
     L.pmdi_gibbs_run.argtypes = [vp, i64, i64, i64, vp, vp]
     L.pmdi_gibbs_run2.restype = C.c_int
     L.pmdi_gibbs_run2.argtypes = [vp, i64, i64, i64, vp, vp, vp]
+    L.pmdi_gibbs_run3.restype = C.c_int
+    L.pmdi_gibbs_run3.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp]
+    L.pmdi_fusion_create.restype = C.c_int
+    L.pmdi_fusion_create.argtypes = [i32, i32, i64, i32, i32, vp, i32, C.POINTER(vp)]
+    L.pmdi_fusion_destroy.argtypes = [vp]
+    L.pmdi_fusion_reset.restype = C.c_int
+    L.pmdi_fusion_reset.argtypes = [vp, vp]
+    L.pmdi_fusion_add_samples.restype = C.c_int
+    L.pmdi_fusion_add_samples.argtypes = [vp, vp, i64, vp]
+    L.pmdi_fusion_add_gibbs.restype = C.c_int
+    L.pmdi_fusion_add_gibbs.argtypes = [vp, vp, vp]
+    L.pmdi_fusion_merge.restype = C.c_int
+    L.pmdi_fusion_merge.argtypes = [vp, vp, vp, i64, vp]
+    L.pmdi_fusion_samples.restype = i64
+    L.pmdi_fusion_samples.argtypes = [vp]
+    L.pmdi_fusion_groups.restype = C.c_int
+    L.pmdi_fusion_groups.argtypes = [vp, C.POINTER(i32), vp]
+    L.pmdi_fusion_counts.restype = C.c_int
+    L.pmdi_fusion_counts.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp]
     L.pmdi_summary_create.restype = C.c_int
     L.pmdi_summary_create.argtypes = [i32, i32, i32, i32, i64, i64, i64, C.POINTER(vp)]
     L.pmdi_summary_destroy.argtypes = [vp]
@@ -607,12 +628,14 @@ class Gibbs:
         _check(lib().pmdi_gibbs_iterate(self.h, int(n_iter), C.c_void_p(samples_ptr) if samples_ptr else None,
                                         C.c_void_p(stream) if stream else None))
 
-    def run(self, n_iter, burnin=0, thin=1, acc=None, stream=None, summary=None):
-        """pmdi_gibbs_run2: n_iter iterations; after local iteration t = 1..n_iter the state of every chain is added to `acc` (a
-        psm.PsmAccumulator: the allocations) and to `summary` (a summary.SummaryAccumulator: M, Phi, cluster counts, feature
-        flags) iff t > burnin and (t - burnin - 1) % thin == 0 (psm.retained_iterations).  Either may be None."""
-        _check(lib().pmdi_gibbs_run2(self.h, int(n_iter), int(burnin), int(thin), acc.h if acc is not None else None,
-                                     summary.h if summary is not None else None, C.c_void_p(stream) if stream else None))
+    def run(self, n_iter, burnin=0, thin=1, acc=None, stream=None, summary=None, fusion=None):
+        """pmdi_gibbs_run3: n_iter iterations; after local iteration t = 1..n_iter the state of every chain is added to `acc` (a
+        psm.PsmAccumulator: the allocations), to `summary` (a summary.SummaryAccumulator: M, Phi, cluster counts, feature
+        flags) and to `fusion` (a fusion.FusionAccumulator: which observations the datasets cluster alike) iff t > burnin and
+        (t - burnin - 1) % thin == 0 (psm.retained_iterations).  Any may be None."""
+        _check(lib().pmdi_gibbs_run3(self.h, int(n_iter), int(burnin), int(thin), acc.h if acc is not None else None,
+                                     summary.h if summary is not None else None, fusion.h if fusion is not None else None,
+                                     C.c_void_p(stream) if stream else None))
 
     def pack_samples(self, out_ptr, stream=None):
         _check(lib().pmdi_gibbs_pack_samples(self.h, C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))

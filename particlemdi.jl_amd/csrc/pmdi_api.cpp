@@ -248,6 +248,23 @@ struct pmdi_summary {
     int64_t T = 0;                       // adds so far
 };
 
+// Streaming fusion accumulator (pmdi_fusion_* entry points)
+struct pmdi_fusion {
+    int device = 0, K = 0, n_labels = 0, G = 0;
+    long long n = 0;
+    bool with_matrix = false;
+    unsigned char masks[256] = {};       // [G] bit sets of datasets (at most 247 sets of two or more of 8)
+    unsigned char order[256] = {};       // [G] the groups sorted by class: 2 members, 3..4, 5..8 (the counting kernels' builds)
+    int n_class[3] = {};                 // groups per class
+    unsigned char *d_masks = nullptr;    // masks, then order, on the device: 2 x 256 bytes
+    int *counts = nullptr;               // [G][n][n], or null without matrices; the strict upper triangle is current only while !dirty
+    int *fused = nullptr;                // [G][n]; with matrices: the diagonals, current only while !dirty
+    unsigned char *pack = nullptr;       // [n_chains][K][n] label bytes of pmdi_fusion_add_gibbs, allocated at first use
+    size_t pack_bytes = 0;
+    int64_t S = 0;                       // samples behind the counts
+    bool dirty = false;                  // (with matrices) something was added since the last mirror
+};
+
 namespace {
 
 int dev_alloc(pmdi_handle *h, void **p, size_t bytes)
@@ -1167,6 +1184,173 @@ int pmdi_psm_acc_counts(pmdi_psm_acc *a, const int32_t **counts, int64_t *S, voi
     return PMDI_OK;
 }
 
+int pmdi_fusion_destroy(pmdi_fusion *a)
+{
+    if (!a) return PMDI_OK;
+    (void)hipSetDevice(a->device);
+    (void)hipDeviceSynchronize();
+    if (a->counts) (void)hipFree(a->counts);
+    if (a->fused) (void)hipFree(a->fused);
+    if (a->d_masks) (void)hipFree(a->d_masks);
+    if (a->pack) (void)hipFree(a->pack);
+    delete a;
+    return PMDI_OK;
+}
+
+int pmdi_fusion_create(int32_t device, int32_t K, int64_t n, int32_t n_labels, int32_t n_groups, const uint8_t *group_masks,
+                       int32_t with_matrix, pmdi_fusion **out)
+{
+    if (!out) return fail(PMDI_E_ARG, "null argument");
+    *out = nullptr;
+    if (K < 2 || K > PMDI_KMAX_I) return fail(PMDI_E_ARG, "K=%d outside 2..%d (a group is two or more datasets)", K, PMDI_KMAX_I);
+    if (n < 1 || n > 65535) return fail(PMDI_E_ARG, "n=%lld outside 1..65535", (long long)n);
+    if (n_labels < 0 || n_labels > 255) return fail(PMDI_E_ARG, "n_labels=%d outside 0..255", n_labels);
+    unsigned char masks[256] = {};
+    int G = 0;
+    if (group_masks) {
+        if (n_groups < 1 || n_groups > 247) return fail(PMDI_E_ARG, "n_groups=%d outside 1..247", n_groups);
+        bool seen[256] = {};
+        for (int g = 0; g < n_groups; ++g) {
+            const unsigned m = group_masks[g];
+            if (__builtin_popcount(m) < 2) return fail(PMDI_E_ARG, "group %d (mask 0x%02x) has fewer than two datasets", g, m);
+            if (m >> K) return fail(PMDI_E_ARG, "group %d (mask 0x%02x) names a dataset >= K=%d", g, m, K);
+            if (seen[m]) return fail(PMDI_E_ARG, "group %d (mask 0x%02x) is given twice", g, m);
+            seen[m] = true;
+            masks[G++] = (unsigned char)m;
+        }
+    } else {                                  // all pairs in the order of Phi: (0,1), (0,2), ..., (K-2,K-1)
+        for (int k1 = 0; k1 < K - 1; ++k1)
+            for (int k2 = k1 + 1; k2 < K; ++k2) masks[G++] = (unsigned char)((1u << k1) | (1u << k2));
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(PMDI_E_DEVICE, "no HIP device visible (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(PMDI_E_DEVICE, "device %d not in 0..%d", device, ndev - 1);
+    HIP_TRY(hipSetDevice(device));
+    pmdi_fusion *a = new (std::nothrow) pmdi_fusion();
+    if (!a) return fail(PMDI_E_MEMORY, "out of host memory");
+    a->device = device; a->K = K; a->n = n; a->n_labels = n_labels; a->G = G; a->with_matrix = with_matrix != 0;
+    memcpy(a->masks, masks, sizeof(masks));
+    for (int c = 0, at = 0; c < 3; ++c)
+        for (int g = 0; g < G; ++g) {
+            const int members = __builtin_popcount(masks[g]);
+            if ((members > 2) + (members > 4) == c) { a->order[at++] = (unsigned char)g; ++a->n_class[c]; }
+        }
+    const size_t cbytes = a->with_matrix ? (size_t)G * n * n * 4 : 0, fbytes = (size_t)G * n * 4;
+    hipError_t e = hipSuccess;
+    size_t want = cbytes;
+    if (cbytes) e = hipMalloc((void **)&a->counts, cbytes);
+    if (e != hipSuccess) a->counts = nullptr;
+    if (e == hipSuccess) { want = fbytes; e = hipMalloc((void **)&a->fused, fbytes); if (e != hipSuccess) a->fused = nullptr; }
+    if (e == hipSuccess) { want = 512; e = hipMalloc((void **)&a->d_masks, 512); if (e != hipSuccess) a->d_masks = nullptr; }
+    if (e != hipSuccess) { pmdi_fusion_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", want, hipGetErrorString(e)); }
+    if ((cbytes && hipMemset(a->counts, 0, cbytes) != hipSuccess) || hipMemset(a->fused, 0, fbytes) != hipSuccess ||
+        hipMemcpy(a->d_masks, a->masks, 256, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(a->d_masks + 256, a->order, 256, hipMemcpyHostToDevice) != hipSuccess) {
+        pmdi_fusion_destroy(a);
+        return fail(PMDI_E_DEVICE, "hipMemset / hipMemcpy failed");
+    }
+    *out = a;
+    return PMDI_OK;
+}
+
+int pmdi_fusion_reset(pmdi_fusion *a, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    if (a->counts) HIP_TRY(hipMemsetAsync(a->counts, 0, (size_t)a->G * a->n * a->n * 4, (hipStream_t)stream));
+    HIP_TRY(hipMemsetAsync(a->fused, 0, (size_t)a->G * a->n * 4, (hipStream_t)stream));
+    a->S = 0; a->dirty = false;
+    return PMDI_OK;
+}
+
+int pmdi_fusion_add_samples(pmdi_fusion *a, const uint8_t *samples, int64_t S, void *stream)
+{
+    if (!a || (!samples && S != 0)) return fail(PMDI_E_ARG, "null argument");
+    if (S < 0) return fail(PMDI_E_ARG, "S=%lld < 0", (long long)S);
+    if (S > 2147483647LL - a->S) return fail(PMDI_E_ARG, "%lld + %lld samples overflow the int32 counts", (long long)a->S, (long long)S);
+    if (S == 0) return PMDI_OK;
+    HIP_TRY(hipSetDevice(a->device));
+    hipError_t e = a->with_matrix ? pmdi_launch_fusion_add(samples, S, a->K, a->n, a->n_labels, a->d_masks, a->d_masks + 256, a->n_class, a->counts, (hipStream_t)stream)
+                                  : pmdi_launch_fusion_obs(samples, S, a->K, a->n, a->d_masks, a->G, a->fused, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "fusion-accumulate launch: %s", hipGetErrorString(e));
+    a->S += S; a->dirty = a->with_matrix;
+    return PMDI_OK;
+}
+
+// what pmdi_fusion_add_gibbs checks before it touches anything (pmdi_gibbs_run3 asks once, before its first iteration)
+static int fusion_accepts(const pmdi_fusion *a, const pmdi_gibbs *g, int64_t n_adds)
+{
+    const pmdi_config &c = g->h->cfg;
+    if (c.K != a->K || c.n != a->n)
+        return fail(PMDI_E_ARG, "the fusion accumulator holds K=%d n=%lld, the chains K=%d n=%lld", a->K, a->n, c.K, (long long)c.n);
+    if (a->n_labels != 0 && c.N > a->n_labels) return fail(PMDI_E_ARG, "the chains use N=%d labels, the fusion accumulator n_labels=%d", c.N, a->n_labels);
+    if (c.device != a->device) return fail(PMDI_E_ARG, "the chains live on device %d, the fusion accumulator on device %d", c.device, a->device);
+    if (n_adds > (2147483647LL - a->S) / c.n_chains)
+        return fail(PMDI_E_ARG, "%lld + %lld x %d samples overflow the int32 counts", (long long)a->S, (long long)n_adds, c.n_chains);
+    return PMDI_OK;
+}
+
+int pmdi_fusion_add_gibbs(pmdi_fusion *a, pmdi_gibbs *g, void *stream)
+{
+    if (!a || !g) return fail(PMDI_E_ARG, "null argument");
+    const int rc = fusion_accepts(a, g, 1);
+    if (rc) return rc;
+    const pmdi_config &c = g->h->cfg;
+    const size_t per = (size_t)c.n_chains * c.K * c.n;
+    HIP_TRY(hipSetDevice(a->device));
+    if (per > a->pack_bytes) {            // (first use, or a handle with more chains than the last one: the old buffer may still be read)
+        if (a->pack) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(a->pack); a->pack = nullptr; a->pack_bytes = 0; }
+        hipError_t e = hipMalloc((void **)&a->pack, per);
+        if (e != hipSuccess) { a->pack = nullptr; return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", per, hipGetErrorString(e)); }
+        a->pack_bytes = per;
+    }
+    hipError_t e = pmdi_launch_pack_samples(g->ga.s, a->pack, (long long)per, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "pack-samples launch: %s", hipGetErrorString(e));
+    return pmdi_fusion_add_samples(a, a->pack, c.n_chains, stream);
+}
+
+int pmdi_fusion_merge(pmdi_fusion *a, const int32_t *fused, const int32_t *counts, int64_t S, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    if (a->with_matrix ? !counts : (!fused || counts))
+        return fail(PMDI_E_ARG, a->with_matrix ? "an accumulator with matrices merges counts" : "an accumulator without matrices merges fused, and no counts");
+    if (S < 0) return fail(PMDI_E_ARG, "S=%lld < 0", (long long)S);
+    if (S > 2147483647LL - a->S) return fail(PMDI_E_ARG, "%lld + %lld samples overflow the int32 counts", (long long)a->S, (long long)S);
+    HIP_TRY(hipSetDevice(a->device));
+    hipError_t e = a->with_matrix ? pmdi_launch_psm_acc_merge(a->counts, counts, a->G, a->n, (hipStream_t)stream)      // (fused is its diagonal)
+                                  : pmdi_launch_fusion_merge_obs(a->fused, fused, a->G, a->n, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "fusion-merge launch: %s", hipGetErrorString(e));
+    a->S += S; a->dirty = a->with_matrix;
+    return PMDI_OK;
+}
+
+int64_t pmdi_fusion_samples(const pmdi_fusion *a) { return a ? a->S : 0; }
+
+int pmdi_fusion_groups(const pmdi_fusion *a, int32_t *n_groups, uint8_t *masks)
+{
+    if (!a || !n_groups) return fail(PMDI_E_ARG, "null argument");
+    *n_groups = a->G;
+    if (masks) memcpy(masks, a->masks, (size_t)a->G);
+    return PMDI_OK;
+}
+
+int pmdi_fusion_counts(pmdi_fusion *a, const int32_t **fused, const int32_t **counts, int64_t *S, void *stream)
+{
+    if (!a || !fused) return fail(PMDI_E_ARG, "null argument");
+    if (a->dirty) {
+        HIP_TRY(hipSetDevice(a->device));
+        hipError_t e = pmdi_launch_psm_acc_mirror(a->counts, a->G, a->n, (hipStream_t)stream);
+        if (e == hipSuccess) e = pmdi_launch_fusion_diag(a->counts, a->G, a->n, a->fused, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(PMDI_E_DEVICE, "fusion-mirror launch: %s", hipGetErrorString(e));
+        a->dirty = false;
+    }
+    *fused = a->fused;
+    if (counts) *counts = a->counts;
+    if (S) *S = a->S;
+    return PMDI_OK;
+}
+
 int pmdi_summary_destroy(pmdi_summary *a)
 {
     if (!a) return PMDI_OK;
@@ -1766,7 +1950,8 @@ int pmdi_gibbs_iterate(pmdi_gibbs *g, int64_t n_iter, uint8_t *samples, void *st
     return PMDI_OK;
 }
 
-int pmdi_gibbs_run2(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, void *stream)
+int pmdi_gibbs_run3(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
+                    void *stream)
 {
     if (!g || n_iter < 0) return fail(PMDI_E_ARG, "bad argument");
     if (burnin < 0 || thin < 1) return fail(PMDI_E_ARG, "burnin=%lld must be >= 0 and thin=%lld >= 1", (long long)burnin, (long long)thin);
@@ -1774,6 +1959,7 @@ int pmdi_gibbs_run2(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
     int rc;
     if (acc && (rc = psm_acc_accepts(acc, g, kept))) return rc;
     if (summ && (rc = summary_accepts(summ, g, kept))) return rc;
+    if (fus && (rc = fusion_accepts(fus, g, kept))) return rc;
     for (int64_t t = 1; t <= n_iter; ++t) {
         if ((rc = pmdi_gibbs_step(g, PMDI_STEP_BEGIN, stream)) || (rc = pmdi_gibbs_step(g, PMDI_STEP_HYPERS, stream)) ||
             (rc = pmdi_gibbs_step(g, PMDI_STEP_SWEEP, stream)))
@@ -1783,9 +1969,15 @@ int pmdi_gibbs_run2(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
         if (t > burnin && (t - burnin - 1) % thin == 0) {
             if (acc && (rc = pmdi_psm_acc_add_gibbs(acc, g, stream))) return rc;
             if (summ && (rc = pmdi_summary_add_gibbs(summ, g, stream))) return rc;
+            if (fus && (rc = pmdi_fusion_add_gibbs(fus, g, stream))) return rc;
         }
     }
     return PMDI_OK;
+}
+
+int pmdi_gibbs_run2(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, void *stream)
+{
+    return pmdi_gibbs_run3(g, n_iter, burnin, thin, acc, summ, nullptr, stream);
 }
 
 int pmdi_gibbs_run(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, void *stream)

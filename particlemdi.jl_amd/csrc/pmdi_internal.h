@@ -236,6 +236,15 @@ hipError_t pmdi_launch_label_counts(const int *s, int *counts, int n_rows, long 
 hipError_t pmdi_launch_psm_acc_add(const unsigned char *samples, long long S, int K, long long n, int n_labels, int *counts, hipStream_t stream);
 hipError_t pmdi_launch_psm_acc_mirror(int *counts, int K, long long n, hipStream_t stream);
 hipError_t pmdi_launch_psm_acc_merge(int *a, const int *b, int K, long long n, hipStream_t stream);
+// the streaming fusion accumulator (pmdi_fusion.hip): masks [G] bit sets of datasets on the device; counts [G][n][n] as above with
+// K := G (mirror and merge are the PSM accumulator's); fused [G][n]
+// order [G]: the groups sorted by class (2, 3..4, 5..8 members), n_class[3] how many of each
+hipError_t pmdi_launch_fusion_add(const unsigned char *samples, long long S, int K, long long n, int n_labels, const unsigned char *masks,
+                                  const unsigned char *order, const int *n_class, int *counts, hipStream_t stream);
+hipError_t pmdi_launch_fusion_obs(const unsigned char *samples, long long S, int K, long long n, const unsigned char *masks, int G, int *fused,
+                                  hipStream_t stream);
+hipError_t pmdi_launch_fusion_diag(const int *counts, int G, long long n, int *fused, hipStream_t stream);
+hipError_t pmdi_launch_fusion_merge_obs(int *a, const int *b, int G, long long n, hipStream_t stream);
 // candidates scored against the counts (pmdi_psm_score.hip): out = B agree, B pairs, 1 total, zeroed by the caller; wide: D > 2^22
 hipError_t pmdi_launch_psm_score(const int *counts, int K, long long n, int which, int wide, const int *cand, long long B, long long ld,
                                  unsigned long long *out, hipStream_t stream);

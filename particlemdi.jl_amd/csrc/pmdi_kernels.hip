@@ -266,7 +266,7 @@ __global__ void __launch_bounds__(256) label_count_kernel(const int *__restrict_
 __global__ void __launch_bounds__(256) psm_count_kernel(const unsigned char *__restrict__ samples, long long S, int K, long long n,
                                                         long long row_lo, long long row_hi, int *__restrict__ counts)
 {
-    psm_count_body<false>(samples, S, K, n, blockIdx.z, row_lo + (long long)blockIdx.y * 64, (long long)blockIdx.x * 64, row_hi,
+    psm_count_body<false>(PsmStageLabel{(int)blockIdx.z}, samples, S, K, n, blockIdx.z, row_lo + (long long)blockIdx.y * 64, (long long)blockIdx.x * 64, row_hi,
                           row_hi - row_lo, row_lo, counts);
 }
 
@@ -274,7 +274,7 @@ template <int NKB>
 __global__ void __launch_bounds__(256) psm_count_mfma_kernel(const unsigned char *__restrict__ samples, long long S, int K, long long n,
                                                              long long row_lo, long long row_hi, int *__restrict__ counts)
 {
-    psm_count_mfma_body<NKB, false>(samples, S, K, n, blockIdx.z, row_lo + (long long)blockIdx.y * 128, (long long)blockIdx.x * 128, row_hi,
+    psm_count_mfma_body<NKB, false>(PsmStageLabel{(int)blockIdx.z}, samples, S, K, n, blockIdx.z, row_lo + (long long)blockIdx.y * 128, (long long)blockIdx.x * 128, row_hi,
                                     row_hi - row_lo, row_lo, counts);
 }
 

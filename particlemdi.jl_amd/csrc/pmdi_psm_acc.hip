@@ -20,7 +20,7 @@ __global__ void __launch_bounds__(256) psm_acc_kernel(const unsigned char *__res
 {
     int bi, bj;
     psm_tile_pair(blockIdx.x, bi, bj);
-    psm_count_body<true>(samples, S, K, n, blockIdx.y, (long long)bi * 64, (long long)bj * 64, n, n, 0, counts);
+    psm_count_body<true>(PsmStageLabel{(int)blockIdx.y}, samples, S, K, n, blockIdx.y, (long long)bi * 64, (long long)bj * 64, n, n, 0, counts);
 }
 
 // grid: x = tile pair (128-wide tiles), y = dataset.
@@ -32,7 +32,7 @@ __global__ void __launch_bounds__(256, 4) psm_acc_mfma_kernel(const unsigned cha
 {
     int bi, bj;
     psm_tile_pair(blockIdx.x, bi, bj);
-    psm_count_mfma_body<NKB, true>(samples, S, K, n, blockIdx.y, (long long)bi * 128, (long long)bj * 128, n, n, 0, counts);
+    psm_count_mfma_body<NKB, true>(PsmStageLabel{(int)blockIdx.y}, samples, S, K, n, blockIdx.y, (long long)bi * 128, (long long)bj * 128, n, n, 0, counts);
 }
 
 // counts[k][j][i] = counts[k][i][j] for i > j: a 64 x 64 tile of the lower triangle is read row-wise, transposed through LDS

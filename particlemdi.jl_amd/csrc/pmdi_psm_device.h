@@ -120,18 +120,100 @@ __device__ __forceinline__ void psm_cmp_add4(const WT *w, int ri, const int (&cj
 // Each __global__ wrapper says which tile and where it goes: (i0, j0) its first row and column, i_end the end of the rows it may
 // read and write (the columns end at n); the output holds out_rows rows of n ints per dataset, the first of them row out_row0 of
 // the matrix.  ACC: counts += tile, else counts = tile.
+//
+// How the staged values of one round get into LDS is the body's STAGE parameter, the staging rule:
+//   Elem            the staged value's type
+//   round<ROWS, COLS>(As, Bs, ...)    stages samples t0 .. t0 + ROWS - 1 of the tile's COLS rows (from i0) into As and of its COLS
+//                   columns (from j0) into Bs; what lies beyond the matrix or the samples is staged as a padding value that is never
+//                   equal to anything staged on the other side (MFMA bodies: outside every 32-label block in use)
+// PsmStageLabel: the label of dataset k -- the per-dataset counts.  One byte per lane and step, rows and columns guarded apart.
+struct PsmStageLabel {
+    typedef unsigned char Elem;
+    int k;
+    template <int ROWS, int COLS>
+    __device__ __forceinline__ void round(Elem (*As)[COLS], Elem (*Bs)[COLS], const unsigned char *__restrict__ samples, long long t0,
+                                          long long S, int K, long long n, long long i0, long long j0, long long i_end, int lc, int lt) const
+    {
+#pragma unroll 4
+        for (int tt = lt; tt < ROWS; tt += 256 / COLS) {
+            const long long t = t0 + tt;
+            unsigned char av = 255, bv = 254;                    // padding: never equal to anything on the other side
+            if (t < S) {
+                const unsigned char *row = samples + ((size_t)t * K + k) * n;
+                if (i0 + lc < i_end) av = row[i0 + lc];
+                if (j0 + lc < n) bv = row[j0 + lc];
+            }
+            As[tt][lc] = av; Bs[tt][lc] = bv;
+        }
+    }
+};
 
-// Byte compares on the vector ALUs (any label 0..255).  One workgroup = a 64 x 64 tile of (row i, column j) pairs of dataset k;
-// 256 lanes, 4 x 4 pairs each.  The labels of 64 samples for the tile's 64 rows and 64 columns are staged in LDS (sample-major,
-// so a lane reads its 4 row labels and 4 column labels as one dword each).
-#define PSM_TT 64
-template <bool ACC>
-__device__ __forceinline__ void psm_count_body(const unsigned char *__restrict__ samples, long long S, int K, long long n, int k,
-                                               long long i0, long long j0, long long i_end, long long out_rows, long long out_row0,
-                                               int *__restrict__ counts)
+// PsmStageFused: the label the NM datasets mem[] share (a group of fewer repeats its first member), or "nothing" when they do not
+// all agree -- the fused counts of pmdi_fusion.hip.  E = unsigned char for the MFMA bodies, where the padding bytes already are
+// "nothing" (an all-zero one-hot row); E = unsigned short for the byte compares, where every byte 0..255 may be a label and the
+// fused flag needs a bit of its own: 0x100 / 0x200 lie above all of them.  Every address is clamped into the batch and the guards
+// select afterwards, so no load sits under a branch: the 2 NM loads of each of four steps are in flight together.
+template <typename E, int NM>
+struct PsmStageFused {
+    typedef E Elem;
+    static constexpr Elem pad_a = sizeof(E) == 1 ? 255 : 0x100, pad_b = sizeof(E) == 1 ? 254 : 0x200;
+    int mem[NM];
+    __device__ __forceinline__ explicit PsmStageFused(unsigned mask)       // mask: workgroup-uniform, 2 .. NM bits set
+    {
+        const int first = __builtin_ctz(mask);
+#pragma unroll
+        for (int j = 0; j < NM; ++j) {
+            mem[j] = mask ? __builtin_ctz(mask) : first;
+            mask &= mask - 1;
+        }
+    }
+    template <int ROWS, int COLS>
+    __device__ __forceinline__ void round(Elem (*As)[COLS], Elem (*Bs)[COLS], const unsigned char *__restrict__ samples, long long t0,
+                                          long long S, int K, long long n, long long i0, long long j0, long long i_end, int lc, int lt) const
+    {
+        const bool in_a = i0 + lc < i_end, in_b = j0 + lc < n;
+        const long long xa = in_a ? i0 + lc : i0, xb = in_b ? j0 + lc : j0;       // (i0 < i_end <= n and j0 < n: both inside)
+#pragma unroll 4
+        for (int tt = lt; tt < ROWS; tt += 256 / COLS) {
+            const long long t = t0 + tt;
+            const unsigned char *row = samples + (size_t)(t < S ? t : S - 1) * K * n;
+            unsigned char a[NM], b[NM];
+#pragma unroll
+            for (int j = 0; j < NM; ++j) { a[j] = row[(size_t)mem[j] * n + xa]; b[j] = row[(size_t)mem[j] * n + xb]; }
+            bool fa = in_a && t < S, fb = in_b && t < S;
+#pragma unroll
+            for (int j = 1; j < NM; ++j) { fa &= a[j] == a[0]; fb &= b[j] == b[0]; }
+            As[tt][lc] = fa ? (Elem)a[0] : pad_a; Bs[tt][lc] = fb ? (Elem)b[0] : pad_b;
+        }
+    }
+};
+
+// four consecutive staged values of an LDS row as one read
+__device__ __forceinline__ void psm_unpack4(const unsigned char *p, unsigned (&v)[4])
 {
-    __shared__ __attribute__((aligned(16))) unsigned char As[PSM_TT][64];
-    __shared__ __attribute__((aligned(16))) unsigned char Bs[PSM_TT][64];
+    const unsigned v4 = *(const unsigned *)p;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = (v4 >> (8 * r)) & 0xffu;
+}
+
+__device__ __forceinline__ void psm_unpack4(const unsigned short *p, unsigned (&v)[4])
+{
+    const uint2 v4 = *(const uint2 *)p;
+    v[0] = v4.x & 0xffffu; v[1] = v4.x >> 16; v[2] = v4.y & 0xffffu; v[3] = v4.y >> 16;
+}
+
+// Byte compares on the vector ALUs (any label 0..255).  One workgroup = a 64 x 64 tile of (row i, column j) pairs of matrix k;
+// 256 lanes, 4 x 4 pairs each.  The staged values of 64 samples for the tile's 64 rows and 64 columns are kept in LDS (sample-major,
+// so a lane reads its 4 row values and 4 column values as one dword, or two, each).
+#define PSM_TT 64
+template <bool ACC, typename STAGE>
+__device__ __forceinline__ void psm_count_body(const STAGE stage, const unsigned char *__restrict__ samples, long long S, int K,
+                                               long long n, int k, long long i0, long long j0, long long i_end, long long out_rows,
+                                               long long out_row0, int *__restrict__ counts)
+{
+    typedef typename STAGE::Elem Elem;
+    __shared__ __attribute__((aligned(16))) Elem As[PSM_TT][64];
+    __shared__ __attribute__((aligned(16))) Elem Bs[PSM_TT][64];
     const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
     int acc[4][4];
 #pragma unroll
@@ -140,25 +222,13 @@ __device__ __forceinline__ void psm_count_body(const unsigned char *__restrict__
         for (int c = 0; c < 4; ++c) acc[r][c] = 0;
     const int lc = tid & 63, lt = tid >> 6;                 // staging: column of the tile, sample row mod 4
     for (long long t0 = 0; t0 < S; t0 += PSM_TT) {
-#pragma unroll 4
-        for (int tt = lt; tt < PSM_TT; tt += 4) {
-            const long long t = t0 + tt;
-            unsigned char av = 255, bv = 254;                // padding: never equal to anything on the other side
-            if (t < S) {
-                const unsigned char *row = samples + ((size_t)t * K + k) * n;
-                if (i0 + lc < i_end) av = row[i0 + lc];
-                if (j0 + lc < n) bv = row[j0 + lc];
-            }
-            As[tt][lc] = av; Bs[tt][lc] = bv;
-        }
+        stage.template round<PSM_TT, 64>(As, Bs, samples, t0, S, K, n, i0, j0, i_end, lc, lt);
         __syncthreads();
 #pragma unroll 8
         for (int tt = 0; tt < PSM_TT; ++tt) {
-            const unsigned a4 = *(const unsigned *)&As[tt][ty * 4];
-            const unsigned b4 = *(const unsigned *)&Bs[tt][tx * 4];
             unsigned a[4], b[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { a[r] = (a4 >> (8 * r)) & 0xffu; b[r] = (b4 >> (8 * r)) & 0xffu; }
+            psm_unpack4(&As[tt][ty * 4], a);
+            psm_unpack4(&Bs[tt][tx * 4], b);
 #pragma unroll
             for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -202,11 +272,12 @@ __device__ __forceinline__ psm_v4i psm_onehot(int label, int kb, int h)
 }
 
 #define PSM_MT 32       // samples staged per round
-template <int NKB, bool ACC>
-__device__ __forceinline__ void psm_count_mfma_body(const unsigned char *__restrict__ samples, long long S, int K, long long n, int k,
-                                                    long long i0, long long j0, long long i_end, long long out_rows, long long out_row0,
-                                                    int *__restrict__ counts)
+template <int NKB, bool ACC, typename STAGE>
+__device__ __forceinline__ void psm_count_mfma_body(const STAGE stage, const unsigned char *__restrict__ samples, long long S, int K,
+                                                    long long n, int k, long long i0, long long j0, long long i_end, long long out_rows,
+                                                    long long out_row0, int *__restrict__ counts)
 {
+    static_assert(sizeof(typename STAGE::Elem) == 1, "the one-hot fragments are built from staged bytes");
     __shared__ __attribute__((aligned(16))) unsigned char As[PSM_MT][128];
     __shared__ __attribute__((aligned(16))) unsigned char Bs[PSM_MT][128];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -221,17 +292,7 @@ __device__ __forceinline__ void psm_count_mfma_body(const unsigned char *__restr
             for (int e = 0; e < 16; ++e) acc[a][b][e] = 0;
     const int lc = tid & 127, lt = tid >> 7;                   // staging: column of the tile, sample row mod 2
     for (long long t0 = 0; t0 < S; t0 += PSM_MT) {
-#pragma unroll 4
-        for (int tt = lt; tt < PSM_MT; tt += 2) {
-            const long long t = t0 + tt;
-            unsigned char av = 255, bv = 254;                  // padding
-            if (t < S) {
-                const unsigned char *row = samples + ((size_t)t * K + k) * n;
-                if (i0 + lc < i_end) av = row[i0 + lc];
-                if (j0 + lc < n) bv = row[j0 + lc];
-            }
-            As[tt][lc] = av; Bs[tt][lc] = bv;
-        }
+        stage.template round<PSM_MT, 128>(As, Bs, samples, t0, S, K, n, i0, j0, i_end, lc, lt);
         __syncthreads();
 #pragma unroll 2
         for (int tt = 0; tt < PSM_MT; ++tt) {

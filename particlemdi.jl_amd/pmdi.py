@@ -112,7 +112,7 @@ def pmdi(dataFiles, dataTypes, N, particles, rho, iter, outputFile, thin=1, feat
 
 
 def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=0, thin=1, featureSelect=False,
-                seed=0, device=0, q1_mode=0, q2_mode=0, summary=False, final_allocations=False):
+                seed=0, device=0, q1_mode=0, q2_mode=0, summary=False, final_allocations=False, **more):
     """`n_chains` independent chains of particleMDI on one MI355X, pooled on the device: runs `iter` iterations of every
     chain, discards the first `burnin`, adds every `thin`-th one after that (psm.retained_iterations) of every chain to one
     streaming accumulator (psm.PsmAccumulator) and returns its psm.PsmCounts -- the device-resident posterior-similarity
@@ -123,13 +123,34 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     over the chains, a trace row per retained iteration and, with featureSelect=True, the feature-selection probabilities.
     Its rows are the ones summary.get_phi / get_nclust / get_feature_select_probs keep with burnin + 1 in a file of pmdi().
     final_allocations=True: the chains' last allocations are copied to an int32 CUDA tensor (n_chains, K, n) of 0-based labels
-    before the handles close and appended to the returned tuple -- the candidates of psm.best_sampled_allocation."""
+    before the handles close and appended to the returned tuple -- the candidates of psm.best_sampled_allocation.
+    fusion (keyword only, default False): a third accumulator (fusion.FusionAccumulator) takes the same retained iterations and its fusion.FusionCounts --
+    per group of datasets, how often each observation is clustered alike in all of them, and the posterior-similarity matrix
+    of those fused observations -- is returned after the summary: (counts[, summary][, fusion][, draws]).  True = all pairs
+    of datasets, with matrices; "probabilities" = all pairs, the per-observation counts only; an iterable of tuples of
+    0-based dataset indices = those groups, with matrices.  Needs K > 1."""
+    from .fusion import FusionAccumulator, _group_masks
+    fusion = more.pop("fusion", False)
+    if more:
+        raise TypeError(f"pmdi_pooled() got an unexpected keyword argument {next(iter(more))!r}")
     from .psm import PsmAccumulator, _DeviceInt32View, retained_iterations
     from .summary import SummaryAccumulator
     K, n_obs, names = _check_arguments(dataFiles, dataTypes, N, particles, rho)
     _need(n_chains >= 1, "n_chains must be >= 1")
     _need(0 <= burnin < iter, "burnin must be >= 0 and smaller than iter (nothing would be retained)")
     _need(thin >= 1, "thin must be >= 1")
+    fusion_groups, fusion_matrix = None, True
+    if fusion is not False and fusion is not None:
+        _need(K > 1, "fusion needs two or more datasets")
+        if isinstance(fusion, str):
+            _need(fusion == "probabilities", 'fusion must be True, "probabilities" or an iterable of groups of datasets')
+            fusion_matrix = False
+        elif fusion is not True:
+            fusion_groups, masks = _group_masks(K, fusion)
+            _need(len(fusion_groups) >= 1, "fusion: no group given")
+            _need(all(len(g) >= 2 and g[-1] < K for g in fusion_groups), f"fusion: every group needs two or more of the datasets 0..{K - 1}")
+            _need(len(set(masks.tolist())) == len(masks), "fusion: a group is given twice")
+        fusion = True
     sweeper = Sweeper(dataFiles, dataTypes, N, particles, n_chains=n_chains, seed=seed, device=device,
                       q1_mode=q1_mode, q2_mode=q2_mode)
     g = Gibbs(sweeper, rho=rho, feature_select=bool(featureSelect))
@@ -138,11 +159,14 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     if summary:
         summ = SummaryAccumulator(n_chains, K, N, n_obs, sumD=sweeper.sumD if featureSelect else 0,
                                   trace_cap=len(retained_iterations(iter, burnin, thin)), device=device)
+    fus = FusionAccumulator(K, n_obs, n_labels=N, groups=fusion_groups, matrix=fusion_matrix, device=device) if fusion else None
     try:
-        g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ)
+        g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ, fusion=fus)
         g.results()                      # synchronises; raises on a kernel-side error of any chain
         counts = acc.counts(names=names)   # (the view keeps the accumulator alive)
         out = (counts,) if summ is None else (counts, summ.summary(names=names, feature_D=sweeper.D))
+        if fus is not None:
+            out += (fus.counts(names=names),)      # (views again: they keep the accumulator alive)
         if final_allocations:
             import torch
             dev = torch.device("cuda", int(device))

@@ -1,0 +1,223 @@
+"""The streaming fusion accumulator without a GPU: the new entry points are declared, exported and listed; the kernels are in
+the code object; pmdi_fusion_create validates before it touches a device; the default groups are the pairs in the order of
+Phi; pmdi_pooled checks its fusion argument before it builds anything; the yardstick on a case worked by hand; every kernel
+of pmdi_fusion.hip compiles for gfx950 without scratch."""
+import ctypes as C
+import importlib
+import os
+import re
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import _np_fusion as NF
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+NEW_FUNCTIONS = ["pmdi_fusion_create", "pmdi_fusion_destroy", "pmdi_fusion_reset", "pmdi_fusion_add_samples",
+                 "pmdi_fusion_add_gibbs", "pmdi_fusion_merge", "pmdi_fusion_samples", "pmdi_fusion_groups", "pmdi_fusion_counts",
+                 "pmdi_gibbs_run3"]
+KERNELS = ("fusion_acc_kernel", "fusion_acc_mfma_kernel", "fusion_obs_kernel", "fusion_diag_kernel", "fusion_add_kernel")
+
+
+def test_new_entry_points_are_declared_exported_and_listed(pkg):
+    src = open(os.path.join(ROOT, "include", "pmdi_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    declared = set(re.findall(r"\b(pmdi_[A-Za-z_0-9]+)\s*\(", src))
+    lib = pkg.lib()
+    for name in NEW_FUNCTIONS:
+        assert name in declared, f"{name} is not declared in include/pmdi_hip.h"
+        assert hasattr(lib, name), f"{name} is not exported by the library"
+        assert name in pkg.EXPORTS, f"{name} is not listed in EXPORTS"
+    assert lib.pmdi_abi_version() == pkg.ABI_VERSION == 2
+    for name in ("FusionAccumulator", "FusionCounts", "fused_consensus_allocations"):
+        assert hasattr(pkg, name), name
+
+
+def test_the_kernels_are_in_the_code_object(pkg):
+    blob = open(pkg.LIB_PATH, "rb").read()
+    for kernel in KERNELS:
+        assert kernel.encode() in blob, kernel
+
+
+def _masks(groups):
+    return np.array([sum(1 << k for k in g) for g in groups], dtype=np.uint8)
+
+
+GOOD = dict(K=3, n=100, n_labels=12, groups=((0, 1), (0, 1, 2)))
+
+
+@pytest.mark.parametrize("change", [
+    dict(K=1, groups=None), dict(K=1), dict(K=0, groups=None), dict(K=9, groups=None), dict(n=0), dict(n=65536), dict(n_labels=-1),
+    dict(n_labels=256), dict(groups=((0,), (0, 1))), dict(groups=((0, 1), ())), dict(groups=((0, 3),)), dict(groups=((1, 2), (0, 7))),
+    dict(groups=((0, 1), (1, 2), (1, 0))), dict(groups=())])
+def test_create_validates_before_any_device_use(pkg, change):
+    a = {**GOOD, **change}
+    h = C.c_void_p()
+    if a["groups"] is None:
+        rc = pkg.lib().pmdi_fusion_create(0, a["K"], a["n"], a["n_labels"], 0, None, 1, C.byref(h))
+    else:
+        m = _masks(a["groups"])
+        buf = np.concatenate([m, np.zeros(1, dtype=np.uint8)])         # (an empty list still has an address: n_groups = 0 is the error)
+        rc = pkg.lib().pmdi_fusion_create(0, a["K"], a["n"], a["n_labels"], len(m), buf.ctypes.data_as(C.c_void_p), 1, C.byref(h))
+    assert rc == -1                    # PMDI_E_ARG, with or without a GPU
+    assert not h.value
+    with pytest.raises(pkg.PmdiError) as e:
+        pkg.FusionAccumulator(a["K"], a["n"], a["n_labels"], groups=a["groups"])
+    assert e.value.code == -1
+
+
+def test_create_with_good_arguments_reaches_the_device(pkg):
+    """The checks above are not vacuous: the same call with nothing wrong gets as far as the device -- PMDI_E_DEVICE where
+    there is none (no CPU path), an accumulator where there is one."""
+    import torch
+    m = _masks(GOOD["groups"])
+    for with_matrix in (1, 0):
+        h = C.c_void_p()
+        rc = pkg.lib().pmdi_fusion_create(0, GOOD["K"], GOOD["n"], GOOD["n_labels"], len(m), m.ctypes.data_as(C.c_void_p), with_matrix,
+                                          C.byref(h))
+        if torch.cuda.is_available():
+            assert rc == 0 and h.value
+            G = C.c_int32(0)
+            got = np.zeros(2, dtype=np.uint8)
+            assert pkg.lib().pmdi_fusion_groups(h, C.byref(G), got.ctypes.data_as(C.c_void_p)) == 0
+            assert G.value == 2 and got.tolist() == m.tolist()
+            assert pkg.lib().pmdi_fusion_samples(h) == 0
+            assert pkg.lib().pmdi_fusion_destroy(h) == 0
+        else:
+            assert rc == -2 and not h.value
+    assert pkg.lib().pmdi_fusion_samples(None) == 0
+    assert pkg.lib().pmdi_fusion_destroy(None) == 0
+
+
+def test_null_handles_are_argument_errors(pkg):
+    L = pkg.lib()
+    assert L.pmdi_fusion_create(0, 2, 10, 0, 0, None, 1, None) == -1
+    assert L.pmdi_fusion_reset(None, None) == -1
+    assert L.pmdi_fusion_add_samples(None, None, 1, None) == -1
+    assert L.pmdi_fusion_add_gibbs(None, None, None) == -1
+    assert L.pmdi_fusion_merge(None, None, None, 0, None) == -1
+    assert L.pmdi_fusion_groups(None, None, None) == -1
+    assert L.pmdi_fusion_counts(None, None, None, None, None) == -1
+    assert L.pmdi_gibbs_run3(None, 1, 0, 1, None, None, None, None) == -1
+
+
+def test_default_group_order_is_the_order_of_phi(pkg):
+    """calculate_Phi_lab (src/update_hypers.jl): i = 1; for k1 in 1:(K - 1), for k2 in (k1 + 1):K -- written out by hand here,
+    the order tests/test_summary_host.py::test_phi_matrix_pair_order pins for phi_matrix()."""
+    from particlemdi_jl_amd import fusion
+    by_hand = {2: ((0, 1),), 3: ((0, 1), (0, 2), (1, 2)), 4: ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))}
+    for K, want in by_hand.items():
+        assert fusion.default_groups(K) == want == NF.default_groups(K)
+    # the library's own default (the C loop of pmdi_fusion_create) is read back where there is a device: test_gpu_fusion.py
+    src = open(os.path.join(ROOT, "particlemdi.jl_amd", "csrc", "pmdi_api.cpp")).read()
+    body = src[src.index("int pmdi_fusion_create("):]
+    assert re.search(r"for \(int k1 = 0; k1 < K - 1; \+\+k1\)\s*for \(int k2 = k1 \+ 1; k2 < K; \+\+k2\) masks\[G\+\+\]", body)
+
+
+def test_group_masks_and_members(pkg):
+    from particlemdi_jl_amd import fusion
+    groups, masks = fusion._group_masks(4, [(2, 0), (3, 1, 0), [1, 1, 2]])
+    assert groups == ((0, 2), (0, 1, 3), (1, 2)) and masks.tolist() == [5, 11, 6]
+    assert [fusion._mask_members(m) for m in masks] == list(groups)
+    for bad in ([(0, 8)], [(-1, 0)]):
+        with pytest.raises(ValueError):
+            fusion._group_masks(4, bad)
+
+
+def test_the_yardstick_on_a_case_worked_by_hand():
+    """S = 2, K = 3, n = 3.  Sample 0: dataset rows 0: [5 5 7], 1: [5 6 7], 2: [5 5 9]; sample 1: 0: [1 1 1], 1: [1 1 2], 2: [3 1 1].
+    (0,1): fused in sample 0 at i = 0, 2 (labels 5, 7), in sample 1 at i = 0, 1 (labels 1, 1).
+    (0,1,2): sample 0 at i = 0; sample 1 at i = 1."""
+    smp = np.array([[[5, 5, 7], [5, 6, 7], [5, 5, 9]], [[1, 1, 1], [1, 1, 2], [3, 1, 1]]], dtype=np.uint8)
+    fused, counts = NF.fusion_counts(smp, ((0, 1), (2, 1, 0)))
+    assert fused.tolist() == [[2, 1, 1], [1, 1, 0]]
+    assert counts[0].tolist() == [[2, 1, 0], [1, 1, 0], [0, 0, 1]]
+    assert counts[1].tolist() == [[1, 0, 0], [0, 1, 0], [0, 0, 0]]
+
+
+def test_fusion_counts_arithmetic(pkg):
+    """FusionCounts on host tensors (nothing here needs a device): index, probabilities as one IEEE division each,
+    fused_observations with a strict threshold, psm() without matrices."""
+    import torch
+    fc = pkg.FusionCounts(((0, 1), (0, 2)), ["A+B", "A+C"], 3, torch.tensor([[3, 1, 2], [0, 3, 1]], dtype=torch.int32))
+    assert fc.index((1, 0)) == 0 and fc.index([0, 2]) == 1 and fc.index(1) == 1
+    for bad in ((1, 2), 2, -1):
+        with pytest.raises(ValueError):
+            fc.index(bad)
+    p = fc.probabilities()
+    assert p.dtype == np.float64 and p.tolist() == [[1.0, 1 / 3, 2 / 3], [0.0, 1.0, 1 / 3]]
+    assert fc.fused_observations((0, 1)).tolist() == [0, 2] and fc.fused_observations((0, 1)).dtype == np.int64
+    assert fc.fused_observations(1, threshold=1 / 3).tolist() == [1]          # strictly above
+    with pytest.raises(ValueError):
+        fc.psm((0, 1))
+    with pytest.raises(ValueError):
+        pkg.fused_consensus_allocations(fc, (0, 1), k=2)
+
+
+def _good():
+    x = np.zeros((10, 2))
+    return dict(dataFiles=[x, x, x], dataTypes=["gaussian"] * 3, N=3, particles=4, rho=0.25, iter=5, n_chains=2)
+
+
+@pytest.mark.parametrize("change", [
+    dict(dataFiles=[np.zeros((10, 2))], dataTypes=["gaussian"], fusion=True),
+    dict(dataFiles=[np.zeros((10, 2))], dataTypes=["gaussian"], fusion="probabilities"),
+    dict(dataFiles=[np.zeros((10, 2))], dataTypes=["gaussian"], fusion=[(0, 1)]),
+    dict(fusion="matrices"), dict(fusion=[(0,)]), dict(fusion=[(0, 3)]), dict(fusion=[(0, 1), (1, 0)]), dict(fusion=[]),
+    dict(fusion=[(0, -1)]), dict(fusion=True, burnin=5)])
+def test_pmdi_pooled_checks_fusion_before_building_anything(pkg, change, monkeypatch):
+    P = importlib.import_module("particlemdi_jl_amd.pmdi")
+
+    def never(*a, **k):
+        raise AssertionError("pmdi_pooled built something before it had checked its arguments")
+    monkeypatch.setattr(P, "Sweeper", never)
+    monkeypatch.setattr(P, "Gibbs", never)
+    with pytest.raises(ValueError):
+        P.pmdi_pooled(**{**_good(), **change})
+
+
+@pytest.mark.parametrize("fusion", [True, "probabilities", [(0, 1), (2, 1, 0)], False])
+def test_pmdi_pooled_takes_fusion_after_its_checks(pkg, fusion, monkeypatch):
+    P = importlib.import_module("particlemdi_jl_amd.pmdi")
+
+    class Reached(Exception):
+        pass
+
+    def reached(*a, **k):
+        raise Reached()
+    monkeypatch.setattr(P, "Sweeper", reached)
+    with pytest.raises(Reached):
+        P.pmdi_pooled(**_good(), fusion=fusion)
+
+
+def test_fusion_kernels_use_no_scratch():
+    """hipcc cross-compiles without a GPU: every kernel of pmdi_fusion.hip reports ScratchSize 0 and no VGPR spills, and the
+    matrix-core kernels the four waves per SIMD they ask for."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    src = os.path.join(ROOT, "particlemdi.jl_amd", "csrc", "pmdi_fusion.hip")
+    with tempfile.TemporaryDirectory() as tmp:
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
+                            "--cuda-device-only", "-c", src, "-o", os.path.join(tmp, "x.o"),
+                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    cur, scratch, vspill, occ = None, {}, {}, {}
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = m.group(1)
+        for pat, into in ((r"ScratchSize \[bytes/lane\]: (\d+)", scratch), (r"VGPRs Spill: (\d+)", vspill),
+                          (r"Occupancy \[waves/SIMD\]: (\d+)", occ)):
+            m = re.search(pat, line)
+            if m and cur:
+                into[cur] = int(m.group(1))
+    mfma = [k for k in scratch if "fusion_acc_mfma_kernel" in k]
+    assert len(mfma) == 6, sorted(scratch)          # labels < 32 / < 64, groups of up to 2 / 4 / 8 datasets
+    for want in KERNELS:
+        assert any(want in k for k in scratch), (want, sorted(scratch))
+    for k in scratch:
+        assert scratch[k] == 0 and vspill[k] == 0, (k, scratch[k], vspill[k])
+    for k in mfma:
+        assert occ[k] >= 4, (k, occ[k])
