@@ -12,10 +12,11 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("PMDI_LIB_PATH") or os.path.join(_PKG, "libpmdi_hip.so")   # override: A/B builds only
-_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_fusion.hip", "pmdi_summary.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_api.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
+_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_fusion.hip", "pmdi_summary.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_api.cpp", "pmdi_acc.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
 _HEADERS = [os.path.join(_PKG, "csrc", "pmdi_internal.h"), os.path.join(_PKG, "csrc", "pmdi_device.h"),
             os.path.join(_PKG, "csrc", "pmdi_sweep_body.h"), os.path.join(_PKG, "csrc", "pmdi_sweep2_body.h"),
             os.path.join(_PKG, "csrc", "pmdi_arith.h"), os.path.join(_PKG, "csrc", "pmdi_psm_device.h"),
+            os.path.join(_PKG, "csrc", "pmdi_host.h"),
             os.path.join(_ROOT, "include", "pmdi_hip.h")]
 
 GAUSSIAN, CATEGORICAL, NEGBINOM = 0, 1, 2
@@ -338,9 +339,57 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
-class Sweeper:
+class _Handle:
+    """Owner of one handle of the library: `self.h` is None until the subclass's constructor has created it and after close();
+    `_destroy` names the function that frees it (default: `_prefix`_destroy)."""
+    _prefix = _destroy = None
+    h = None
+
+    def close(self):
+        if self.h:
+            getattr(lib(), self._destroy or self._prefix + "_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Accumulator(_Handle):
+    """What the streaming accumulators (psm.PsmAccumulator, fusion.FusionAccumulator, summary.SummaryAccumulator) share: the
+    entry points `_prefix`_destroy / _reset / _add_gibbs / _samples, and every call on the current torch stream of `self.device`."""
+
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+
+    def _samples(self):
+        return int(getattr(lib(), self._prefix + "_samples")(self.h))
+
+    def reset(self):
+        _check(getattr(lib(), self._prefix + "_reset")(self.h, self._stream()))
+
+    def add_gibbs(self, gibbs):
+        """The current state of every chain of a Gibbs, as far as this accumulator counts it (the counting accumulators: the
+        allocations, n_chains samples; the summary: s, M, Phi, and the feature flags when feature selection is on)."""
+        _check(getattr(lib(), self._prefix + "_add_gibbs")(self.h, gibbs.h, self._stream()))
+
+    def _checked_tensor(self, t, dtype, shape, what):
+        """t, contiguous, if it is a CUDA tensor of that dtype and shape (None: any extent) on this device; else ValueError."""
+        if t is None or not t.is_cuda or t.dtype != dtype or t.dim() != len(shape) or (t.device.index or 0) != self.device \
+                or any(want is not None and want != got for want, got in zip(shape, t.shape)):
+            got = "None" if t is None else f"{t.dtype} {tuple(t.shape)} on {t.device}"
+            want = "(" + ", ".join("*" if w is None else str(w) for w in shape) + ")"
+            raise ValueError(f"{type(self).__name__}.{what} must be a CUDA {dtype} tensor {want} on device {self.device}, not {got}")
+        return t.contiguous()
+
+
+class Sweeper(_Handle):
     """A batch of `n_chains` independent chains on one MI355X: the device side of
     pmdi()'s per-iteration sweep (src/pmdi.jl:165-171, 188-350, 354-370)."""
+    _destroy = "pmdi_destroy"
 
     def __init__(self, data, kinds, N, P, n_chains=1, seed=0, device=0, q1_mode=0, q2_mode=0,
                  pool_cap=0, block_threads=0, tuning=None):
@@ -392,17 +441,6 @@ class Sweeper:
         self.settled = bool(L.pmdi_settled_kernel(h, None))
         self.npairs = max(1, self.K * (self.K - 1) // 2)
         self._keep = None  # the library copied the data
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().pmdi_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def sweep(self, it, s, order_obs, n1, Pi, Phi, flags=None, lw_init=None, trace=False):
         """Per chain (leading axis C, dropped when n_chains == 1 inputs are 2-D):
@@ -499,8 +537,9 @@ class Sweeper:
         return ClusterBatch(self, k, B)
 
 
-class CsvWriter:
+class CsvWriter(_Handle):
     """pmdi()'s output file (src/pmdi.jl:147-158, 377-383) written by the native, byte-compatible writer."""
+    _destroy = "pmdi_csv_close"
 
     def __init__(self, path, K, n, data_names=None, feature_D=None):
         names = None
@@ -527,17 +566,6 @@ class CsvWriter:
         f = np.ascontiguousarray(fl, dtype=np.uint8)
         _check(lib().pmdi_csv_write_flags(self.h, _ptr(f)))
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().pmdi_csv_close(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def read_allocations(path, burnin=0, thin=1):
     """The allocation samples of a pmdi() output file as generate_psm reads them (consensus_map.jl:32-47), through the native
@@ -559,8 +587,9 @@ def format_float64(x):
     return buf.value.decode()
 
 
-class Comm:
+class Comm(_Handle):
     """One rank of the RCCL communicator behind pmdi_allgather_samples (one process per GPU)."""
+    _destroy = "pmdi_comm_destroy"
 
     def __init__(self, device, n_ranks, rank, unique_id):
         uid = np.ascontiguousarray(unique_id, dtype=np.uint8)
@@ -581,17 +610,6 @@ class Comm:
         st = (C.c_void_p * 1)(stream or None)
         _check(lib().pmdi_allgather_samples(comms, 1, send, recv, int(bytes_per_rank), st))
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().pmdi_comm_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class GibbsView(C.Structure):
     _fields_ = [(f, C.c_void_p) for f in ("M", "gamma", "gamma0", "Phi", "vZ", "Pi", "log1p_phi", "feature_prob", "logweight",
@@ -601,10 +619,11 @@ class GibbsView(C.Structure):
 STEP_BEGIN, STEP_HYPERS, STEP_SWEEP, STEP_FEATSEL, STEP_ALIGN = range(5)
 
 
-class Gibbs:
+class Gibbs(_Handle):
     """Device-resident Gibbs chains of a Sweeper's handle (include/pmdi_hip.h, pmdi_gibbs_*): M, gamma, Phi, v, Z,
     the allocations and order_obs of every chain live on the MI355X; an iteration (src/pmdi.jl:164-384) is a
     handful of kernel launches and nothing crosses PCIe."""
+    _destroy = "pmdi_gibbs_destroy"
 
     def __init__(self, sweeper, rho=0.25, feature_select=False):
         self.sw = sweeper
@@ -612,17 +631,6 @@ class Gibbs:
         _check(lib().pmdi_gibbs_create(sweeper.h, float(rho), int(bool(feature_select)), C.byref(h)))
         self.h = h
         self.n1 = int(np.floor(rho * sweeper.n))
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().pmdi_gibbs_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def iterate(self, n_iter=1, samples_ptr=None, stream=None):
         _check(lib().pmdi_gibbs_iterate(self.h, int(n_iter), C.c_void_p(samples_ptr) if samples_ptr else None,
@@ -687,9 +695,10 @@ class Gibbs:
         return v
 
 
-class ClusterBatch:
+class ClusterBatch(_Handle):
     """B stand-alone clusters of dataset k on the device: the calc_logprob /
     cluster_add! / calc_logmarginal protocol of src/datatypes/*.jl."""
+    _destroy = "pmdi_clusters_free"
 
     def __init__(self, sweeper, k, B):
         self.sw, self.k, self.B = sweeper, int(k), int(B)
@@ -722,14 +731,3 @@ class ClusterBatch:
         out = np.zeros((self.B, stride.value))
         _check(lib().pmdi_cluster_stats(self.h, _ptr(out), C.addressof(stride)))
         return out
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().pmdi_clusters_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -1,0 +1,483 @@
+// pmdi_acc.cpp -- the streaming accumulators of include/pmdi_hip.h (pmdi_psm_acc_*, pmdi_fusion_*, pmdi_summary_*) and their
+// driver pmdi_gibbs_run / run2 / run3, which needs nothing of a pmdi_gibbs but the public pmdi_gibbs_step.
+#include "pmdi_host.h"
+
+#include <cstring>
+#include <new>
+
+// What the two counting accumulators share: the problem they count for, the samples behind the counts and the label bytes
+// of the last *_add_gibbs
+struct CountingAcc {
+    int device = 0, K = 0, n_labels = 0;
+    long long n = 0;
+    int64_t S = 0;                       // samples behind the counts
+    bool dirty = false;                  // something was added since the last mirror (fusion: with matrices only)
+    unsigned char *pack = nullptr;       // [n_chains][K][n] label bytes of *_add_gibbs, allocated at first use
+    size_t pack_bytes = 0;
+};
+
+// Streaming PSM accumulator (pmdi_psm_acc_* entry points)
+struct pmdi_psm_acc : CountingAcc {
+    int *counts = nullptr;               // [K][n][n]; the strict upper triangle is current only while !dirty
+};
+
+// Streaming fusion accumulator (pmdi_fusion_* entry points)
+struct pmdi_fusion : CountingAcc {
+    int G = 0;
+    bool with_matrix = false;
+    unsigned char masks[256] = {};       // [G] bit sets of datasets (at most 247 sets of two or more of 8)
+    unsigned char order[256] = {};       // [G] the groups sorted by class: 2 members, 3..4, 5..8 (the counting kernels' builds)
+    int n_class[3] = {};                 // groups per class
+    unsigned char *d_masks = nullptr;    // masks, then order, on the device: 2 x 256 bytes
+    int *counts = nullptr;               // [G][n][n], or null without matrices; the strict upper triangle is current only while !dirty
+    int *fused = nullptr;                // [G][n]; with matrices: the diagonals, current only while !dirty
+};
+
+// Streaming summary accumulator (pmdi_summary_* entry points): one device slab, the arrays of include/pmdi_hip.h one after
+// the other (8-byte elements), then the error flag and the per-add scratch
+enum { SUM_HIST, SUM_NSUM, SUM_NSUMSQ, SUM_M_MEAN, SUM_M_M2, SUM_PHI_MEAN, SUM_PHI_M2, SUM_FLAG_COUNT, SUM_TR_NCLUST, SUM_TR_M,
+       SUM_TR_PHI, SUM_ARRAYS };         // the order of pmdi_summary_get's arguments
+struct pmdi_summary {
+    int device = 0, C = 0, K = 0, N = 0, npairs = 0;
+    long long n = 0, sumD = 0, trace_cap = 0;
+    char *slab = nullptr;
+    size_t state_bytes = 0;              // what reset zeroes: every array and the error flag
+    size_t count[SUM_ARRAYS] = {};       // elements of each array ...
+    char *at[SUM_ARRAYS] = {};           // ... and where it starts in the slab (int64: hist, nsum, nsumsq, flag_count, tr_nclust; else double)
+    int *err = nullptr, *nclust = nullptr;
+    int64_t T = 0;                       // adds so far
+};
+
+namespace {
+
+// the device of a new accumulator: it exists, and is the current one from here on
+int open_device(int32_t device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(PMDI_E_DEVICE, "no HIP device visible (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(PMDI_E_DEVICE, "device %d not in 0..%d", device, ndev - 1);
+    HIP_TRY(hipSetDevice(device));
+    return PMDI_OK;
+}
+
+// what add_samples and merge check before S more samples go in; `missing`: a pointer the call needs is null
+int takes_more(const CountingAcc *a, bool missing, int64_t S)
+{
+    if (!a || missing) return fail(PMDI_E_ARG, "null argument");
+    if (S < 0) return fail(PMDI_E_ARG, "S=%lld < 0", (long long)S);
+    if (S > 2147483647LL - a->S) return fail(PMDI_E_ARG, "%lld + %lld samples overflow the int32 counts", (long long)a->S, (long long)S);
+    return PMDI_OK;
+}
+
+// what *_add_gibbs checks before it touches anything (pmdi_gibbs_run3 asks once, before its first iteration); noun: what the
+// messages call `a`
+int accepts(const CountingAcc *a, const char *noun, const pmdi_gibbs *g, int64_t n_adds)
+{
+    const pmdi_config &c = g->h->cfg;
+    if (c.K != a->K || c.n != a->n)
+        return fail(PMDI_E_ARG, "the %s holds K=%d n=%lld, the chains K=%d n=%lld", noun, a->K, a->n, c.K, (long long)c.n);
+    if (a->n_labels != 0 && c.N > a->n_labels) return fail(PMDI_E_ARG, "the chains use N=%d labels, the %s n_labels=%d", c.N, noun, a->n_labels);
+    if (c.device != a->device) return fail(PMDI_E_ARG, "the chains live on device %d, the %s on device %d", c.device, noun, a->device);
+    if (n_adds > (2147483647LL - a->S) / c.n_chains)
+        return fail(PMDI_E_ARG, "%lld + %lld x %d samples overflow the int32 counts", (long long)a->S, (long long)n_adds, c.n_chains);
+    return PMDI_OK;
+}
+
+// the chains' current labels as bytes in a->pack, [n_chains][K][n]
+int pack_labels(CountingAcc *a, const pmdi_gibbs *g, void *stream)
+{
+    const pmdi_config &c = g->h->cfg;
+    const size_t per = (size_t)c.n_chains * c.K * c.n;
+    HIP_TRY(hipSetDevice(a->device));
+    if (per > a->pack_bytes) {            // (first use, or a handle with more chains than the last one: the old buffer may still be read)
+        if (a->pack) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(a->pack); a->pack = nullptr; a->pack_bytes = 0; }
+        hipError_t e = hipMalloc((void **)&a->pack, per);
+        if (e != hipSuccess) { a->pack = nullptr; return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", per, hipGetErrorString(e)); }
+        a->pack_bytes = per;
+    }
+    hipError_t e = pmdi_launch_pack_samples(g->ga.s, a->pack, (long long)per, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "pack-samples launch: %s", hipGetErrorString(e));
+    return PMDI_OK;
+}
+
+// what pmdi_summary_add_gibbs checks before it touches anything (pmdi_gibbs_run2 asks once, before its first iteration)
+int summary_accepts(const pmdi_summary *a, const pmdi_gibbs *g, int64_t n_adds)
+{
+    const pmdi_config &c = g->h->cfg;
+    if (c.n_chains != a->C || c.K != a->K || c.N != a->N || c.n != a->n)
+        return fail(PMDI_E_ARG, "the accumulator holds n_chains=%d K=%d N=%d n=%lld, the chains n_chains=%d K=%d N=%d n=%lld", a->C, a->K, a->N,
+                    a->n, c.n_chains, c.K, c.N, (long long)c.n);
+    if (a->sumD != g->h->sumD && !(a->sumD == 0 && !g->feature_select))
+        return fail(PMDI_E_ARG, "the accumulator holds sumD=%lld, the chains sumD=%d", a->sumD, g->h->sumD);
+    if (c.device != a->device) return fail(PMDI_E_ARG, "the chains live on device %d, the accumulator on device %d", c.device, a->device);
+    if (n_adds > 2147483647LL - a->T) return fail(PMDI_E_ARG, "%lld + %lld adds pass INT32_MAX", (long long)a->T, (long long)n_adds);
+    return PMDI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pmdi_psm_acc_destroy(pmdi_psm_acc *a)
+{
+    if (!a) return PMDI_OK;
+    (void)hipSetDevice(a->device);
+    (void)hipDeviceSynchronize();
+    if (a->counts) (void)hipFree(a->counts);
+    if (a->pack) (void)hipFree(a->pack);
+    delete a;
+    return PMDI_OK;
+}
+
+int pmdi_psm_acc_create(int32_t device, int32_t K, int64_t n, int32_t n_labels, pmdi_psm_acc **out)
+{
+    if (!out) return fail(PMDI_E_ARG, "null argument");
+    *out = nullptr;
+    if (K < 1 || K > PMDI_KMAX_I) return fail(PMDI_E_ARG, "K=%d outside 1..%d", K, PMDI_KMAX_I);
+    if (n < 1 || n > 65535) return fail(PMDI_E_ARG, "n=%lld outside 1..65535", (long long)n);
+    if (n_labels < 0 || n_labels > 255) return fail(PMDI_E_ARG, "n_labels=%d outside 0..255", n_labels);
+    if (const int rc = open_device(device)) return rc;
+    pmdi_psm_acc *a = new (std::nothrow) pmdi_psm_acc();
+    if (!a) return fail(PMDI_E_MEMORY, "out of host memory");
+    a->device = device; a->K = K; a->n = n; a->n_labels = n_labels;
+    const size_t bytes = (size_t)K * n * n * 4;
+    hipError_t e = hipMalloc((void **)&a->counts, bytes);
+    if (e != hipSuccess) { a->counts = nullptr; pmdi_psm_acc_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e)); }
+    if (hipMemset(a->counts, 0, bytes) != hipSuccess) { pmdi_psm_acc_destroy(a); return fail(PMDI_E_DEVICE, "hipMemset failed"); }
+    *out = a;
+    return PMDI_OK;
+}
+
+int pmdi_psm_acc_reset(pmdi_psm_acc *a, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipMemsetAsync(a->counts, 0, (size_t)a->K * a->n * a->n * 4, (hipStream_t)stream));
+    a->S = 0; a->dirty = false;
+    return PMDI_OK;
+}
+
+int pmdi_psm_acc_add_samples(pmdi_psm_acc *a, const uint8_t *samples, int64_t S, void *stream)
+{
+    if (const int rc = takes_more(a, !samples && S != 0, S)) return rc;
+    if (S == 0) return PMDI_OK;
+    HIP_TRY(hipSetDevice(a->device));
+    hipError_t e = pmdi_launch_psm_acc_add(samples, S, a->K, a->n, a->n_labels, a->counts, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "psm-accumulate launch: %s", hipGetErrorString(e));
+    a->S += S; a->dirty = true;
+    return PMDI_OK;
+}
+
+int pmdi_psm_acc_add_gibbs(pmdi_psm_acc *a, pmdi_gibbs *g, void *stream)
+{
+    if (!a || !g) return fail(PMDI_E_ARG, "null argument");
+    int rc;
+    if ((rc = accepts(a, "accumulator", g, 1)) || (rc = pack_labels(a, g, stream))) return rc;
+    return pmdi_psm_acc_add_samples(a, a->pack, g->h->cfg.n_chains, stream);
+}
+
+int pmdi_psm_acc_merge(pmdi_psm_acc *a, const int32_t *counts, int64_t S, void *stream)
+{
+    if (const int rc = takes_more(a, !counts, S)) return rc;
+    HIP_TRY(hipSetDevice(a->device));
+    hipError_t e = pmdi_launch_psm_acc_merge(a->counts, counts, a->K, a->n, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "psm-merge launch: %s", hipGetErrorString(e));
+    a->S += S; a->dirty = true;
+    return PMDI_OK;
+}
+
+int64_t pmdi_psm_acc_samples(const pmdi_psm_acc *a) { return a ? a->S : 0; }
+
+int pmdi_psm_acc_counts(pmdi_psm_acc *a, const int32_t **counts, int64_t *S, void *stream)
+{
+    if (!a || !counts) return fail(PMDI_E_ARG, "null argument");
+    if (a->dirty) {
+        HIP_TRY(hipSetDevice(a->device));
+        hipError_t e = pmdi_launch_psm_acc_mirror(a->counts, a->K, a->n, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(PMDI_E_DEVICE, "psm-mirror launch: %s", hipGetErrorString(e));
+        a->dirty = false;
+    }
+    *counts = a->counts;
+    if (S) *S = a->S;
+    return PMDI_OK;
+}
+
+int pmdi_fusion_destroy(pmdi_fusion *a)
+{
+    if (!a) return PMDI_OK;
+    (void)hipSetDevice(a->device);
+    (void)hipDeviceSynchronize();
+    if (a->counts) (void)hipFree(a->counts);
+    if (a->fused) (void)hipFree(a->fused);
+    if (a->d_masks) (void)hipFree(a->d_masks);
+    if (a->pack) (void)hipFree(a->pack);
+    delete a;
+    return PMDI_OK;
+}
+
+int pmdi_fusion_create(int32_t device, int32_t K, int64_t n, int32_t n_labels, int32_t n_groups, const uint8_t *group_masks,
+                       int32_t with_matrix, pmdi_fusion **out)
+{
+    if (!out) return fail(PMDI_E_ARG, "null argument");
+    *out = nullptr;
+    if (K < 2 || K > PMDI_KMAX_I) return fail(PMDI_E_ARG, "K=%d outside 2..%d (a group is two or more datasets)", K, PMDI_KMAX_I);
+    if (n < 1 || n > 65535) return fail(PMDI_E_ARG, "n=%lld outside 1..65535", (long long)n);
+    if (n_labels < 0 || n_labels > 255) return fail(PMDI_E_ARG, "n_labels=%d outside 0..255", n_labels);
+    unsigned char masks[256] = {};
+    int G = 0;
+    if (group_masks) {
+        if (n_groups < 1 || n_groups > 247) return fail(PMDI_E_ARG, "n_groups=%d outside 1..247", n_groups);
+        bool seen[256] = {};
+        for (int g = 0; g < n_groups; ++g) {
+            const unsigned m = group_masks[g];
+            if (__builtin_popcount(m) < 2) return fail(PMDI_E_ARG, "group %d (mask 0x%02x) has fewer than two datasets", g, m);
+            if (m >> K) return fail(PMDI_E_ARG, "group %d (mask 0x%02x) names a dataset >= K=%d", g, m, K);
+            if (seen[m]) return fail(PMDI_E_ARG, "group %d (mask 0x%02x) is given twice", g, m);
+            seen[m] = true;
+            masks[G++] = (unsigned char)m;
+        }
+    } else {                                  // all pairs in the order of Phi: (0,1), (0,2), ..., (K-2,K-1)
+        for (int k1 = 0; k1 < K - 1; ++k1)
+            for (int k2 = k1 + 1; k2 < K; ++k2) masks[G++] = (unsigned char)((1u << k1) | (1u << k2));
+    }
+    if (const int rc = open_device(device)) return rc;
+    pmdi_fusion *a = new (std::nothrow) pmdi_fusion();
+    if (!a) return fail(PMDI_E_MEMORY, "out of host memory");
+    a->device = device; a->K = K; a->n = n; a->n_labels = n_labels; a->G = G; a->with_matrix = with_matrix != 0;
+    memcpy(a->masks, masks, sizeof(masks));
+    for (int c = 0, at = 0; c < 3; ++c)
+        for (int g = 0; g < G; ++g) {
+            const int members = __builtin_popcount(masks[g]);
+            if ((members > 2) + (members > 4) == c) { a->order[at++] = (unsigned char)g; ++a->n_class[c]; }
+        }
+    const size_t cbytes = a->with_matrix ? (size_t)G * n * n * 4 : 0, fbytes = (size_t)G * n * 4;
+    hipError_t e = hipSuccess;
+    size_t want = cbytes;
+    if (cbytes) e = hipMalloc((void **)&a->counts, cbytes);
+    if (e != hipSuccess) a->counts = nullptr;
+    if (e == hipSuccess) { want = fbytes; e = hipMalloc((void **)&a->fused, fbytes); if (e != hipSuccess) a->fused = nullptr; }
+    if (e == hipSuccess) { want = 512; e = hipMalloc((void **)&a->d_masks, 512); if (e != hipSuccess) a->d_masks = nullptr; }
+    if (e != hipSuccess) { pmdi_fusion_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", want, hipGetErrorString(e)); }
+    if ((cbytes && hipMemset(a->counts, 0, cbytes) != hipSuccess) || hipMemset(a->fused, 0, fbytes) != hipSuccess ||
+        hipMemcpy(a->d_masks, a->masks, 256, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(a->d_masks + 256, a->order, 256, hipMemcpyHostToDevice) != hipSuccess) {
+        pmdi_fusion_destroy(a);
+        return fail(PMDI_E_DEVICE, "hipMemset / hipMemcpy failed");
+    }
+    *out = a;
+    return PMDI_OK;
+}
+
+int pmdi_fusion_reset(pmdi_fusion *a, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    if (a->counts) HIP_TRY(hipMemsetAsync(a->counts, 0, (size_t)a->G * a->n * a->n * 4, (hipStream_t)stream));
+    HIP_TRY(hipMemsetAsync(a->fused, 0, (size_t)a->G * a->n * 4, (hipStream_t)stream));
+    a->S = 0; a->dirty = false;
+    return PMDI_OK;
+}
+
+int pmdi_fusion_add_samples(pmdi_fusion *a, const uint8_t *samples, int64_t S, void *stream)
+{
+    if (const int rc = takes_more(a, !samples && S != 0, S)) return rc;
+    if (S == 0) return PMDI_OK;
+    HIP_TRY(hipSetDevice(a->device));
+    hipError_t e = a->with_matrix ? pmdi_launch_fusion_add(samples, S, a->K, a->n, a->n_labels, a->d_masks, a->d_masks + 256, a->n_class, a->counts, (hipStream_t)stream)
+                                  : pmdi_launch_fusion_obs(samples, S, a->K, a->n, a->d_masks, a->G, a->fused, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "fusion-accumulate launch: %s", hipGetErrorString(e));
+    a->S += S; a->dirty = a->with_matrix;
+    return PMDI_OK;
+}
+
+int pmdi_fusion_add_gibbs(pmdi_fusion *a, pmdi_gibbs *g, void *stream)
+{
+    if (!a || !g) return fail(PMDI_E_ARG, "null argument");
+    int rc;
+    if ((rc = accepts(a, "fusion accumulator", g, 1)) || (rc = pack_labels(a, g, stream))) return rc;
+    return pmdi_fusion_add_samples(a, a->pack, g->h->cfg.n_chains, stream);
+}
+
+int pmdi_fusion_merge(pmdi_fusion *a, const int32_t *fused, const int32_t *counts, int64_t S, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    if (a->with_matrix ? !counts : (!fused || counts))
+        return fail(PMDI_E_ARG, a->with_matrix ? "an accumulator with matrices merges counts" : "an accumulator without matrices merges fused, and no counts");
+    if (const int rc = takes_more(a, false, S)) return rc;
+    HIP_TRY(hipSetDevice(a->device));
+    hipError_t e = a->with_matrix ? pmdi_launch_psm_acc_merge(a->counts, counts, a->G, a->n, (hipStream_t)stream)      // (fused is its diagonal)
+                                  : pmdi_launch_fusion_merge_obs(a->fused, fused, a->G, a->n, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "fusion-merge launch: %s", hipGetErrorString(e));
+    a->S += S; a->dirty = a->with_matrix;
+    return PMDI_OK;
+}
+
+int64_t pmdi_fusion_samples(const pmdi_fusion *a) { return a ? a->S : 0; }
+
+int pmdi_fusion_groups(const pmdi_fusion *a, int32_t *n_groups, uint8_t *masks)
+{
+    if (!a || !n_groups) return fail(PMDI_E_ARG, "null argument");
+    *n_groups = a->G;
+    if (masks) memcpy(masks, a->masks, (size_t)a->G);
+    return PMDI_OK;
+}
+
+int pmdi_fusion_counts(pmdi_fusion *a, const int32_t **fused, const int32_t **counts, int64_t *S, void *stream)
+{
+    if (!a || !fused) return fail(PMDI_E_ARG, "null argument");
+    if (a->dirty) {
+        HIP_TRY(hipSetDevice(a->device));
+        hipError_t e = pmdi_launch_psm_acc_mirror(a->counts, a->G, a->n, (hipStream_t)stream);
+        if (e == hipSuccess) e = pmdi_launch_fusion_diag(a->counts, a->G, a->n, a->fused, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(PMDI_E_DEVICE, "fusion-mirror launch: %s", hipGetErrorString(e));
+        a->dirty = false;
+    }
+    *fused = a->fused;
+    if (counts) *counts = a->counts;
+    if (S) *S = a->S;
+    return PMDI_OK;
+}
+
+int pmdi_summary_destroy(pmdi_summary *a)
+{
+    if (!a) return PMDI_OK;
+    (void)hipSetDevice(a->device);
+    (void)hipDeviceSynchronize();
+    if (a->slab) (void)hipFree(a->slab);
+    delete a;
+    return PMDI_OK;
+}
+
+int pmdi_summary_create(int32_t device, int32_t n_chains, int32_t K, int32_t N, int64_t n, int64_t sumD, int64_t trace_cap,
+                        pmdi_summary **out)
+{
+    if (!out) return fail(PMDI_E_ARG, "null argument");
+    *out = nullptr;
+    if (K < 1 || K > PMDI_KMAX_I) return fail(PMDI_E_ARG, "K=%d outside 1..%d", K, PMDI_KMAX_I);
+    if (N < 2 || N > 255) return fail(PMDI_E_ARG, "N=%d outside 2..255", N);
+    if (n < 1) return fail(PMDI_E_ARG, "n=%lld < 1", (long long)n);
+    if (n_chains < 1 || (long long)n_chains * K > 2147483647LL) return fail(PMDI_E_ARG, "n_chains=%d: need n_chains >= 1 and n_chains * K <= INT32_MAX", n_chains);
+    if (sumD < 0) return fail(PMDI_E_ARG, "sumD=%lld < 0", (long long)sumD);
+    if (trace_cap < 0 || trace_cap > 2147483647LL) return fail(PMDI_E_ARG, "trace_cap=%lld outside 0..INT32_MAX (the bound of the number of adds)", (long long)trace_cap);
+    if (const int rc = open_device(device)) return rc;
+    pmdi_summary *a = new (std::nothrow) pmdi_summary();
+    if (!a) return fail(PMDI_E_MEMORY, "out of host memory");
+    a->device = device; a->C = n_chains; a->K = K; a->N = N; a->npairs = K * (K - 1) / 2; a->n = n; a->sumD = sumD; a->trace_cap = trace_cap;
+    const size_t CK = (size_t)n_chains * K, CP = (size_t)n_chains * a->npairs;
+    // 8-byte elements: the arrays in the order of SUM_*, then err; then nclust (int)
+    const size_t counts[SUM_ARRAYS] = {(size_t)K * (N + 1), CK, CK, CK, CK, CP, CP, (size_t)sumD, (size_t)trace_cap * K, (size_t)trace_cap * K,
+                                       (size_t)trace_cap * a->npairs};
+    long double total = 1.0L + (long double)CK;
+    for (size_t c : counts) total += (long double)c;
+    if (total * 8.0L > 4.0e18L) { delete a; return fail(PMDI_E_MEMORY, "the accumulator would need more than 4e18 bytes"); }
+    a->state_bytes = 8;
+    for (int i = 0; i < SUM_ARRAYS; ++i) { a->count[i] = counts[i]; a->state_bytes += counts[i] * 8; }
+    const size_t bytes = a->state_bytes + CK * 4;
+    hipError_t e = hipMalloc((void **)&a->slab, bytes);
+    if (e != hipSuccess) { a->slab = nullptr; pmdi_summary_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e)); }
+    if (hipMemset(a->slab, 0, bytes) != hipSuccess) { pmdi_summary_destroy(a); return fail(PMDI_E_DEVICE, "hipMemset failed"); }
+    char *p = a->slab;
+    for (int i = 0; i < SUM_ARRAYS; ++i) { a->at[i] = p; p += a->count[i] * 8; }
+    a->err = (int *)p; a->nclust = (int *)(a->slab + a->state_bytes);
+    *out = a;
+    return PMDI_OK;
+}
+
+int pmdi_summary_reset(pmdi_summary *a, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipMemsetAsync(a->slab, 0, a->state_bytes, (hipStream_t)stream));
+    a->T = 0;
+    return PMDI_OK;
+}
+
+int pmdi_summary_add_arrays(pmdi_summary *a, const int32_t *s, const double *M, const double *Phi, const uint8_t *flags, void *stream)
+{
+    if (!a || !s || !M || (!Phi && a->npairs > 0)) return fail(PMDI_E_ARG, "null argument");
+    if (a->T >= 2147483647LL) return fail(PMDI_E_ARG, "%lld + 1 adds pass INT32_MAX", (long long)a->T);
+    HIP_TRY(hipSetDevice(a->device));
+    SummaryArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.C = a->C; sa.K = a->K; sa.N = a->N; sa.npairs = a->npairs; sa.phi_stride = a->npairs > 0 ? a->npairs : 1;
+    sa.n = a->n; sa.sumD = a->sumD;
+    sa.s = s; sa.M = M; sa.Phi = Phi; sa.flags = flags;
+    auto i64 = [a](int i) { return (long long *)a->at[i]; };
+    auto f64 = [a](int i) { return (double *)a->at[i]; };
+    sa.nclust = a->nclust; sa.err = a->err; sa.hist = i64(SUM_HIST); sa.nclust_sum = i64(SUM_NSUM); sa.nclust_sumsq = i64(SUM_NSUMSQ);
+    sa.M_mean = f64(SUM_M_MEAN); sa.M_m2 = f64(SUM_M_M2); sa.Phi_mean = f64(SUM_PHI_MEAN); sa.Phi_m2 = f64(SUM_PHI_M2);
+    sa.flag_count = i64(SUM_FLAG_COUNT);
+    if (a->T < a->trace_cap) {
+        sa.tr_nclust = i64(SUM_TR_NCLUST) + (size_t)a->T * a->K; sa.tr_M = f64(SUM_TR_M) + (size_t)a->T * a->K;
+        sa.tr_Phi = f64(SUM_TR_PHI) + (size_t)a->T * a->npairs;
+    }
+    hipError_t e = pmdi_launch_summary_add(sa, (long long)a->T + 1, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "summary-add launch: %s", hipGetErrorString(e));
+    a->T += 1;
+    return PMDI_OK;
+}
+
+int pmdi_summary_add_gibbs(pmdi_summary *a, pmdi_gibbs *g, void *stream)
+{
+    if (!a || !g) return fail(PMDI_E_ARG, "null argument");
+    const int rc = summary_accepts(a, g, 1);
+    if (rc) return rc;
+    return pmdi_summary_add_arrays(a, g->ga.s, g->ga.M, g->ga.Phi, (g->feature_select && a->sumD > 0) ? g->flags : nullptr, stream);
+}
+
+int64_t pmdi_summary_samples(const pmdi_summary *a) { return a ? a->T : 0; }
+
+int pmdi_summary_get(pmdi_summary *a, int64_t *nclust_hist, int64_t *nclust_sum, int64_t *nclust_sumsq, double *M_mean, double *M_m2,
+                     double *Phi_mean, double *Phi_m2, int64_t *flag_count, int64_t *trace_nclust, double *trace_M, double *trace_Phi,
+                     void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    hipStream_t st = (hipStream_t)stream;
+    int err = 0;
+    void *const dst[SUM_ARRAYS] = {nclust_hist, nclust_sum, nclust_sumsq, M_mean, M_m2, Phi_mean, Phi_m2, flag_count, trace_nclust, trace_M, trace_Phi};
+    for (int i = 0; i < SUM_ARRAYS; ++i)
+        if (dst[i] && a->count[i]) HIP_TRY(hipMemcpyAsync(dst[i], a->at[i], a->count[i] * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&err, a->err, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (err) return fail(PMDI_E_DATA, "a label outside 0..%d was added (pmdi_summary_add_arrays); pmdi_summary_reset clears the accumulator", a->N - 1);
+    return PMDI_OK;
+}
+
+int pmdi_gibbs_run3(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
+                    void *stream)
+{
+    if (!g || n_iter < 0) return fail(PMDI_E_ARG, "bad argument");
+    if (burnin < 0 || thin < 1) return fail(PMDI_E_ARG, "burnin=%lld must be >= 0 and thin=%lld >= 1", (long long)burnin, (long long)thin);
+    const int64_t kept = n_iter > burnin ? (n_iter - burnin - 1) / thin + 1 : 0;
+    int rc;
+    if (acc && (rc = accepts(acc, "accumulator", g, kept))) return rc;
+    if (summ && (rc = summary_accepts(summ, g, kept))) return rc;
+    if (fus && (rc = accepts(fus, "fusion accumulator", g, kept))) return rc;
+    for (int64_t t = 1; t <= n_iter; ++t) {
+        if ((rc = pmdi_gibbs_step(g, PMDI_STEP_BEGIN, stream)) || (rc = pmdi_gibbs_step(g, PMDI_STEP_HYPERS, stream)) ||
+            (rc = pmdi_gibbs_step(g, PMDI_STEP_SWEEP, stream)))
+            return rc;
+        if (g->feature_select && (rc = pmdi_gibbs_step(g, PMDI_STEP_FEATSEL, stream))) return rc;
+        if ((rc = pmdi_gibbs_step(g, PMDI_STEP_ALIGN, stream))) return rc;
+        if (t > burnin && (t - burnin - 1) % thin == 0) {
+            if (acc && (rc = pmdi_psm_acc_add_gibbs(acc, g, stream))) return rc;
+            if (summ && (rc = pmdi_summary_add_gibbs(summ, g, stream))) return rc;
+            if (fus && (rc = pmdi_fusion_add_gibbs(fus, g, stream))) return rc;
+        }
+    }
+    return PMDI_OK;
+}
+
+int pmdi_gibbs_run2(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, void *stream)
+{
+    return pmdi_gibbs_run3(g, n_iter, burnin, thin, acc, summ, nullptr, stream);
+}
+
+int pmdi_gibbs_run(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, void *stream)
+{
+    return pmdi_gibbs_run2(g, n_iter, burnin, thin, acc, nullptr, stream);
+}
+
+}  // extern "C"

@@ -3,8 +3,7 @@
 // boundary, owns device memory, builds the exact-arithmetic lookup tables and
 // launches the kernels of pmdi_kernels.hip.  No CPU fallback exists: every
 // compute entry point runs on the gfx950 device or fails.
-#include "pmdi_internal.h"
-#include "../../include/pmdi_hip.h"
+#include "pmdi_host.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -24,23 +23,6 @@ namespace {
 
 thread_local char g_err[512] = "";
 
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                  \
-    do {                                                                               \
-        hipError_t e__ = (expr);                                                       \
-        if (e__ != hipSuccess)                                                         \
-            return fail(e__ == hipErrorOutOfMemory ? PMDI_E_MEMORY : PMDI_E_DEVICE,    \
-                        "%s: %s", #expr, hipGetErrorString(e__));                      \
-    } while (0)
-
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // the device generator (pmdi_device.h uniform01) on the host: Philox4x32-10, ctr = (p, pos, site<<16|k, iter)
@@ -58,28 +40,6 @@ double host_uniform01(unsigned long long seed, unsigned iter, unsigned pos, unsi
     const unsigned long long m = ((unsigned long long)(c0 >> 6) << 26) | (unsigned long long)(c1 >> 6);
     return (double)(2 * m + 1) * (1.0 / 9007199254740992.0);
 }
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    int ensure(size_t b)
-    {
-        if (b <= bytes && p) return 0;
-        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
-        if (b == 0) b = 16;
-        hipError_t e = hipMalloc(&p, b);
-        if (e != hipSuccess) { p = nullptr; return fail(PMDI_E_MEMORY, "hipMalloc(%zu): %s", b, hipGetErrorString(e)); }
-        bytes = b;
-        return 0;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-};
-
-// device memory of one call, freed on return
-struct Scratch {
-    void *p = nullptr;
-    ~Scratch() { if (p) (void)hipFree(p); }
-};
 
 // the divisor of the `which` matrix of counts (pmdi_psm_*_device): S, or S K for the Overall one
 unsigned __int128 psm_divisor(int64_t S, int32_t K, int32_t which) { return (unsigned __int128)S * (unsigned)(which == K ? K : 1); }
@@ -124,7 +84,7 @@ size_t layout_arena(DsetDev &d, int N, int P, long long cap, long long n_rows_ss
 
 }  // namespace
 
-// error reporting for the other translation units of the library (pmdi_csv.cpp, pmdi_comm.cpp)
+// error reporting of every translation unit of the library (declared in pmdi_host.h)
 int pmdi_set_error(int code, const char *fmt, ...)
 {
     va_list ap;
@@ -149,120 +109,12 @@ int pmdi_psm_shared_args(const char *who, int64_t S, int32_t K, int64_t n, int32
     return PMDI_OK;
 }
 
-struct pmdi_handle {
-    pmdi_config cfg{};
-    pmdi_tuning tun{};           // the creator's knobs (a copy: cfg.tuning is not kept), -1 = automatic
-    int T = 0;
-    long long cap = 0;
-    int Dmax = 0, sumD = 0, npairs = 1;
-    int terms_cap = 0, pid_lds = 0, pp_lds = 0, col_lds = 0, two_per_cu = 0;
-    // light group (block_threads == 0 only): chains whose last sweep met few live clusters per step are
-    // swept by 256-thread workgroups on a second stream, concurrently with the wide workgroups of the rest
-    bool split = false;
-    int l_terms_cap = 0, l_pid_lds = 0, l_pp_lds = 0, l_col_lds = 0;
-    int r_terms_cap = 0, r_pid_lds = 0, r_pp_lds = 0, r_col_lds = 0;     // the general kernel's LDS layout at the settled-chain kernel's workgroup width (hand-over in place)
-    long long light_ids = 0;
-    hipStream_t stream2 = nullptr, stream3 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join3 = nullptr;
-    unsigned *start_sig = nullptr;   // signal memory: workgroups of the heaviest-chains launch that have started (hipStreamWaitValue32)
-    int very_heavy = 0;          // the first `very_heavy` heavy chains of the launch order get a CU each (256-register build)
-    bool phase_on = false;
-    hipStream_t stream = nullptr;
-    DsetDev ds[PMDI_KMAX_I]{};
-    std::vector<void *> owned;          // device allocations freed in destroy
-    // per-call staging (device)
-    DevBuf d_s_in, d_order, d_Pi, d_logphi, d_flags, d_s_out, d_lw, d_pstar, d_stats, d_err, d_trace;
-    DevBuf d_swept_by, d_resume;
-    bool s2_continue = true;     // a chain the settled-chain kernel gives back is carried on by the general kernel at that observation
-                                 // (false: swept again from the start -- the round-3 behaviour, kept for A/B runs)
-    DevBuf d_usc, d_partstar, d_kstate, d_phase, d_args, d_args2, d_args3, d_args4, d_args5, d_requeue, d_requeue_total, d_handed, d_group, d_cost, d_lorder, d_ticket, d_work, d_anclog, d_evpos, d_xcnt, d_xinc, d_xlab, d_xhdr;
-    int ksplit = 0;
-    int ksplit_batch = 0;        // split mode: chain slots per launch when n_chains * K workgroups are not resident at once (0 = one launch)
-    bool have_order = false;
-    // argument blocks travel through a ring of pinned host slots: the stream-ordered copy is then asynchronous for the host too
-    static constexpr int RING = 64;
-    SweepArgs *ring = nullptr;
-    hipEvent_t ring_ev[RING] = {};
-    bool ring_used[RING] = {};
-    int ring_head = 0;
-    // settled-chain kernel (pmdi_sweep2.hip): takes the light group of a sweep when the configuration is one it is built for
-    bool s2_ok = false;
-    S2Layout s2{};
-    int sweep_no = 0;
-    int sticky = 3;              // sweeps a chain stays with the general kernel after the settled-chain kernel gave it back (PMDI_STICKY)
-    int err_keep = 0;            // set by the device-resident driver around its sweeps (pmdi_gibbs_step)
-    int children = 0;            // live pmdi_gibbs / cluster-batch objects: pmdi_destroy refuses while > 0
-    // feature selection
-    DevBuf d_traj, d_lm, d_firstpos, d_fnull, d_fflags, d_fprob;
-    bool swept = false;
-    long long last_n1 = 0;
-};
-
 struct pmdi_cluster_batch {
     pmdi_handle *h = nullptr;
     int k = 0, B = 0;
     DsetDev d{};
     void *arena = nullptr;
     DevBuf d_rows, d_flags, d_out;
-};
-
-// Device-resident Gibbs state of every chain of a handle (pmdi_gibbs_* entry points)
-struct pmdi_gibbs {
-    pmdi_handle *h = nullptr;
-    int device = 0;                      // (cached: destroy must not have to look at the handle)
-    GibbsArgs ga{};
-    int *s_next = nullptr;               // the sweep's output; exchanged with ga.s after every sweep
-    unsigned char *flags = nullptr;      // [chain][sumD] featureFlag
-    double *fprob = nullptr;             // [chain][sumD] featureProb of the last feature selection
-    double *lw = nullptr;                // [chain][P]
-    int *pstar = nullptr;                // [chain]
-    long long *stats = nullptr;          // [chain][8]
-    int *err = nullptr;                  // [chain]
-    long long n1 = 0;
-    int feature_select = 0;
-    int64_t iter = 0;                    // Gibbs iterations done
-    std::vector<void *> owned;
-};
-
-// Streaming PSM accumulator (pmdi_psm_acc_* entry points)
-struct pmdi_psm_acc {
-    int device = 0, K = 0, n_labels = 0;
-    long long n = 0;
-    int *counts = nullptr;               // [K][n][n]; the strict upper triangle is current only while !dirty
-    unsigned char *pack = nullptr;       // [n_chains][K][n] label bytes of pmdi_psm_acc_add_gibbs, allocated at first use
-    size_t pack_bytes = 0;
-    int64_t S = 0;                       // samples behind the counts
-    bool dirty = false;                  // something was added since the last mirror
-};
-
-// Streaming summary accumulator (pmdi_summary_* entry points): one device slab, the arrays of include/pmdi_hip.h one after
-// the other (8-byte elements), then the error flag and the per-add scratch
-struct pmdi_summary {
-    int device = 0, C = 0, K = 0, N = 0, npairs = 0;
-    long long n = 0, sumD = 0, trace_cap = 0;
-    char *slab = nullptr;
-    size_t state_bytes = 0;              // what reset zeroes: every array and the error flag
-    long long *hist = nullptr, *nsum = nullptr, *nsumsq = nullptr, *flag_count = nullptr, *tr_nclust = nullptr;
-    double *M_mean = nullptr, *M_m2 = nullptr, *Phi_mean = nullptr, *Phi_m2 = nullptr, *tr_M = nullptr, *tr_Phi = nullptr;
-    int *err = nullptr, *nclust = nullptr;
-    int64_t T = 0;                       // adds so far
-};
-
-// Streaming fusion accumulator (pmdi_fusion_* entry points)
-struct pmdi_fusion {
-    int device = 0, K = 0, n_labels = 0, G = 0;
-    long long n = 0;
-    bool with_matrix = false;
-    unsigned char masks[256] = {};       // [G] bit sets of datasets (at most 247 sets of two or more of 8)
-    unsigned char order[256] = {};       // [G] the groups sorted by class: 2 members, 3..4, 5..8 (the counting kernels' builds)
-    int n_class[3] = {};                 // groups per class
-    unsigned char *d_masks = nullptr;    // masks, then order, on the device: 2 x 256 bytes
-    int *counts = nullptr;               // [G][n][n], or null without matrices; the strict upper triangle is current only while !dirty
-    int *fused = nullptr;                // [G][n]; with matrices: the diagonals, current only while !dirty
-    unsigned char *pack = nullptr;       // [n_chains][K][n] label bytes of pmdi_fusion_add_gibbs, allocated at first use
-    size_t pack_bytes = 0;
-    int64_t S = 0;                       // samples behind the counts
-    bool dirty = false;                  // (with matrices) something was added since the last mirror
 };
 
 namespace {
@@ -1068,419 +920,6 @@ int pmdi_psm_refine_device(int32_t device, const int32_t *counts, int64_t S, int
     return PMDI_OK;
 }
 
-int pmdi_psm_acc_destroy(pmdi_psm_acc *a)
-{
-    if (!a) return PMDI_OK;
-    (void)hipSetDevice(a->device);
-    (void)hipDeviceSynchronize();
-    if (a->counts) (void)hipFree(a->counts);
-    if (a->pack) (void)hipFree(a->pack);
-    delete a;
-    return PMDI_OK;
-}
-
-int pmdi_psm_acc_create(int32_t device, int32_t K, int64_t n, int32_t n_labels, pmdi_psm_acc **out)
-{
-    if (!out) return fail(PMDI_E_ARG, "null argument");
-    *out = nullptr;
-    if (K < 1 || K > PMDI_KMAX_I) return fail(PMDI_E_ARG, "K=%d outside 1..%d", K, PMDI_KMAX_I);
-    if (n < 1 || n > 65535) return fail(PMDI_E_ARG, "n=%lld outside 1..65535", (long long)n);
-    if (n_labels < 0 || n_labels > 255) return fail(PMDI_E_ARG, "n_labels=%d outside 0..255", n_labels);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(PMDI_E_DEVICE, "no HIP device visible (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(PMDI_E_DEVICE, "device %d not in 0..%d", device, ndev - 1);
-    HIP_TRY(hipSetDevice(device));
-    pmdi_psm_acc *a = new (std::nothrow) pmdi_psm_acc();
-    if (!a) return fail(PMDI_E_MEMORY, "out of host memory");
-    a->device = device; a->K = K; a->n = n; a->n_labels = n_labels;
-    const size_t bytes = (size_t)K * n * n * 4;
-    hipError_t e = hipMalloc((void **)&a->counts, bytes);
-    if (e != hipSuccess) { a->counts = nullptr; pmdi_psm_acc_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e)); }
-    if (hipMemset(a->counts, 0, bytes) != hipSuccess) { pmdi_psm_acc_destroy(a); return fail(PMDI_E_DEVICE, "hipMemset failed"); }
-    *out = a;
-    return PMDI_OK;
-}
-
-int pmdi_psm_acc_reset(pmdi_psm_acc *a, void *stream)
-{
-    if (!a) return fail(PMDI_E_ARG, "null argument");
-    HIP_TRY(hipSetDevice(a->device));
-    HIP_TRY(hipMemsetAsync(a->counts, 0, (size_t)a->K * a->n * a->n * 4, (hipStream_t)stream));
-    a->S = 0; a->dirty = false;
-    return PMDI_OK;
-}
-
-int pmdi_psm_acc_add_samples(pmdi_psm_acc *a, const uint8_t *samples, int64_t S, void *stream)
-{
-    if (!a || (!samples && S != 0)) return fail(PMDI_E_ARG, "null argument");
-    if (S < 0) return fail(PMDI_E_ARG, "S=%lld < 0", (long long)S);
-    if (S > 2147483647LL - a->S) return fail(PMDI_E_ARG, "%lld + %lld samples overflow the int32 counts", (long long)a->S, (long long)S);
-    if (S == 0) return PMDI_OK;
-    HIP_TRY(hipSetDevice(a->device));
-    hipError_t e = pmdi_launch_psm_acc_add(samples, S, a->K, a->n, a->n_labels, a->counts, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "psm-accumulate launch: %s", hipGetErrorString(e));
-    a->S += S; a->dirty = true;
-    return PMDI_OK;
-}
-
-// what pmdi_psm_acc_add_gibbs checks before it touches anything (pmdi_gibbs_run asks once, before its first iteration)
-static int psm_acc_accepts(const pmdi_psm_acc *a, const pmdi_gibbs *g, int64_t n_adds)
-{
-    const pmdi_config &c = g->h->cfg;
-    if (c.K != a->K || c.n != a->n)
-        return fail(PMDI_E_ARG, "the accumulator holds K=%d n=%lld, the chains K=%d n=%lld", a->K, a->n, c.K, (long long)c.n);
-    if (a->n_labels != 0 && c.N > a->n_labels) return fail(PMDI_E_ARG, "the chains use N=%d labels, the accumulator n_labels=%d", c.N, a->n_labels);
-    if (c.device != a->device) return fail(PMDI_E_ARG, "the chains live on device %d, the accumulator on device %d", c.device, a->device);
-    if (n_adds > (2147483647LL - a->S) / c.n_chains)
-        return fail(PMDI_E_ARG, "%lld + %lld x %d samples overflow the int32 counts", (long long)a->S, (long long)n_adds, c.n_chains);
-    return PMDI_OK;
-}
-
-int pmdi_psm_acc_add_gibbs(pmdi_psm_acc *a, pmdi_gibbs *g, void *stream)
-{
-    if (!a || !g) return fail(PMDI_E_ARG, "null argument");
-    const int rc = psm_acc_accepts(a, g, 1);
-    if (rc) return rc;
-    const pmdi_config &c = g->h->cfg;
-    const size_t per = (size_t)c.n_chains * c.K * c.n;
-    HIP_TRY(hipSetDevice(a->device));
-    if (per > a->pack_bytes) {            // (first use, or a handle with more chains than the last one: the old buffer may still be read)
-        if (a->pack) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(a->pack); a->pack = nullptr; a->pack_bytes = 0; }
-        hipError_t e = hipMalloc((void **)&a->pack, per);
-        if (e != hipSuccess) { a->pack = nullptr; return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", per, hipGetErrorString(e)); }
-        a->pack_bytes = per;
-    }
-    hipError_t e = pmdi_launch_pack_samples(g->ga.s, a->pack, (long long)per, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "pack-samples launch: %s", hipGetErrorString(e));
-    return pmdi_psm_acc_add_samples(a, a->pack, c.n_chains, stream);
-}
-
-int pmdi_psm_acc_merge(pmdi_psm_acc *a, const int32_t *counts, int64_t S, void *stream)
-{
-    if (!a || !counts) return fail(PMDI_E_ARG, "null argument");
-    if (S < 0) return fail(PMDI_E_ARG, "S=%lld < 0", (long long)S);
-    if (S > 2147483647LL - a->S) return fail(PMDI_E_ARG, "%lld + %lld samples overflow the int32 counts", (long long)a->S, (long long)S);
-    HIP_TRY(hipSetDevice(a->device));
-    hipError_t e = pmdi_launch_psm_acc_merge(a->counts, counts, a->K, a->n, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "psm-merge launch: %s", hipGetErrorString(e));
-    a->S += S; a->dirty = true;
-    return PMDI_OK;
-}
-
-int64_t pmdi_psm_acc_samples(const pmdi_psm_acc *a) { return a ? a->S : 0; }
-
-int pmdi_psm_acc_counts(pmdi_psm_acc *a, const int32_t **counts, int64_t *S, void *stream)
-{
-    if (!a || !counts) return fail(PMDI_E_ARG, "null argument");
-    if (a->dirty) {
-        HIP_TRY(hipSetDevice(a->device));
-        hipError_t e = pmdi_launch_psm_acc_mirror(a->counts, a->K, a->n, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(PMDI_E_DEVICE, "psm-mirror launch: %s", hipGetErrorString(e));
-        a->dirty = false;
-    }
-    *counts = a->counts;
-    if (S) *S = a->S;
-    return PMDI_OK;
-}
-
-int pmdi_fusion_destroy(pmdi_fusion *a)
-{
-    if (!a) return PMDI_OK;
-    (void)hipSetDevice(a->device);
-    (void)hipDeviceSynchronize();
-    if (a->counts) (void)hipFree(a->counts);
-    if (a->fused) (void)hipFree(a->fused);
-    if (a->d_masks) (void)hipFree(a->d_masks);
-    if (a->pack) (void)hipFree(a->pack);
-    delete a;
-    return PMDI_OK;
-}
-
-int pmdi_fusion_create(int32_t device, int32_t K, int64_t n, int32_t n_labels, int32_t n_groups, const uint8_t *group_masks,
-                       int32_t with_matrix, pmdi_fusion **out)
-{
-    if (!out) return fail(PMDI_E_ARG, "null argument");
-    *out = nullptr;
-    if (K < 2 || K > PMDI_KMAX_I) return fail(PMDI_E_ARG, "K=%d outside 2..%d (a group is two or more datasets)", K, PMDI_KMAX_I);
-    if (n < 1 || n > 65535) return fail(PMDI_E_ARG, "n=%lld outside 1..65535", (long long)n);
-    if (n_labels < 0 || n_labels > 255) return fail(PMDI_E_ARG, "n_labels=%d outside 0..255", n_labels);
-    unsigned char masks[256] = {};
-    int G = 0;
-    if (group_masks) {
-        if (n_groups < 1 || n_groups > 247) return fail(PMDI_E_ARG, "n_groups=%d outside 1..247", n_groups);
-        bool seen[256] = {};
-        for (int g = 0; g < n_groups; ++g) {
-            const unsigned m = group_masks[g];
-            if (__builtin_popcount(m) < 2) return fail(PMDI_E_ARG, "group %d (mask 0x%02x) has fewer than two datasets", g, m);
-            if (m >> K) return fail(PMDI_E_ARG, "group %d (mask 0x%02x) names a dataset >= K=%d", g, m, K);
-            if (seen[m]) return fail(PMDI_E_ARG, "group %d (mask 0x%02x) is given twice", g, m);
-            seen[m] = true;
-            masks[G++] = (unsigned char)m;
-        }
-    } else {                                  // all pairs in the order of Phi: (0,1), (0,2), ..., (K-2,K-1)
-        for (int k1 = 0; k1 < K - 1; ++k1)
-            for (int k2 = k1 + 1; k2 < K; ++k2) masks[G++] = (unsigned char)((1u << k1) | (1u << k2));
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(PMDI_E_DEVICE, "no HIP device visible (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(PMDI_E_DEVICE, "device %d not in 0..%d", device, ndev - 1);
-    HIP_TRY(hipSetDevice(device));
-    pmdi_fusion *a = new (std::nothrow) pmdi_fusion();
-    if (!a) return fail(PMDI_E_MEMORY, "out of host memory");
-    a->device = device; a->K = K; a->n = n; a->n_labels = n_labels; a->G = G; a->with_matrix = with_matrix != 0;
-    memcpy(a->masks, masks, sizeof(masks));
-    for (int c = 0, at = 0; c < 3; ++c)
-        for (int g = 0; g < G; ++g) {
-            const int members = __builtin_popcount(masks[g]);
-            if ((members > 2) + (members > 4) == c) { a->order[at++] = (unsigned char)g; ++a->n_class[c]; }
-        }
-    const size_t cbytes = a->with_matrix ? (size_t)G * n * n * 4 : 0, fbytes = (size_t)G * n * 4;
-    hipError_t e = hipSuccess;
-    size_t want = cbytes;
-    if (cbytes) e = hipMalloc((void **)&a->counts, cbytes);
-    if (e != hipSuccess) a->counts = nullptr;
-    if (e == hipSuccess) { want = fbytes; e = hipMalloc((void **)&a->fused, fbytes); if (e != hipSuccess) a->fused = nullptr; }
-    if (e == hipSuccess) { want = 512; e = hipMalloc((void **)&a->d_masks, 512); if (e != hipSuccess) a->d_masks = nullptr; }
-    if (e != hipSuccess) { pmdi_fusion_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", want, hipGetErrorString(e)); }
-    if ((cbytes && hipMemset(a->counts, 0, cbytes) != hipSuccess) || hipMemset(a->fused, 0, fbytes) != hipSuccess ||
-        hipMemcpy(a->d_masks, a->masks, 256, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(a->d_masks + 256, a->order, 256, hipMemcpyHostToDevice) != hipSuccess) {
-        pmdi_fusion_destroy(a);
-        return fail(PMDI_E_DEVICE, "hipMemset / hipMemcpy failed");
-    }
-    *out = a;
-    return PMDI_OK;
-}
-
-int pmdi_fusion_reset(pmdi_fusion *a, void *stream)
-{
-    if (!a) return fail(PMDI_E_ARG, "null argument");
-    HIP_TRY(hipSetDevice(a->device));
-    if (a->counts) HIP_TRY(hipMemsetAsync(a->counts, 0, (size_t)a->G * a->n * a->n * 4, (hipStream_t)stream));
-    HIP_TRY(hipMemsetAsync(a->fused, 0, (size_t)a->G * a->n * 4, (hipStream_t)stream));
-    a->S = 0; a->dirty = false;
-    return PMDI_OK;
-}
-
-int pmdi_fusion_add_samples(pmdi_fusion *a, const uint8_t *samples, int64_t S, void *stream)
-{
-    if (!a || (!samples && S != 0)) return fail(PMDI_E_ARG, "null argument");
-    if (S < 0) return fail(PMDI_E_ARG, "S=%lld < 0", (long long)S);
-    if (S > 2147483647LL - a->S) return fail(PMDI_E_ARG, "%lld + %lld samples overflow the int32 counts", (long long)a->S, (long long)S);
-    if (S == 0) return PMDI_OK;
-    HIP_TRY(hipSetDevice(a->device));
-    hipError_t e = a->with_matrix ? pmdi_launch_fusion_add(samples, S, a->K, a->n, a->n_labels, a->d_masks, a->d_masks + 256, a->n_class, a->counts, (hipStream_t)stream)
-                                  : pmdi_launch_fusion_obs(samples, S, a->K, a->n, a->d_masks, a->G, a->fused, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "fusion-accumulate launch: %s", hipGetErrorString(e));
-    a->S += S; a->dirty = a->with_matrix;
-    return PMDI_OK;
-}
-
-// what pmdi_fusion_add_gibbs checks before it touches anything (pmdi_gibbs_run3 asks once, before its first iteration)
-static int fusion_accepts(const pmdi_fusion *a, const pmdi_gibbs *g, int64_t n_adds)
-{
-    const pmdi_config &c = g->h->cfg;
-    if (c.K != a->K || c.n != a->n)
-        return fail(PMDI_E_ARG, "the fusion accumulator holds K=%d n=%lld, the chains K=%d n=%lld", a->K, a->n, c.K, (long long)c.n);
-    if (a->n_labels != 0 && c.N > a->n_labels) return fail(PMDI_E_ARG, "the chains use N=%d labels, the fusion accumulator n_labels=%d", c.N, a->n_labels);
-    if (c.device != a->device) return fail(PMDI_E_ARG, "the chains live on device %d, the fusion accumulator on device %d", c.device, a->device);
-    if (n_adds > (2147483647LL - a->S) / c.n_chains)
-        return fail(PMDI_E_ARG, "%lld + %lld x %d samples overflow the int32 counts", (long long)a->S, (long long)n_adds, c.n_chains);
-    return PMDI_OK;
-}
-
-int pmdi_fusion_add_gibbs(pmdi_fusion *a, pmdi_gibbs *g, void *stream)
-{
-    if (!a || !g) return fail(PMDI_E_ARG, "null argument");
-    const int rc = fusion_accepts(a, g, 1);
-    if (rc) return rc;
-    const pmdi_config &c = g->h->cfg;
-    const size_t per = (size_t)c.n_chains * c.K * c.n;
-    HIP_TRY(hipSetDevice(a->device));
-    if (per > a->pack_bytes) {            // (first use, or a handle with more chains than the last one: the old buffer may still be read)
-        if (a->pack) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(a->pack); a->pack = nullptr; a->pack_bytes = 0; }
-        hipError_t e = hipMalloc((void **)&a->pack, per);
-        if (e != hipSuccess) { a->pack = nullptr; return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", per, hipGetErrorString(e)); }
-        a->pack_bytes = per;
-    }
-    hipError_t e = pmdi_launch_pack_samples(g->ga.s, a->pack, (long long)per, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "pack-samples launch: %s", hipGetErrorString(e));
-    return pmdi_fusion_add_samples(a, a->pack, c.n_chains, stream);
-}
-
-int pmdi_fusion_merge(pmdi_fusion *a, const int32_t *fused, const int32_t *counts, int64_t S, void *stream)
-{
-    if (!a) return fail(PMDI_E_ARG, "null argument");
-    if (a->with_matrix ? !counts : (!fused || counts))
-        return fail(PMDI_E_ARG, a->with_matrix ? "an accumulator with matrices merges counts" : "an accumulator without matrices merges fused, and no counts");
-    if (S < 0) return fail(PMDI_E_ARG, "S=%lld < 0", (long long)S);
-    if (S > 2147483647LL - a->S) return fail(PMDI_E_ARG, "%lld + %lld samples overflow the int32 counts", (long long)a->S, (long long)S);
-    HIP_TRY(hipSetDevice(a->device));
-    hipError_t e = a->with_matrix ? pmdi_launch_psm_acc_merge(a->counts, counts, a->G, a->n, (hipStream_t)stream)      // (fused is its diagonal)
-                                  : pmdi_launch_fusion_merge_obs(a->fused, fused, a->G, a->n, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "fusion-merge launch: %s", hipGetErrorString(e));
-    a->S += S; a->dirty = a->with_matrix;
-    return PMDI_OK;
-}
-
-int64_t pmdi_fusion_samples(const pmdi_fusion *a) { return a ? a->S : 0; }
-
-int pmdi_fusion_groups(const pmdi_fusion *a, int32_t *n_groups, uint8_t *masks)
-{
-    if (!a || !n_groups) return fail(PMDI_E_ARG, "null argument");
-    *n_groups = a->G;
-    if (masks) memcpy(masks, a->masks, (size_t)a->G);
-    return PMDI_OK;
-}
-
-int pmdi_fusion_counts(pmdi_fusion *a, const int32_t **fused, const int32_t **counts, int64_t *S, void *stream)
-{
-    if (!a || !fused) return fail(PMDI_E_ARG, "null argument");
-    if (a->dirty) {
-        HIP_TRY(hipSetDevice(a->device));
-        hipError_t e = pmdi_launch_psm_acc_mirror(a->counts, a->G, a->n, (hipStream_t)stream);
-        if (e == hipSuccess) e = pmdi_launch_fusion_diag(a->counts, a->G, a->n, a->fused, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(PMDI_E_DEVICE, "fusion-mirror launch: %s", hipGetErrorString(e));
-        a->dirty = false;
-    }
-    *fused = a->fused;
-    if (counts) *counts = a->counts;
-    if (S) *S = a->S;
-    return PMDI_OK;
-}
-
-int pmdi_summary_destroy(pmdi_summary *a)
-{
-    if (!a) return PMDI_OK;
-    (void)hipSetDevice(a->device);
-    (void)hipDeviceSynchronize();
-    if (a->slab) (void)hipFree(a->slab);
-    delete a;
-    return PMDI_OK;
-}
-
-int pmdi_summary_create(int32_t device, int32_t n_chains, int32_t K, int32_t N, int64_t n, int64_t sumD, int64_t trace_cap,
-                        pmdi_summary **out)
-{
-    if (!out) return fail(PMDI_E_ARG, "null argument");
-    *out = nullptr;
-    if (K < 1 || K > PMDI_KMAX_I) return fail(PMDI_E_ARG, "K=%d outside 1..%d", K, PMDI_KMAX_I);
-    if (N < 2 || N > 255) return fail(PMDI_E_ARG, "N=%d outside 2..255", N);
-    if (n < 1) return fail(PMDI_E_ARG, "n=%lld < 1", (long long)n);
-    if (n_chains < 1 || (long long)n_chains * K > 2147483647LL) return fail(PMDI_E_ARG, "n_chains=%d: need n_chains >= 1 and n_chains * K <= INT32_MAX", n_chains);
-    if (sumD < 0) return fail(PMDI_E_ARG, "sumD=%lld < 0", (long long)sumD);
-    if (trace_cap < 0 || trace_cap > 2147483647LL) return fail(PMDI_E_ARG, "trace_cap=%lld outside 0..INT32_MAX (the bound of the number of adds)", (long long)trace_cap);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(PMDI_E_DEVICE, "no HIP device visible (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(PMDI_E_DEVICE, "device %d not in 0..%d", device, ndev - 1);
-    HIP_TRY(hipSetDevice(device));
-    pmdi_summary *a = new (std::nothrow) pmdi_summary();
-    if (!a) return fail(PMDI_E_MEMORY, "out of host memory");
-    a->device = device; a->C = n_chains; a->K = K; a->N = N; a->npairs = K * (K - 1) / 2; a->n = n; a->sumD = sumD; a->trace_cap = trace_cap;
-    const size_t CK = (size_t)n_chains * K, CP = (size_t)n_chains * a->npairs;
-    // 8-byte elements: hist, nsum, nsumsq, M_mean, M_m2, Phi_mean, Phi_m2, flag_count, tr_nclust, tr_M, tr_Phi, err; then nclust (int)
-    const size_t counts[11] = {(size_t)K * (N + 1), CK, CK, CK, CK, CP, CP, (size_t)sumD, (size_t)trace_cap * K, (size_t)trace_cap * K,
-                               (size_t)trace_cap * a->npairs};
-    long double total = 1.0L + (long double)CK;
-    for (size_t c : counts) total += (long double)c;
-    if (total * 8.0L > 4.0e18L) { delete a; return fail(PMDI_E_MEMORY, "the accumulator would need more than 4e18 bytes"); }
-    size_t off[12], o = 0;
-    for (int i = 0; i < 11; ++i) { off[i] = o; o += counts[i] * 8; }
-    off[11] = o; o += 8;
-    a->state_bytes = o;
-    const size_t bytes = o + CK * 4;
-    hipError_t e = hipMalloc((void **)&a->slab, bytes);
-    if (e != hipSuccess) { a->slab = nullptr; pmdi_summary_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e)); }
-    if (hipMemset(a->slab, 0, bytes) != hipSuccess) { pmdi_summary_destroy(a); return fail(PMDI_E_DEVICE, "hipMemset failed"); }
-    char *p = a->slab;
-    a->hist = (long long *)(p + off[0]); a->nsum = (long long *)(p + off[1]); a->nsumsq = (long long *)(p + off[2]);
-    a->M_mean = (double *)(p + off[3]); a->M_m2 = (double *)(p + off[4]); a->Phi_mean = (double *)(p + off[5]); a->Phi_m2 = (double *)(p + off[6]);
-    a->flag_count = (long long *)(p + off[7]); a->tr_nclust = (long long *)(p + off[8]); a->tr_M = (double *)(p + off[9]);
-    a->tr_Phi = (double *)(p + off[10]); a->err = (int *)(p + off[11]); a->nclust = (int *)(p + a->state_bytes);
-    *out = a;
-    return PMDI_OK;
-}
-
-int pmdi_summary_reset(pmdi_summary *a, void *stream)
-{
-    if (!a) return fail(PMDI_E_ARG, "null argument");
-    HIP_TRY(hipSetDevice(a->device));
-    HIP_TRY(hipMemsetAsync(a->slab, 0, a->state_bytes, (hipStream_t)stream));
-    a->T = 0;
-    return PMDI_OK;
-}
-
-int pmdi_summary_add_arrays(pmdi_summary *a, const int32_t *s, const double *M, const double *Phi, const uint8_t *flags, void *stream)
-{
-    if (!a || !s || !M || (!Phi && a->npairs > 0)) return fail(PMDI_E_ARG, "null argument");
-    if (a->T >= 2147483647LL) return fail(PMDI_E_ARG, "%lld + 1 adds pass INT32_MAX", (long long)a->T);
-    HIP_TRY(hipSetDevice(a->device));
-    SummaryArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.C = a->C; sa.K = a->K; sa.N = a->N; sa.npairs = a->npairs; sa.phi_stride = a->npairs > 0 ? a->npairs : 1;
-    sa.n = a->n; sa.sumD = a->sumD;
-    sa.s = s; sa.M = M; sa.Phi = Phi; sa.flags = flags;
-    sa.nclust = a->nclust; sa.err = a->err; sa.hist = a->hist; sa.nclust_sum = a->nsum; sa.nclust_sumsq = a->nsumsq;
-    sa.M_mean = a->M_mean; sa.M_m2 = a->M_m2; sa.Phi_mean = a->Phi_mean; sa.Phi_m2 = a->Phi_m2; sa.flag_count = a->flag_count;
-    if (a->T < a->trace_cap) {
-        sa.tr_nclust = a->tr_nclust + (size_t)a->T * a->K; sa.tr_M = a->tr_M + (size_t)a->T * a->K;
-        sa.tr_Phi = a->tr_Phi + (size_t)a->T * a->npairs;
-    }
-    hipError_t e = pmdi_launch_summary_add(sa, (long long)a->T + 1, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "summary-add launch: %s", hipGetErrorString(e));
-    a->T += 1;
-    return PMDI_OK;
-}
-
-// what pmdi_summary_add_gibbs checks before it touches anything (pmdi_gibbs_run2 asks once, before its first iteration)
-static int summary_accepts(const pmdi_summary *a, const pmdi_gibbs *g, int64_t n_adds)
-{
-    const pmdi_config &c = g->h->cfg;
-    if (c.n_chains != a->C || c.K != a->K || c.N != a->N || c.n != a->n)
-        return fail(PMDI_E_ARG, "the accumulator holds n_chains=%d K=%d N=%d n=%lld, the chains n_chains=%d K=%d N=%d n=%lld", a->C, a->K, a->N,
-                    a->n, c.n_chains, c.K, c.N, (long long)c.n);
-    if (a->sumD != g->h->sumD && !(a->sumD == 0 && !g->feature_select))
-        return fail(PMDI_E_ARG, "the accumulator holds sumD=%lld, the chains sumD=%d", a->sumD, g->h->sumD);
-    if (c.device != a->device) return fail(PMDI_E_ARG, "the chains live on device %d, the accumulator on device %d", c.device, a->device);
-    if (n_adds > 2147483647LL - a->T) return fail(PMDI_E_ARG, "%lld + %lld adds pass INT32_MAX", (long long)a->T, (long long)n_adds);
-    return PMDI_OK;
-}
-
-int pmdi_summary_add_gibbs(pmdi_summary *a, pmdi_gibbs *g, void *stream)
-{
-    if (!a || !g) return fail(PMDI_E_ARG, "null argument");
-    const int rc = summary_accepts(a, g, 1);
-    if (rc) return rc;
-    return pmdi_summary_add_arrays(a, g->ga.s, g->ga.M, g->ga.Phi, (g->feature_select && a->sumD > 0) ? g->flags : nullptr, stream);
-}
-
-int64_t pmdi_summary_samples(const pmdi_summary *a) { return a ? a->T : 0; }
-
-int pmdi_summary_get(pmdi_summary *a, int64_t *nclust_hist, int64_t *nclust_sum, int64_t *nclust_sumsq, double *M_mean, double *M_m2,
-                     double *Phi_mean, double *Phi_m2, int64_t *flag_count, int64_t *trace_nclust, double *trace_M, double *trace_Phi,
-                     void *stream)
-{
-    if (!a) return fail(PMDI_E_ARG, "null argument");
-    HIP_TRY(hipSetDevice(a->device));
-    hipStream_t st = (hipStream_t)stream;
-    const size_t CK = (size_t)a->C * a->K, CP = (size_t)a->C * a->npairs, cap = (size_t)a->trace_cap;
-    int err = 0;
-    struct { void *dst; const void *src; size_t count; } cp[] = {
-        {nclust_hist, a->hist, (size_t)a->K * (a->N + 1)}, {nclust_sum, a->nsum, CK}, {nclust_sumsq, a->nsumsq, CK},
-        {M_mean, a->M_mean, CK}, {M_m2, a->M_m2, CK}, {Phi_mean, a->Phi_mean, CP}, {Phi_m2, a->Phi_m2, CP},
-        {flag_count, a->flag_count, (size_t)a->sumD}, {trace_nclust, a->tr_nclust, cap * a->K}, {trace_M, a->tr_M, cap * a->K},
-        {trace_Phi, a->tr_Phi, cap * a->npairs}};
-    for (const auto &c : cp)
-        if (c.dst && c.count) HIP_TRY(hipMemcpyAsync(c.dst, c.src, c.count * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&err, a->err, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (err) return fail(PMDI_E_DATA, "a label outside 0..%d was added (pmdi_summary_add_arrays); pmdi_summary_reset clears the accumulator", a->N - 1);
-    return PMDI_OK;
-}
-
 int pmdi_label_counts_device(pmdi_handle *h, const int32_t *s, int32_t *counts, void *stream)
 {
     if (!h || !s || !counts) return fail(PMDI_E_ARG, "null argument");
@@ -1948,41 +1387,6 @@ int pmdi_gibbs_iterate(pmdi_gibbs *g, int64_t n_iter, uint8_t *samples, void *st
         }
     }
     return PMDI_OK;
-}
-
-int pmdi_gibbs_run3(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
-                    void *stream)
-{
-    if (!g || n_iter < 0) return fail(PMDI_E_ARG, "bad argument");
-    if (burnin < 0 || thin < 1) return fail(PMDI_E_ARG, "burnin=%lld must be >= 0 and thin=%lld >= 1", (long long)burnin, (long long)thin);
-    const int64_t kept = n_iter > burnin ? (n_iter - burnin - 1) / thin + 1 : 0;
-    int rc;
-    if (acc && (rc = psm_acc_accepts(acc, g, kept))) return rc;
-    if (summ && (rc = summary_accepts(summ, g, kept))) return rc;
-    if (fus && (rc = fusion_accepts(fus, g, kept))) return rc;
-    for (int64_t t = 1; t <= n_iter; ++t) {
-        if ((rc = pmdi_gibbs_step(g, PMDI_STEP_BEGIN, stream)) || (rc = pmdi_gibbs_step(g, PMDI_STEP_HYPERS, stream)) ||
-            (rc = pmdi_gibbs_step(g, PMDI_STEP_SWEEP, stream)))
-            return rc;
-        if (g->feature_select && (rc = pmdi_gibbs_step(g, PMDI_STEP_FEATSEL, stream))) return rc;
-        if ((rc = pmdi_gibbs_step(g, PMDI_STEP_ALIGN, stream))) return rc;
-        if (t > burnin && (t - burnin - 1) % thin == 0) {
-            if (acc && (rc = pmdi_psm_acc_add_gibbs(acc, g, stream))) return rc;
-            if (summ && (rc = pmdi_summary_add_gibbs(summ, g, stream))) return rc;
-            if (fus && (rc = pmdi_fusion_add_gibbs(fus, g, stream))) return rc;
-        }
-    }
-    return PMDI_OK;
-}
-
-int pmdi_gibbs_run2(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, void *stream)
-{
-    return pmdi_gibbs_run3(g, n_iter, burnin, thin, acc, summ, nullptr, stream);
-}
-
-int pmdi_gibbs_run(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, void *stream)
-{
-    return pmdi_gibbs_run2(g, n_iter, burnin, thin, acc, nullptr, stream);
 }
 
 int64_t pmdi_gibbs_iterations(const pmdi_gibbs *g) { return g ? g->iter : 0; }

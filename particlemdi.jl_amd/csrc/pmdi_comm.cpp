@@ -4,7 +4,7 @@
 // posterior-similarity matrix (consumer: generate_psm, src/output_analysis/consensus_map.jl:31-65) with no further
 // exchange.  RCCL is bound at first use with dlopen (the process may already have torch's librccl.so mapped: the
 // SONAME resolves to that same copy), so the library loads on machines without it.
-#include "../../include/pmdi_hip.h"
+#include "pmdi_host.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -13,8 +13,6 @@
 #include <cstring>
 #include <new>
 #include <vector>
-
-int pmdi_set_error(int code, const char *fmt, ...);   // pmdi_api.cpp
 
 struct pmdi_comm {
     ncclComm_t comm = nullptr;

@@ -6,7 +6,7 @@
 // A row is [M; Phi; ll; s[1:(n_obs * K)]]' -- a Float64 vector (vcat promotes the Int allocations), so
 // every field prints the way Julia prints a Float64: shortest digits that round-trip, plain notation for
 // 1e-5 <= |x| < 1e6, otherwise d.ddde<exp> ("3.0", "0.0001", "1.0e-5", "1.2345678e6").
-#include "../../include/pmdi_hip.h"
+#include "pmdi_host.h"
 
 #include <charconv>
 #include <cmath>
@@ -23,8 +23,6 @@ struct pmdi_csv {
     int npairs = 1;
     std::string buf;
 };
-
-int pmdi_set_error(int code, const char *fmt, ...);   // pmdi_api.cpp
 
 namespace {
 

@@ -1,0 +1,108 @@
+// pmdi_host.h -- what the host translation units of the library (the .cpp files) share: error reporting, owned device
+// buffers, and the two handle types that more than one of them reads.  Host-only: no .hip file includes it.
+#pragma once
+#include "pmdi_internal.h"
+#include "../../include/pmdi_hip.h"
+
+#include <vector>
+
+// sets the text of pmdi_last_error for this thread and returns `code` (pmdi_api.cpp)
+int pmdi_set_error(int code, const char *fmt, ...);
+constexpr auto fail = pmdi_set_error;       // (the name at the call sites)
+
+#define HIP_TRY(expr)                                                                  \
+    do {                                                                               \
+        hipError_t e__ = (expr);                                                       \
+        if (e__ != hipSuccess)                                                         \
+            return fail(e__ == hipErrorOutOfMemory ? PMDI_E_MEMORY : PMDI_E_DEVICE,    \
+                        "%s: %s", #expr, hipGetErrorString(e__));                      \
+    } while (0)
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    int ensure(size_t b)
+    {
+        if (b <= bytes && p) return 0;
+        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
+        if (b == 0) b = 16;
+        hipError_t e = hipMalloc(&p, b);
+        if (e != hipSuccess) { p = nullptr; return fail(PMDI_E_MEMORY, "hipMalloc(%zu): %s", b, hipGetErrorString(e)); }
+        bytes = b;
+        return 0;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+};
+
+// device memory of one call, freed on return
+struct Scratch {
+    void *p = nullptr;
+    ~Scratch() { if (p) (void)hipFree(p); }
+};
+
+struct pmdi_handle {
+    pmdi_config cfg{};
+    pmdi_tuning tun{};           // the creator's knobs (a copy: cfg.tuning is not kept), -1 = automatic
+    int T = 0;
+    long long cap = 0;
+    int Dmax = 0, sumD = 0, npairs = 1;
+    int terms_cap = 0, pid_lds = 0, pp_lds = 0, col_lds = 0, two_per_cu = 0;
+    // light group (block_threads == 0 only): chains whose last sweep met few live clusters per step are
+    // swept by 256-thread workgroups on a second stream, concurrently with the wide workgroups of the rest
+    bool split = false;
+    int l_terms_cap = 0, l_pid_lds = 0, l_pp_lds = 0, l_col_lds = 0;
+    int r_terms_cap = 0, r_pid_lds = 0, r_pp_lds = 0, r_col_lds = 0;     // the general kernel's LDS layout at the settled-chain kernel's workgroup width (hand-over in place)
+    long long light_ids = 0;
+    hipStream_t stream2 = nullptr, stream3 = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join3 = nullptr;
+    unsigned *start_sig = nullptr;   // signal memory: workgroups of the heaviest-chains launch that have started (hipStreamWaitValue32)
+    int very_heavy = 0;          // the first `very_heavy` heavy chains of the launch order get a CU each (256-register build)
+    bool phase_on = false;
+    hipStream_t stream = nullptr;
+    DsetDev ds[PMDI_KMAX_I]{};
+    std::vector<void *> owned;          // device allocations freed in destroy
+    // per-call staging (device)
+    DevBuf d_s_in, d_order, d_Pi, d_logphi, d_flags, d_s_out, d_lw, d_pstar, d_stats, d_err, d_trace;
+    DevBuf d_swept_by, d_resume;
+    bool s2_continue = true;     // a chain the settled-chain kernel gives back is carried on by the general kernel at that observation
+                                 // (false: swept again from the start -- the round-3 behaviour, kept for A/B runs)
+    DevBuf d_usc, d_partstar, d_kstate, d_phase, d_args, d_args2, d_args3, d_args4, d_args5, d_requeue, d_requeue_total, d_handed, d_group, d_cost, d_lorder, d_ticket, d_work, d_anclog, d_evpos, d_xcnt, d_xinc, d_xlab, d_xhdr;
+    int ksplit = 0;
+    int ksplit_batch = 0;        // split mode: chain slots per launch when n_chains * K workgroups are not resident at once (0 = one launch)
+    bool have_order = false;
+    // argument blocks travel through a ring of pinned host slots: the stream-ordered copy is then asynchronous for the host too
+    static constexpr int RING = 64;
+    SweepArgs *ring = nullptr;
+    hipEvent_t ring_ev[RING] = {};
+    bool ring_used[RING] = {};
+    int ring_head = 0;
+    // settled-chain kernel (pmdi_sweep2.hip): takes the light group of a sweep when the configuration is one it is built for
+    bool s2_ok = false;
+    S2Layout s2{};
+    int sweep_no = 0;
+    int sticky = 3;              // sweeps a chain stays with the general kernel after the settled-chain kernel gave it back (PMDI_STICKY)
+    int err_keep = 0;            // set by the device-resident driver around its sweeps (pmdi_gibbs_step)
+    int children = 0;            // live pmdi_gibbs / cluster-batch objects: pmdi_destroy refuses while > 0
+    // feature selection
+    DevBuf d_traj, d_lm, d_firstpos, d_fnull, d_fflags, d_fprob;
+    bool swept = false;
+    long long last_n1 = 0;
+};
+
+// Device-resident Gibbs state of every chain of a handle (pmdi_gibbs_* entry points)
+struct pmdi_gibbs {
+    pmdi_handle *h = nullptr;
+    int device = 0;                      // (cached: destroy must not have to look at the handle)
+    GibbsArgs ga{};
+    int *s_next = nullptr;               // the sweep's output; exchanged with ga.s after every sweep
+    unsigned char *flags = nullptr;      // [chain][sumD] featureFlag
+    double *fprob = nullptr;             // [chain][sumD] featureProb of the last feature selection
+    double *lw = nullptr;                // [chain][P]
+    int *pstar = nullptr;                // [chain]
+    long long *stats = nullptr;          // [chain][8]
+    int *err = nullptr;                  // [chain]
+    long long n1 = 0;
+    int feature_select = 0;
+    int64_t iter = 0;                    // Gibbs iterations done
+    std::vector<void *> owned;
+};

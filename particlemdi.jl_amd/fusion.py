@@ -13,7 +13,8 @@ FusionAccumulator is the third streaming accumulator beside psm.PsmAccumulator a
 arithmetic on the device throughout: every count is exact."""
 import numpy as np
 
-from .psm import PsmCounts, _DeviceInt32View, get_consensus_allocations
+from ._lib import _check, _ptr, lib
+from .psm import PsmCounts, _CountingAccumulator, _DeviceInt32View, get_consensus_allocations
 
 
 def default_groups(K):
@@ -82,16 +83,15 @@ class FusionCounts:
         return self.fused.cpu().numpy(), None if self.counts is None else self.counts.cpu().numpy()
 
 
-class FusionAccumulator:
+class FusionAccumulator(_CountingAccumulator):
     """Streaming fused counts on one MI355X (include/pmdi_hip.h, pmdi_fusion_*).  K datasets, n observations, n_labels as in
     psm.PsmAccumulator (the model's N; 0 = unknown); groups: an iterable of tuples of 0-based dataset indices (order inside a
     tuple irrelevant), None = all pairs in the order of Phi; matrix=False keeps the per-observation counts only (G n int32
     instead of G n n).  All calls go to the current torch stream of the device; use one stream per accumulator."""
+    _prefix = "pmdi_fusion"
 
     def __init__(self, K, n, n_labels=0, groups=None, matrix=True, device=0):
         import ctypes as C
-        from ._lib import _check, _ptr, lib
-        self.h = None
         h = C.c_void_p()
         if groups is None:
             _check(lib().pmdi_fusion_create(int(device), int(K), int(n), int(n_labels), 0, None, int(bool(matrix)), C.byref(h)))
@@ -107,70 +107,20 @@ class FusionAccumulator:
         _check(lib().pmdi_fusion_groups(h, C.byref(G), _ptr(masks)))
         self.groups = tuple(_mask_members(m) for m in masks)
 
-    def _stream(self):
-        import ctypes as C
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
-
-    def close(self):
-        if getattr(self, "h", None):
-            from ._lib import lib
-            lib().pmdi_fusion_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def S(self):
-        from ._lib import lib
-        return int(lib().pmdi_fusion_samples(self.h))
-
-    def reset(self):
-        from ._lib import _check, lib
-        _check(lib().pmdi_fusion_reset(self.h, self._stream()))
-
-    def add_samples(self, samples):
-        """samples: CUDA uint8 tensor (S, K, n) on the accumulator's device, the layout of psm_counts_device."""
-        import ctypes as C
-        import torch
-        from ._lib import _check, lib
-        if not samples.is_cuda or samples.dtype != torch.uint8 or samples.dim() != 3:
-            raise ValueError("FusionAccumulator.add_samples needs a CUDA uint8 tensor (S, K, n)")
-        if tuple(samples.shape[1:]) != (self.K, self.n) or (samples.device.index or 0) != self.device:
-            raise ValueError(f"FusionAccumulator.add_samples: samples {tuple(samples.shape)} on {samples.device}, "
-                             f"the accumulator holds K={self.K} n={self.n} on device {self.device}")
-        smp = samples.contiguous()
-        _check(lib().pmdi_fusion_add_samples(self.h, C.c_void_p(smp.data_ptr()), int(smp.shape[0]), self._stream()))
-
-    def add_gibbs(self, gibbs):
-        """The current allocations of every chain of a _lib.Gibbs: n_chains samples."""
-        from ._lib import _check, lib
-        _check(lib().pmdi_fusion_add_gibbs(self.h, gibbs.h, self._stream()))
-
     def merge(self, other):
         """S += other's S and counts += other's counts (with matrices; only the lower triangle and diagonal are read) or
         fused += other's fused (without).  other: a FusionAccumulator or a FusionCounts of the same groups on the same device."""
         import ctypes as C
         import torch
-        from ._lib import _check, lib
         fc = other.counts() if isinstance(other, FusionAccumulator) else other
         if tuple(fc.groups) != self.groups:
             raise ValueError(f"FusionAccumulator.merge: groups {fc.groups} are not this accumulator's {self.groups}")
         G = len(self.groups)
-
-        def checked(t, shape, what):
-            if t is None or not t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != shape or (t.device.index or 0) != self.device:
-                raise ValueError(f"FusionAccumulator.merge needs int32 {what} {shape} on device {self.device}")
-            return t.contiguous()
         if self.matrix:
-            cnt = checked(fc.counts, (G, self.n, self.n), "counts")
+            cnt = self._checked_tensor(fc.counts, torch.int32, (G, self.n, self.n), "merge: counts")
             _check(lib().pmdi_fusion_merge(self.h, None, C.c_void_p(cnt.data_ptr()), int(fc.S), self._stream()))
         else:
-            fus = checked(fc.fused, (G, self.n), "fused")
+            fus = self._checked_tensor(fc.fused, torch.int32, (G, self.n), "merge: fused")
             _check(lib().pmdi_fusion_merge(self.h, C.c_void_p(fus.data_ptr()), None, int(fc.S), self._stream()))
 
     def counts(self, names=None):
@@ -179,7 +129,6 @@ class FusionAccumulator:
         or (with matrices) fused are read.  names: the K dataset names (default K1, K2, ...); a group is named by its members'."""
         import ctypes as C
         import torch
-        from ._lib import _check, lib
         names = [f"K{k + 1}" for k in range(self.K)] if names is None else [str(x) for x in names]
         if len(names) != self.K:
             raise ValueError(f"FusionAccumulator.counts: {len(names)} names for K={self.K} datasets")

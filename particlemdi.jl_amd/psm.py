@@ -20,6 +20,8 @@ from given starts (pmdi_psm_refine_device); search_consensus_allocation runs it 
 """
 import numpy as np
 
+from ._lib import _Accumulator, _check, lib
+
 
 def allgather_samples(samples):
     """samples: uint8 tensor (T, C, K, n) of this rank -> (world*T*C, K, n) on every rank."""
@@ -155,76 +157,38 @@ class _DeviceInt32View:
                                          "strides": None}
 
 
-class PsmAccumulator:
-    """Streaming co-clustering counts on one MI355X (include/pmdi_hip.h, pmdi_psm_acc_*): K * n * n int32 that take the
-    allocations of every retained iteration of every chain as they are produced, so pooling chains needs neither a sample
-    buffer nor a CSV.  n_labels as in psm_counts_device (the model's N; 0 = unknown).  All calls go to the current torch
-    stream of the device; use one stream per accumulator.  Exact: integer arithmetic only."""
-
-    def __init__(self, K, n, n_labels=0, device=0):
-        import ctypes as C
-        from ._lib import _check, lib
-        self.h = None
-        h = C.c_void_p()
-        _check(lib().pmdi_psm_acc_create(int(device), int(K), int(n), int(n_labels), C.byref(h)))
-        self.h, self.K, self.n, self.n_labels, self.device = h, int(K), int(n), int(n_labels), int(device)
-
-    def _stream(self):
-        import ctypes as C
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
-
-    def close(self):
-        if getattr(self, "h", None):
-            from ._lib import lib
-            lib().pmdi_psm_acc_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def S(self):
-        from ._lib import lib
-        return int(lib().pmdi_psm_acc_samples(self.h))
-
-    def reset(self):
-        from ._lib import _check, lib
-        _check(lib().pmdi_psm_acc_reset(self.h, self._stream()))
+class _CountingAccumulator(_Accumulator):
+    """The two accumulators of int32 counts over label bytes: K datasets, n observations, S samples so far."""
+    S = property(_Accumulator._samples)
 
     def add_samples(self, samples):
         """samples: CUDA uint8 tensor (S, K, n) on the accumulator's device, the layout of psm_counts_device."""
         import ctypes as C
         import torch
-        from ._lib import _check, lib
-        if not samples.is_cuda or samples.dtype != torch.uint8 or samples.dim() != 3:
-            raise ValueError("PsmAccumulator.add_samples needs a CUDA uint8 tensor (S, K, n)")
-        if tuple(samples.shape[1:]) != (self.K, self.n) or (samples.device.index or 0) != self.device:
-            raise ValueError(f"PsmAccumulator.add_samples: samples {tuple(samples.shape)} on {samples.device}, "
-                             f"the accumulator holds K={self.K} n={self.n} on device {self.device}")
-        smp = samples.contiguous()
-        _check(lib().pmdi_psm_acc_add_samples(self.h, C.c_void_p(smp.data_ptr()), int(smp.shape[0]), self._stream()))
+        smp = self._checked_tensor(samples, torch.uint8, (None, self.K, self.n), "add_samples: samples")
+        _check(getattr(lib(), self._prefix + "_add_samples")(self.h, C.c_void_p(smp.data_ptr()), int(smp.shape[0]), self._stream()))
 
-    def add_gibbs(self, gibbs):
-        """The current allocations of every chain of a _lib.Gibbs: n_chains samples."""
-        from ._lib import _check, lib
-        _check(lib().pmdi_psm_acc_add_gibbs(self.h, gibbs.h, self._stream()))
+
+class PsmAccumulator(_CountingAccumulator):
+    """Streaming co-clustering counts on one MI355X (include/pmdi_hip.h, pmdi_psm_acc_*): K * n * n int32 that take the
+    allocations of every retained iteration of every chain as they are produced, so pooling chains needs neither a sample
+    buffer nor a CSV.  n_labels as in psm_counts_device (the model's N; 0 = unknown).  All calls go to the current torch
+    stream of the device; use one stream per accumulator.  Exact: integer arithmetic only."""
+    _prefix = "pmdi_psm_acc"
+
+    def __init__(self, K, n, n_labels=0, device=0):
+        import ctypes as C
+        h = C.c_void_p()
+        _check(lib().pmdi_psm_acc_create(int(device), int(K), int(n), int(n_labels), C.byref(h)))
+        self.h, self.K, self.n, self.n_labels, self.device = h, int(K), int(n), int(n_labels), int(device)
 
     def merge(self, other):
         """counts += other's counts, S += other's S; other is a PsmAccumulator or a PsmCounts on the same device (only its
         lower triangle and diagonal are read)."""
         import ctypes as C
         import torch
-        from ._lib import _check, lib
         pc = other.counts() if isinstance(other, PsmAccumulator) else other
-        cnt = pc.counts
-        if not cnt.is_cuda or cnt.dtype != torch.int32 or tuple(cnt.shape) != (self.K, self.n, self.n) \
-                or (cnt.device.index or 0) != self.device:
-            raise ValueError(f"PsmAccumulator.merge needs int32 counts ({self.K}, {self.n}, {self.n}) on device {self.device}")
-        cnt = cnt.contiguous()
+        cnt = self._checked_tensor(pc.counts, torch.int32, (self.K, self.n, self.n), "merge: counts")
         _check(lib().pmdi_psm_acc_merge(self.h, C.c_void_p(cnt.data_ptr()), int(pc.S), self._stream()))
 
     def counts(self, names=None):
@@ -233,7 +197,6 @@ class PsmAccumulator:
         counts() has to be called again before the upper triangle is read."""
         import ctypes as C
         import torch
-        from ._lib import _check, lib
         ptr, S = C.c_void_p(), C.c_int64(0)
         _check(lib().pmdi_psm_acc_counts(self.h, C.byref(ptr), C.byref(S), self._stream()))
         view = torch.as_tensor(_DeviceInt32View(self, ptr.value, (self.K, self.n, self.n)), device=torch.device("cuda", self.device))

@@ -18,6 +18,8 @@ import re
 
 import numpy as np
 
+from ._lib import _Accumulator, _check, _ptr, lib
+
 
 def _pairs(K):
     """The pair order of the phi columns (src/pmdi.jl:150-152) and of plot_phi_matrix (phi_plots.jl:35-41)."""
@@ -141,17 +143,17 @@ class PosteriorSummary:
                                 *tr)
 
 
-class SummaryAccumulator:
+class SummaryAccumulator(_Accumulator):
     """Streaming posterior summaries on one MI355X (include/pmdi_hip.h, pmdi_summary_*): per-chain Welford moments of M and
     Phi, the histogram and per-chain sums of the number of occupied clusters, feature-flag counts and an optional trace of
     `trace_cap` rows, updated from the device-resident state of every chain after each retained iteration -- no sample buffer,
     no Gibbs.get per chain.  All calls go to the current torch stream of the device; use one stream per accumulator.  The
     integer arrays are exact; the moments are bit-defined by the order of the adds (the header states the recurrences)."""
+    _prefix = "pmdi_summary"
+    T = property(_Accumulator._samples, doc="Adds so far = retained draws per chain.")
 
     def __init__(self, n_chains, K, N, n, sumD=0, trace_cap=0, device=0):
         import ctypes as C
-        from ._lib import _check, lib
-        self.h = None
         h = C.c_void_p()
         _check(lib().pmdi_summary_create(int(device), int(n_chains), int(K), int(N), int(n), int(sumD), int(trace_cap), C.byref(h)))
         self.h = h
@@ -159,52 +161,16 @@ class SummaryAccumulator:
             int(n_chains), int(K), int(N), int(n), int(sumD), int(trace_cap), int(device)
         self.npairs = self.K * (self.K - 1) // 2
 
-    def _stream(self):
-        import ctypes as C
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
-
-    def close(self):
-        if getattr(self, "h", None):
-            from ._lib import lib
-            lib().pmdi_summary_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def T(self):
-        """Adds so far = retained draws per chain."""
-        from ._lib import lib
-        return int(lib().pmdi_summary_samples(self.h))
-
-    def reset(self):
-        from ._lib import _check, lib
-        _check(lib().pmdi_summary_reset(self.h, self._stream()))
-
-    def add_gibbs(self, gibbs):
-        """The current state (s, M, Phi, and the feature flags when feature selection is on) of every chain of a _lib.Gibbs."""
-        from ._lib import _check, lib
-        _check(lib().pmdi_summary_add_gibbs(self.h, gibbs.h, self._stream()))
-
     def add_arrays(self, s, M, Phi, flags=None):
         """CUDA tensors in the layouts of the resident state: s int32 (C, K, n) 0-based labels, M float64 (C, K), Phi float64
         (C, max(1, npairs)), flags uint8 (C, sumD) or None."""
         import ctypes as C
         import torch
-        from ._lib import _check, lib
         want = [("s", s, torch.int32, (self.C, self.K, self.n)), ("M", M, torch.float64, (self.C, self.K)),
                 ("Phi", Phi, torch.float64, (self.C, max(1, self.npairs)))]
         if flags is not None:
             want.append(("flags", flags, torch.uint8, (self.C, self.sumD)))
-        for name, t, dtype, shape in want:
-            if not t.is_cuda or t.dtype != dtype or tuple(t.shape) != shape or (t.device.index or 0) != self.device:
-                raise ValueError(f"SummaryAccumulator.add_arrays: {name} must be a CUDA {dtype} tensor {shape} on device {self.device}")
-        keep = [t.contiguous() for _, t, _, _ in want]
+        keep = [self._checked_tensor(t, dtype, shape, "add_arrays: " + name) for name, t, dtype, shape in want]
         _check(lib().pmdi_summary_add_arrays(self.h, C.c_void_p(keep[0].data_ptr()), C.c_void_p(keep[1].data_ptr()),
                                              C.c_void_p(keep[2].data_ptr()),
                                              C.c_void_p(keep[3].data_ptr()) if flags is not None else None, self._stream()))
@@ -212,7 +178,6 @@ class SummaryAccumulator:
     def arrays(self):
         """Host copies of every array of the accumulator (synchronises the stream); raises PmdiError(PMDI_E_DATA) if a label
         outside 0..N-1 was added since the last reset."""
-        from ._lib import _check, _ptr, lib
         C_, K, P, R = self.C, self.K, self.npairs, self.trace_cap
         out = {"nclust_hist": np.zeros((K, self.N + 1), dtype=np.int64), "nclust_sum": np.zeros((C_, K), dtype=np.int64),
                "nclust_sumsq": np.zeros((C_, K), dtype=np.int64), "M_mean": np.zeros((C_, K)), "M_m2": np.zeros((C_, K)),

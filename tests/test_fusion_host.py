@@ -112,7 +112,7 @@ def test_default_group_order_is_the_order_of_phi(pkg):
     for K, want in by_hand.items():
         assert fusion.default_groups(K) == want == NF.default_groups(K)
     # the library's own default (the C loop of pmdi_fusion_create) is read back where there is a device: test_gpu_fusion.py
-    src = open(os.path.join(ROOT, "particlemdi.jl_amd", "csrc", "pmdi_api.cpp")).read()
+    src = open(os.path.join(ROOT, "particlemdi.jl_amd", "csrc", "pmdi_acc.cpp")).read()
     body = src[src.index("int pmdi_fusion_create("):]
     assert re.search(r"for \(int k1 = 0; k1 < K - 1; \+\+k1\)\s*for \(int k2 = k1 \+ 1; k2 < K; \+\+k2\) masks\[G\+\+\]", body)
 

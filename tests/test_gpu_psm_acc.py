@@ -220,6 +220,49 @@ def test_errors_leave_the_accumulator_alone(pkg):
     sw.close()
 
 
+@pytest.mark.parametrize("chain_counts", [(2, 5), (5, 2)])
+def test_the_pack_buffer_across_handles_of_different_chain_counts(pkg, chain_counts):
+    """pmdi_psm_acc_add_gibbs and pmdi_fusion_add_gibbs pack the chains' labels into a buffer of the accumulator's own, sized at
+    first use for the Gibbs it met.  (2, 5): the second Gibbs has more chains and both buffers have to grow; (5, 2): the
+    buffers are larger than the second Gibbs needs and stay.  What this catches is a buffer that is not regrown or is sized
+    wrongly; the synchronisation before the old buffer is freed cannot be observed from here.  Expected: twin
+    Sweepers and Gibbs objects with the same seeds keep every iteration's bytes (pmdi_gibbs_iterate), and those go through
+    add_samples into fresh accumulators.  Integer counts: exact equality."""
+    import torch
+    from particlemdi_jl_amd import psm
+    rng = np.random.default_rng(5)
+    n, K, N, P, T = 60, 2, 5, 16, 3
+    z = rng.integers(0, 3, n)
+    data = [rng.normal(size=(n, 3)) + 2.0 * (z[:, None] - 1) for _ in range(K)]
+    acc, fus = psm.PsmAccumulator(K, n, N), pkg.FusionAccumulator(K, n, N)
+    want_acc, want_fus = psm.PsmAccumulator(K, n, N), pkg.FusionAccumulator(K, n, N)
+    for chains in chain_counts:
+        sw_a = pkg.Sweeper(data, ["gaussian"] * K, N, P, n_chains=chains, seed=20 + chains)
+        sw_b = pkg.Sweeper(data, ["gaussian"] * K, N, P, n_chains=chains, seed=20 + chains)
+        ga, gb = pkg.Gibbs(sw_a, rho=0.25), pkg.Gibbs(sw_b, rho=0.25)
+        ga.run(T, acc=acc, fusion=fus)
+        ga.results()
+        smp = torch.zeros((T, chains, K, n), dtype=torch.uint8, device="cuda")
+        gb.iterate(T, samples_ptr=smp.data_ptr())
+        gb.results()
+        assert int(smp.max()) < N
+        want_acc.add_samples(smp.reshape(T * chains, K, n))
+        want_fus.add_samples(smp.reshape(T * chains, K, n))
+        for x in (ga, gb, sw_a, sw_b):
+            x.close()
+    got, want = acc.counts(), want_acc.counts()
+    assert got.S == want.S == acc.S == fus.S == 21
+    _assert_full_counts(got.counts.cpu().numpy(), want.counts.cpu().numpy(), 21)
+    got_f, want_f = fus.counts(), want_fus.counts()
+    assert got_f.S == want_f.S == 21 and got_f.groups == want_f.groups == ((0, 1),)
+    (fused, matrices), (w_fused, w_matrices) = got_f.to_host(), want_f.to_host()
+    assert fused.dtype == w_fused.dtype == np.int32 and np.array_equal(fused, w_fused)
+    assert matrices.dtype == w_matrices.dtype == np.int32 and np.array_equal(matrices, w_matrices)
+    assert fused.any()                                       # (not vacuous: the two datasets do agree somewhere)
+    for x in (acc, fus, want_acc, want_fus):
+        x.close()
+
+
 def test_pooled_run_at_a_users_size(pkg):
     """pmdi_pooled: 64 chains of a K = 2 Gaussian problem, n = 2 000.  The separation was chosen by reasoning, not by trial
     on the device: the three planted centres lie 6 within-cluster standard deviations apart in each of the 10 features of
