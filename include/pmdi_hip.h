@@ -360,6 +360,49 @@ int pmdi_psm_refine_device(int32_t device, const int32_t *counts, int64_t S, int
                            int32_t *labels_out /* device, B n */, int64_t *moves_out /* host, B */,
                            int32_t *sweeps_out /* host, B */, void *stream);
 
+/* ---- a descent of the VI bound with exact integer gains -------------------------------------------------------------
+ * pmdi_psm_refine_vi_device is pmdi_psm_refine_device with the Wade-Ghahramani bound as the objective.  counts, S, K, n, which,
+ * w_ij, D, "only i > j is read", A_i(g), start, the slots and labels_out / moves_out / sweeps_out are those of
+ * pmdi_psm_refine_device; own_j = A_j(c_j).
+ *
+ * The logarithm is the fixed-point L(x), defined for integers 1 <= x < 2^62 and evaluated in integer arithmetic only, so it has
+ * the same bits on every host and device.  With FR = 30, TB = 11:
+ *   T[k] = the integer nearest to log2(1 + k / 2048) 2^30, k = 0..2048 (T[0] = 0, T[2048] = 2^30; every entry fits 32 bits,
+ *          adjacent entries differ by less than 2^20); pmdi_vi_log2_table copies the 2049 entries to a HOST array;
+ *   e = floor(log2 x),  m = x << (62 - e),  f = m - 2^62,  k = f >> 51,  r32 = (f & (2^51 - 1)) >> 19,
+ *   L(x) = (e << 30) + T[k] + (((T[k + 1] - T[k]) r32) >> 32).
+ * L(1) = 0, L is non-decreasing, and |L(x) / 2^30 - log2 x| <= h^2 / (8 ln 2) + 2 x 2^-30 with h = 2^-11 (the chord of a
+ * concave function plus two roundings), about 4.5e-8.
+ *
+ * The objective is the int64
+ *   F(c) = sum over the groups g of [ |g| L(|g|) - 2 sum_{j in g} L(own_j + D) ];
+ * the bound that AllocationRowScores reports is F / (n 2^30) + (1/n) sum_i [log2 (rowtotal_i + D) + log2 D] up to the error
+ * of L, and the added constant does not depend on c.  Moving i out of group a (n_a members, i included) into group b (n_b
+ * members; the new singleton: n_b = 0, A_i(b) = 0, an empty sum) has gain = -Delta,
+ *   Delta = [(n_a - 1) L(n_a - 1) - n_a L(n_a)] + [(n_b + 1) L(n_b + 1) - n_b L(n_b)]
+ *           - 2 sum_{j in a, j != i} [L(own_j + D - w_ij) - L(own_j + D)]
+ *           - 2 sum_{j in b}         [L(own_j + D + w_ij) - L(own_j + D)]
+ *           - 2 [L(A_i(b) + D) - L(A_i(a) + D)],
+ * with 0 L(0) read as 0; terms with w_ij = 0 vanish.  Delta is F(after) - F(before) exactly.
+ * One sweep visits i = 0..n-1 in index order.  For the current i the options are ranked: i's current group (gain 0), the
+ * other live groups by ascending slot, a new singleton in the lowest free slot, offered only if i is not alone and fewer
+ * than PMDI_REFINE_GMAX groups are live; the first option with the largest gain wins, so i moves only to something
+ * strictly better.  Sweeps repeat until one makes no move or max_sweeps (>= 1) are done; convergence is told as for
+ * pmdi_psm_refine_device.  objective_out[b] (HOST int64) = F of labels_out[b], formed from the definition after the last sweep.
+ * With n <= 65535 and D <= 2^31 - 1: own + D < 2^47, |g| L(|g|) < 2^50 and every gain is below 2^55 in magnitude, so nothing
+ * beyond the argument checks guards against overflow.
+ * The call allocates the n x n uint32 work matrix and B n int64 for own, frees both before it returns and therefore
+ * SYNCHRONISES `stream`.  Unlike pmdi_psm_refine_device its device memory grows with the starts, 8 B n bytes (0.24 GB at
+ * n = 10 000, B = 3 000): a caller with many starts passes them in slabs (each call builds the work matrix anew); an allocation
+ * that fails is PMDI_E_MEMORY.  PMDI_E_ARG, before any device use: the conditions of pmdi_psm_refine_device.  A start label outside
+ * 0..PMDI_REFINE_GMAX-1: PMDI_E_DATA, outputs undefined.  n = 1: no move, one sweep, objective = -2 L(D).  Stateless. */
+int pmdi_vi_log2_table(int32_t *out /* host, 2049 */);
+int pmdi_psm_refine_vi_device(int32_t device, const int32_t *counts, int64_t S, int32_t K, int64_t n, int32_t which,
+                              const int32_t *start, int64_t B, int64_t ld, int32_t max_sweeps,
+                              int32_t *labels_out /* device, B n */, int64_t *moves_out /* host, B */,
+                              int32_t *sweeps_out /* host, B */, int64_t *objective_out /* host, B: F of labels_out */,
+                              void *stream);
+
 /* ---- device-resident Gibbs chains -----------------------------------------
  * Everything pmdi() does per iteration AROUND the sweep, for every chain of the handle, without leaving the
  * device: shuffle!(order_obs) (src/pmdi.jl:172), update_M!, update_gamma!, Pi, update_Phi!, update_Z, update_v

@@ -11,7 +11,7 @@ from ._lib import (  # noqa: F401
 from .pmdi import pmdi_pooled  # noqa: F401,E402    (not pmdi(): the name is the submodule's)
 from .psm import (  # noqa: F401,E402
     AllocationRowScores, AllocationScores, PsmAccumulator, PsmCounts, best_sampled_allocation, refine_allocations,
-    retained_iterations, row_scores, score_allocations, search_consensus_allocation, select_consensus_allocations,
+    retained_iterations, row_scores, score_allocations, search_consensus_allocation, select_consensus_allocations, vi_log2_table,
 )
 from .fusion import FusionAccumulator, FusionCounts, fused_consensus_allocations  # noqa: F401,E402
 from .summary import (  # noqa: F401,E402

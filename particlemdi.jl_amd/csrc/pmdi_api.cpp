@@ -920,6 +920,48 @@ int pmdi_psm_refine_device(int32_t device, const int32_t *counts, int64_t S, int
     return PMDI_OK;
 }
 
+int pmdi_vi_log2_table(int32_t *out)
+{
+    if (!out) return fail(PMDI_E_ARG, "pmdi_vi_log2_table: null argument");
+    pmdi_vi_log2_table_host(out);
+    return PMDI_OK;
+}
+
+int pmdi_psm_refine_vi_device(int32_t device, const int32_t *counts, int64_t S, int32_t K, int64_t n, int32_t which,
+                              const int32_t *start, int64_t B, int64_t ld, int32_t max_sweeps, int32_t *labels_out, int64_t *moves_out,
+                              int32_t *sweeps_out, int64_t *objective_out, void *stream)
+{
+    if (!counts || !start || !labels_out || !moves_out || !sweeps_out || !objective_out)
+        return fail(PMDI_E_ARG, "pmdi_psm_refine_vi_device: null argument");
+    const int rc = pmdi_psm_shared_args("pmdi_psm_refine_vi_device", S, K, n, which, true, B, ld);
+    if (rc) return rc;
+    const unsigned __int128 D = psm_divisor(S, K, which);
+    if (D > 2147483647u)                             // a w fits the uint32 work matrix; own + D < 2^47 and every gain stays below 2^55
+        return fail(PMDI_E_ARG, "pmdi_psm_refine_vi_device: S=%lld: D > 2^31 - 1", (long long)S);
+    if (max_sweeps < 1) return fail(PMDI_E_ARG, "pmdi_psm_refine_vi_device: max_sweeps=%d < 1", max_sweeps);
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    Scratch work, own, out;
+    const size_t out_bytes = (size_t)B * 20 + 8;     // B moves, B objectives, B sweeps, the flag
+    HIP_TRY(hipMalloc(&work.p, (size_t)n * (size_t)n * 4));
+    HIP_TRY(hipMalloc(&own.p, (size_t)B * (size_t)n * 8));
+    HIP_TRY(hipMalloc(&out.p, out_bytes));
+    HIP_TRY(hipMemsetAsync(out.p, 0, out_bytes, st));
+    long long *d_moves = (long long *)out.p, *d_obj = d_moves + B;
+    int *d_sweeps = (int *)(d_obj + B), *d_flag = d_sweeps + B;
+    const hipError_t e = pmdi_launch_psm_refine_vi(counts, K, n, which, (long long)D, (unsigned *)work.p, (long long *)own.p, start, B, ld,
+                                                   max_sweeps, labels_out, d_moves, d_sweeps, d_obj, d_flag, st);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "psm-refine-vi launch: %s", hipGetErrorString(e));
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(moves_out, d_moves, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(objective_out, d_obj, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(sweeps_out, d_sweeps, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&bad, d_flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));               // the work spaces are freed on return
+    if (bad) return fail(PMDI_E_DATA, "pmdi_psm_refine_vi_device: a start label outside 0..%d", PMDI_REFINE_GMAX - 1);
+    return PMDI_OK;
+}
+
 int pmdi_label_counts_device(pmdi_handle *h, const int32_t *s, int32_t *counts, void *stream)
 {
     if (!h || !s || !counts) return fail(PMDI_E_ARG, "null argument");

@@ -257,6 +257,14 @@ hipError_t pmdi_launch_psm_rowscore(const int *counts, int K, long long n, int w
 hipError_t pmdi_launch_psm_refine(const int *counts, int K, long long n, int which, long long D, int wide, unsigned *W, const int *start,
                                   long long B, long long ld, int max_sweeps, int *labels, long long *moves, int *sweeps, int *flag,
                                   hipStream_t stream);
+// the work matrix alone (both descents build it first)
+hipError_t pmdi_launch_psm_refine_build(const int *counts, int K, long long n, int which, unsigned *W, hipStream_t stream);
+// VI descent (pmdi_psm_refine_vi.hip): W as above; own = B n int64 work space; labels [B][n], moves [B], sweeps [B], objective [B],
+// flag [1] (zeroed by the caller) on the device.  pmdi_vi_log2_table_host: the 2049 table entries of the fixed-point logarithm.
+hipError_t pmdi_launch_psm_refine_vi(const int *counts, int K, long long n, int which, long long D, unsigned *W, long long *own,
+                                     const int *start, long long B, long long ld, int max_sweeps, int *labels, long long *moves,
+                                     int *sweeps, long long *objective, int *flag, hipStream_t stream);
+void pmdi_vi_log2_table_host(int *out);
 
 // One add of the streaming summary accumulator (pmdi_summary.hip): the source arrays in the GibbsArgs layouts, the
 // accumulator's state, and this add's trace row.

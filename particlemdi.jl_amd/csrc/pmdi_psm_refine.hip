@@ -176,16 +176,22 @@ __global__ void __launch_bounds__(PSM_REFINE_THREADS) psm_refine_kernel(const un
 
 }  // namespace
 
+// The work matrix of both descents (this one and pmdi_psm_refine_vi.hip): W = n x n uint32, every element written.
+hipError_t pmdi_launch_psm_refine_build(const int *counts, int K, long long n, int which, unsigned *W, hipStream_t stream)
+{
+    const unsigned tile_pairs = psm_tile_pairs(n, 64);
+    hipLaunchKernelGGL(psm_refine_build_kernel, dim3(tile_pairs < 8192u ? tile_pairs : 8192u), dim3(256), 0, stream, counts, K, n, which,
+                       tile_pairs, W);
+    return hipGetLastError();
+}
+
 // W: n x n uint32 work space.  labels [B][n], moves [B], sweeps [B], flag [1] (zero before the launch) on the device.
 // wide: D n >= 2^32.  1 <= n <= 65535, 1 <= B, D <= 2^31 - 1 and max_sweeps >= 1 are the caller's to check.
 hipError_t pmdi_launch_psm_refine(const int *counts, int K, long long n, int which, long long D, int wide, unsigned *W, const int *start,
                                   long long B, long long ld, int max_sweeps, int *labels, long long *moves, int *sweeps, int *flag,
                                   hipStream_t stream)
 {
-    const unsigned tile_pairs = psm_tile_pairs(n, 64);
-    hipLaunchKernelGGL(psm_refine_build_kernel, dim3(tile_pairs < 8192u ? tile_pairs : 8192u), dim3(256), 0, stream, counts, K, n, which,
-                       tile_pairs, W);
-    hipError_t e = hipGetLastError();
+    hipError_t e = pmdi_launch_psm_refine_build(counts, K, n, which, W, stream);
     if (e != hipSuccess) return e;
     const long long slab = 1LL << 20;                // starts per launch
     for (long long at = 0; at < B; at += slab) {

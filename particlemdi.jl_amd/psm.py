@@ -16,7 +16,8 @@ select_consensus_allocations picks the cut and the linkage with it, best_sampled
 
 row_scores keeps those sums per observation (pmdi_psm_rowscore_device): how firmly each observation sits in its cluster, and
 the variation-of-information bound of Wade & Ghahramani (2018).  refine_allocations is a coordinate descent of Binder's loss
-from given starts (pmdi_psm_refine_device); search_consensus_allocation runs it from every cut and selects by VI, Binder or PEAR.
+(pmdi_psm_refine_device) or of that VI bound in exact fixed-point arithmetic (pmdi_psm_refine_vi_device) from given starts;
+search_consensus_allocation runs either or both from every cut and selects by VI, Binder or PEAR.
 """
 import numpy as np
 
@@ -530,17 +531,32 @@ def _first_appearance(rows, base):
     return out, distinct
 
 
-def refine_allocations(psm, starts, orderby=0, max_sweeps=64):
-    """A coordinate descent of Binder's loss from each start clustering, on the MI355X (pmdi_psm_refine_device; the visiting
-    order, the gains and the tie rule are in include/pmdi_hip.h): sweeps over i = 0..n-1 in which i moves to the group, or
-    to a new singleton, that lowers the loss most, until a sweep makes no move or max_sweeps are done.  Integer gains: the
-    same result on every run.  starts: (B, n) integer labels of any value, numpy or a CUDA tensor; every row is renumbered
-    0.. by first appearance first and may hold at most REFINE_GMAX (4096) distinct labels (ValueError otherwise).
-    Returns (labels, info): labels int64 (B, n) renumbered 1.. by first appearance as cutree does; info = {"moves": int64
-    (B,), "sweeps": int64 (B,), "converged": bool (B,)}, converged = the last sweep made no move.  There is no CPU path."""
+def vi_log2_table():
+    """The 2049 entries T[k] = round(log2(1 + k / 2048) 2^30) of the fixed-point logarithm behind refine_allocations(loss="vi")
+    (include/pmdi_hip.h, pmdi_vi_log2_table), int32; needs no device."""
+    from ._lib import _check, _ptr, lib
+    out = np.zeros(2049, dtype=np.int32)
+    _check(lib().pmdi_vi_log2_table(_ptr(out)))
+    return out
+
+
+def refine_allocations(psm, starts, orderby=0, max_sweeps=64, loss="binder", max_bytes=1 << 30):
+    """A coordinate descent from each start clustering, on the MI355X: sweeps over i = 0..n-1 in which i moves to the group, or
+    to a new singleton, that lowers the loss most, until a sweep makes no move or max_sweeps are done.  loss="binder": Binder's
+    loss (pmdi_psm_refine_device); loss="vi": the variation-of-information bound of Wade & Ghahramani (2018) with a fixed-point
+    logarithm (pmdi_psm_refine_vi_device).  The visiting order, the gains and the tie rule of both are in include/pmdi_hip.h.
+    Integer gains: the same result on every run.  starts: (B, n) integer labels of any value, numpy or a CUDA tensor; every
+    row is renumbered 0.. by first appearance first and may hold at most REFINE_GMAX (4096) distinct labels (ValueError
+    otherwise).  Returns (labels, info): labels int64 (B, n) renumbered 1.. by first appearance as cutree does; info =
+    {"moves": int64 (B,), "sweeps": int64 (B,), "converged": bool (B,)}, converged = the last sweep made no move; with
+    loss="vi" also "objective": int64 (B,), the integer objective F of the labels returned; that call needs 8 n bytes of device
+    work space per start, so the starts go to it in slabs that keep it under max_bytes (one start per slab at the least; every
+    slab builds the work matrix anew).  There is no CPU path."""
     import ctypes as C
     import torch
     from ._lib import REFINE_GMAX, _check, _ptr, lib
+    if loss not in ("binder", "vi"):
+        raise ValueError(f"refine_allocations: loss {loss!r} is not 'binder' or 'vi'")
     cnt = _checked_counts(psm, "refine_allocations")
     which = _which_matrix(psm, orderby, "refine_allocations")
     K, n, _ = cnt.shape
@@ -555,36 +571,52 @@ def refine_allocations(psm, starts, orderby=0, max_sweeps=64):
     B = arr.shape[0]
     st = torch.cuda.current_stream(cnt.device)
 
+    # the VI call keeps own_j of every start in a work space of 8 n bytes per start
+    slab = int(max(1, int(max_bytes) // (8 * n))) if loss == "vi" else B
+
     def run(d_start, nb, sweeps_cap):
         d_out = torch.empty((nb, n), dtype=torch.int32, device=cnt.device)
-        moves, sweeps = np.zeros(nb, dtype=np.int64), np.zeros(nb, dtype=np.int32)
-        _check(lib().pmdi_psm_refine_device(cnt.device.index or 0, C.c_void_p(cnt.data_ptr()), int(psm.S), K, n, which,
-                                            C.c_void_p(d_start.data_ptr()), nb, n, int(sweeps_cap), C.c_void_p(d_out.data_ptr()),
-                                            _ptr(moves), _ptr(sweeps), C.c_void_p(st.cuda_stream)))
-        return d_out, moves, sweeps
+        moves, sweeps, objective = np.zeros(nb, dtype=np.int64), np.zeros(nb, dtype=np.int32), np.zeros(nb, dtype=np.int64)
+        for at in range(0, nb, slab):
+            m = min(slab, nb - at)
+            head = (cnt.device.index or 0, C.c_void_p(cnt.data_ptr()), int(psm.S), K, n, which, C.c_void_p(d_start.data_ptr() + 4 * at * n),
+                    m, n, int(sweeps_cap), C.c_void_p(d_out.data_ptr() + 4 * at * n), _ptr(moves[at:at + m]), _ptr(sweeps[at:at + m]))
+            if loss == "vi":
+                _check(lib().pmdi_psm_refine_vi_device(*head, _ptr(objective[at:at + m]), C.c_void_p(st.cuda_stream)))
+            else:
+                _check(lib().pmdi_psm_refine_device(*head, C.c_void_p(st.cuda_stream)))
+        return d_out, moves, sweeps, objective
 
     d_start = torch.from_numpy(slots.astype(np.int32)).to(cnt.device)
-    d_out, moves, sweeps = run(d_start, B, max_sweeps)
+    d_out, moves, sweeps, objective = run(d_start, B, max_sweeps)
     converged = sweeps < int(max_sweeps)
     capped = np.flatnonzero(~converged)
     if len(capped):                 # all sweeps used: the last one made no move iff a run one sweep shorter made as many moves
         fewer = np.zeros(len(capped), dtype=np.int64)
         if int(max_sweeps) > 1:
-            _, fewer, _ = run(d_start[torch.from_numpy(capped).to(cnt.device)].contiguous(), len(capped), int(max_sweeps) - 1)
+            _, fewer, _, _ = run(d_start[torch.from_numpy(capped).to(cnt.device)].contiguous(), len(capped), int(max_sweeps) - 1)
         converged[capped] = moves[capped] == fewer
     labels, _ = _first_appearance(d_out.cpu().numpy(), 1)
-    return labels, {"moves": moves, "sweeps": sweeps.astype(np.int64), "converged": converged}
+    info = {"moves": moves, "sweeps": sweeps.astype(np.int64), "converged": converged}
+    if loss == "vi":
+        info["objective"] = objective
+    return labels, info
 
 
 def search_consensus_allocation(psm, k=range(2, 21), linkage=("ward",), orderby=0, criterion="vi", refine=True, max_sweeps=64):
     """select_consensus_allocations with a search and a third criterion: the candidates are the cuts k of every linkage (formed
-    exactly as there) and, with refine=True, after all the cuts the refine_allocations form of each cut in the same order.
-    All candidates are scored by ONE score_allocations and ONE row_scores call.  Returns (labels, table): the winner (int64
-    labels 1..) and the rows (source, linkage, k, n_clusters, binder, pear, vi) in candidate order, source "cut" or "refined".
-    criterion "vi" (AllocationRowScores.vi, lowest wins), "binder" (lowest) or "pear" (highest); among equal doubles the
-    earliest candidate wins, NaN candidates are skipped, all NaN raises ValueError."""
+    exactly as there) and, after all the cuts, the refine_allocations form of each cut in the same order.  refine: True or
+    "binder" (the Binder descent, source "refined"), "vi" (the VI descent, source "refined_vi"), "both" (the "refined" rows,
+    then the "refined_vi" rows) or False (the cuts alone).  All candidates are scored by ONE score_allocations and ONE
+    row_scores call.  Returns (labels, table): the winner (int64 labels 1..) and the rows (source, linkage, k, n_clusters,
+    binder, pear, vi) in candidate order.  criterion "vi" (AllocationRowScores.vi, lowest wins), "binder" (lowest) or "pear"
+    (highest); among equal doubles the earliest candidate wins, NaN candidates are skipped, all NaN raises ValueError."""
     if criterion not in ("vi", "binder", "pear"):
         raise ValueError(f"criterion {criterion!r} is not 'vi', 'binder' or 'pear'")
+    losses = {True: ("binder",), "binder": ("binder",), "vi": ("vi",), "both": ("binder", "vi"), False: ()}
+    refine = refine if isinstance(refine, str) else bool(refine)
+    if refine not in losses:
+        raise ValueError(f"refine {refine!r} is not True, False, 'binder', 'vi' or 'both'")
     if not isinstance(psm, PsmCounts):
         raise ValueError("search_consensus_allocation needs a PsmCounts (the device-resident counts)")
     which = _which_matrix(psm, orderby, "search_consensus_allocation")
@@ -599,11 +631,13 @@ def search_consensus_allocation(psm, k=range(2, 21), linkage=("ward",), orderby=
         for kk in ks:
             cuts.append(cutree(hc, k=kk))
             rows.append(("cut", lk, kk))
-    cand = np.stack(cuts)
-    if refine:
-        refined, _ = refine_allocations(psm, cand, orderby=orderby, max_sweeps=max_sweeps)
-        cand = np.concatenate([cand, refined])
-        rows += [("refined", lk, kk) for _, lk, kk in rows]
+    cut_rows, cut_cand = list(rows), np.stack(cuts)
+    cand = [cut_cand]
+    for loss in losses[refine]:
+        refined, _ = refine_allocations(psm, cut_cand, orderby=orderby, max_sweeps=max_sweeps, loss=loss)
+        cand.append(refined)
+        rows += [("refined" if loss == "binder" else "refined_vi", lk, kk) for _, lk, kk in cut_rows]
+    cand = np.concatenate(cand)
     sc = score_allocations(psm, cand, orderby=orderby)
     binder, pear, vi = sc.binder(), sc.pear(), row_scores(psm, cand, orderby=orderby).vi()
     best = _argbest({"vi": vi, "binder": binder, "pear": pear}[criterion], criterion)
