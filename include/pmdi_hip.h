@@ -403,6 +403,34 @@ int pmdi_psm_refine_vi_device(int32_t device, const int32_t *counts, int64_t S, 
                               int32_t *sweeps_out /* host, B */, int64_t *objective_out /* host, B: F of labels_out */,
                               void *stream);
 
+/* ---- consensus_map (src/output_analysis/consensus_map.jl:125-196): block sums of the PSMs over a grouping ------------------
+ * The reference gathers Symmetric(psm.psm[m], :L)[order, order] for every matrix and hands n x n cells to a plotting library.
+ * pmdi_psm_blocksum_device sums the matrices over a grouping of the observations instead, without an n x n temporary.  With the
+ * pixel bins of the leaf order as groups the result is the consensus map binned to pixels (one group per observation: the
+ * permuted matrix itself); with cluster labels it is the cluster x cluster similarity table.
+ *
+ * counts, S, K, n, w_ij and D are those of pmdi_psm_score_device: only counts[k][i][j] with i > j is read, w_ij := w_ji for
+ * i < j, the diagonal counts as D (p_ii = 1) and is never read; a stale or garbage upper triangle or diagonal changes nothing.
+ * group: HOST int32 [n] (it is the product of pmdi_hclust_device / pmdi_cutree, which are host results), values 0..G-1; a group
+ * may be empty.  For every matrix m (m < K: dataset m, D_m = S; m = K, K > 1 only: the Overall matrix, w = sum_k counts_k,
+ * D_m = S K -- the exact mean of pmdi_psm_score_device, not the reference's floating-point order) and groups g, h
+ *   out[m][g][h] = sum_{i : group_i = g} sum_{j : group_j = h} w^m_ij,      the terms i = j included as D_m.
+ * out: DEVICE int64 [M][G][G], M = K + (K > 1).  All M tables come from ONE pass over the K count matrices, and the Overall
+ * table is the exact sum of the K others.  EVERY element of out is written, whatever it held before; an empty group gives a
+ * zero row and column; every table is symmetric.  Integers only: exact in any summation order.
+ * The strict lower triangle of every count matrix is read once, along its rows, and nothing else of it.  The call allocates
+ * 12 n + 8 ceil(n / 32) + 12 G + 96 bytes of device tables at the most (the observations sorted by group, their chunks of at
+ * most 32 rows, 16-bit labels: 0.13 MB at n = 10 000) and no table that grows with n x n or with chunks x G: partial sums go
+ * straight into out.  It frees the tables before it returns and therefore SYNCHRONISES `stream`; an allocation that fails is
+ * PMDI_E_MEMORY.
+ * PMDI_E_ARG, before any device use: K outside 1..PMDI_KMAX; n < 1 or n > 65535; G < 1 or G > PMDI_BLOCKSUM_GMAX; S < 1; a null
+ * pointer; a group value outside 0..G-1; S K n^2 >= 2^62 (the bound that keeps every sum inside int64).
+ * n = 1: out[m][group_0][group_0] = D_m, all else 0.  A count above S is a caller error and is not checked.  Stateless. */
+#define PMDI_BLOCKSUM_GMAX 2048   /* groups of one call: what one workgroup's LDS holds in 64-bit bins */
+int pmdi_psm_blocksum_device(int32_t device, const int32_t *counts, int64_t S, int32_t K, int64_t n,
+                             const int32_t *group /* host, n */, int32_t G,
+                             int64_t *out /* device, [M][G][G], M = K + (K > 1) */, void *stream);
+
 /* ---- device-resident Gibbs chains -----------------------------------------
  * Everything pmdi() does per iteration AROUND the sweep, for every chain of the handle, without leaving the
  * device: shuffle!(order_obs) (src/pmdi.jl:172), update_M!, update_gamma!, Pi, update_Phi!, update_Z, update_v

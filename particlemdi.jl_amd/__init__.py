@@ -4,13 +4,14 @@ The directory name `particlemdi.jl_amd` is not a Python identifier; load it
 with `__graft_entry__.load_package()` which registers it as `particlemdi_jl_amd`.
 """
 from ._lib import (  # noqa: F401
-    ABI_VERSION, CATEGORICAL, EXPORTS, GAUSSIAN, KIND_BY_NAME, LIB_PATH, NEGBINOM,
+    ABI_VERSION, BLOCKSUM_GMAX, CATEGORICAL, EXPORTS, GAUSSIAN, KIND_BY_NAME, LIB_PATH, NEGBINOM,
     ClusterBatch, Comm, CsvWriter, Gibbs, format_float64, read_allocations, PmdiError, REFINE_GMAX, Sweeper, build, lib,
     STEP_ALIGN, STEP_BEGIN, STEP_FEATSEL, STEP_HYPERS, STEP_SWEEP,
 )
 from .pmdi import pmdi_pooled  # noqa: F401,E402    (not pmdi(): the name is the submodule's)
 from .psm import (  # noqa: F401,E402
-    AllocationRowScores, AllocationScores, PsmAccumulator, PsmCounts, best_sampled_allocation, refine_allocations,
+    AllocationRowScores, AllocationScores, BlockSimilarity, ConsensusMap, PsmAccumulator, PsmCounts, best_sampled_allocation,
+    block_similarity, block_sums, consensus_map, refine_allocations,
     retained_iterations, row_scores, score_allocations, search_consensus_allocation, select_consensus_allocations, vi_log2_table,
 )
 from .fusion import FusionAccumulator, FusionCounts, fused_consensus_allocations  # noqa: F401,E402

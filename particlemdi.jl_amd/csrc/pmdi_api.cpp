@@ -4,6 +4,7 @@
 // launches the kernels of pmdi_kernels.hip.  No CPU fallback exists: every
 // compute entry point runs on the gfx950 device or fails.
 #include "pmdi_host.h"
+#include "pmdi_psm_blocksum_plan.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -959,6 +960,43 @@ int pmdi_psm_refine_vi_device(int32_t device, const int32_t *counts, int64_t S, 
     HIP_TRY(hipMemcpyAsync(&bad, d_flag, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));               // the work spaces are freed on return
     if (bad) return fail(PMDI_E_DATA, "pmdi_psm_refine_vi_device: a start label outside 0..%d", PMDI_REFINE_GMAX - 1);
+    return PMDI_OK;
+}
+
+static_assert(PMDI_BLOCKSUM_GMAX == PSM_BLOCKSUM_GMAX_I, "the header's group count is the kernel's");
+
+int pmdi_psm_blocksum_device(int32_t device, const int32_t *counts, int64_t S, int32_t K, int64_t n, const int32_t *group, int32_t G,
+                             int64_t *out, void *stream)
+{
+    if (!counts || !group || !out) return fail(PMDI_E_ARG, "pmdi_psm_blocksum_device: null argument");
+    if (K < 1 || K > PMDI_KMAX || S < 1 || n < 1 || n > 65535 || G < 1 || G > PMDI_BLOCKSUM_GMAX)
+        return fail(PMDI_E_ARG, "pmdi_psm_blocksum_device: S=%lld K=%d n=%lld G=%d out of range (K <= %d, n <= 65535, G <= %d)",
+                    (long long)S, K, (long long)n, G, PMDI_KMAX, PMDI_BLOCKSUM_GMAX);
+    if ((unsigned __int128)S * (unsigned)K * (unsigned __int128)(n * n) >= ((unsigned __int128)1 << 62))      // every sum stays inside int64
+        return fail(PMDI_E_ARG, "pmdi_psm_blocksum_device: S=%lld with K=%d, n=%lld: S K n^2 >= 2^62", (long long)S, K, (long long)n);
+    PsmBlocksumPlan plan;
+    const long long bad = psm_blocksum_plan(group, n, G, plan);
+    if (bad >= 0)
+        return fail(PMDI_E_ARG, "pmdi_psm_blocksum_device: group[%lld]=%d outside 0..%d", bad, group[bad], G - 1);
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    // one allocation: the labels (8-byte reads) first, then the int tables
+    const int nchunks = plan.nchunks();
+    const size_t o_perm = align_up(plan.g16.size() * 2, 16), o_at = o_perm + (size_t)n * 4, o_info = o_at + ((size_t)nchunks + 1) * 4,
+                 o_size = o_info + (size_t)nchunks * 4, bytes = o_size + (size_t)G * 4;
+    Scratch tab;
+    HIP_TRY(hipMalloc(&tab.p, bytes));
+    char *d = (char *)tab.p;
+    HIP_TRY(hipMemcpyAsync(d, plan.g16.data(), plan.g16.size() * 2, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d + o_perm, plan.perm.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d + o_at, plan.chunk_at.data(), ((size_t)nchunks + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d + o_info, plan.chunk_info.data(), (size_t)nchunks * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d + o_size, plan.gsize.data(), (size_t)G * 4, hipMemcpyHostToDevice, st));
+    const hipError_t e = pmdi_launch_psm_blocksum(counts, S, K, n, G, (const unsigned short *)d, plan.npad, (const int *)(d + o_perm),
+                                                  (const int *)(d + o_at), (const int *)(d + o_info), nchunks, (const int *)(d + o_size),
+                                                  (unsigned long long *)out, st);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "psm-blocksum launch: %s", hipGetErrorString(e));
+    HIP_TRY(hipStreamSynchronize(st));               // the tables (and the plan they were copied from) are freed on return
     return PMDI_OK;
 }
 

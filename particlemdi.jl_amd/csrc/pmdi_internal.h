@@ -265,6 +265,11 @@ hipError_t pmdi_launch_psm_refine_vi(const int *counts, int K, long long n, int 
                                      const int *start, long long B, long long ld, int max_sweeps, int *labels, long long *moves,
                                      int *sweeps, long long *objective, int *flag, hipStream_t stream);
 void pmdi_vi_log2_table_host(int *out);
+// block sums over a grouping (pmdi_psm_blocksum.hip): the tables of PsmBlocksumPlan (pmdi_psm_blocksum_plan.h) on the device;
+// out [K + (K > 1)][G][G] on the device, every element written
+hipError_t pmdi_launch_psm_blocksum(const int *counts, long long S, int K, long long n, int G, const unsigned short *g16, long long npad,
+                                    const int *perm, const int *chunk_at, const int *chunk_info, int nchunks, const int *gsize,
+                                    unsigned long long *out, hipStream_t stream);
 
 // One add of the streaming summary accumulator (pmdi_summary.hip): the source arrays in the GibbsArgs layouts, the
 // accumulator's state, and this add's trace row.

@@ -471,6 +471,19 @@ function psm_refine_device(counts::Ptr{Cvoid}, S::Integer, K::Integer, n::Intege
     return moves, sweeps
 end
 
+# ---- consensus_map (consensus_map.jl:125-196): block sums of the PSMs over a grouping (pmdi_psm_blocksum_device; not executed, as above) ----
+# group: host Int32 group numbers 0..G-1, one per observation -- the pixel bins of hc.order, `group[hc.order] .= (0:n-1) .* H .÷ n`,
+# or cluster labels .- 1; out: device pointer to Int64 [M][G][G], M = K + (K > 1), filled.  Returns the M divisors: the map of
+# matrix m is out[m] ./ (D[m] .* (rows x columns of every pixel)).  Synchronises.
+const BLOCKSUM_GMAX = 2048
+function psm_blocksum_device(counts::Ptr{Cvoid}, S::Integer, K::Integer, n::Integer, group::Vector{Int32}, G::Integer, out::Ptr{Cvoid};
+                             device::Integer = 0, stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:pmdi_psm_blocksum_device, LIB), Cint,
+                (Int32, Ptr{Cvoid}, Int64, Int32, Int64, Ptr{Int32}, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
+                device, counts, S, K, n, group, G, out, stream))
+    return K > 1 ? vcat(fill(Int64(S), K), Int64(S) * K) : [Int64(S)]
+end
+
 # ---- the cluster plugin protocol on the device (unit-level entry points) ----------------------
 # calc_logprob / cluster_add! / calc_logmarginal for a batch of stand-alone clusters of dataset k;
 # see pmdi_clusters_new, pmdi_cluster_add, pmdi_calc_logprob, pmdi_calc_logmarginal in the header.

@@ -18,6 +18,10 @@ row_scores keeps those sums per observation (pmdi_psm_rowscore_device): how firm
 the variation-of-information bound of Wade & Ghahramani (2018).  refine_allocations is a coordinate descent of Binder's loss
 (pmdi_psm_refine_device) or of that VI bound in exact fixed-point arithmetic (pmdi_psm_refine_vi_device) from given starts;
 search_consensus_allocation runs either or both from every cut and selects by VI, Binder or PEAR.
+
+consensus_map (consensus_map.jl:125-196) is the figure a run ends in, as data: the matrices in leaf order binned to pixels, from
+block_sums (pmdi_psm_blocksum_device), the block sums of the PSMs over a grouping; block_similarity is the same reduction over
+cluster labels, the cluster x cluster similarity table.
 """
 import numpy as np
 
@@ -695,3 +699,168 @@ def generate_psm(outputFile, burnin=0, thin=1, host=False, device=None):
         dev = torch.device("cuda", 0 if device is None else int(device))
         rows = psm_rows(torch.from_numpy(samples).to(dev), 0, n, n_labels=int(samples.max()) + 1).cpu().numpy()
     return PosteriorSimilarityMatrix([rows[k] for k in range(rows.shape[0])], list(names) + (["Overall"] if K > 1 else []))
+
+
+def block_sums(psm, group, G=None):
+    """Block sums of the K (+1) posterior-similarity matrices over a grouping of the observations, on the MI355X
+    (pmdi_psm_blocksum_device): sums[m, g, h] = sum_{i in g} sum_{j in h} w^m_ij with the diagonal counted as D_m.  One pass
+    over the lower triangles of the counts, no n x n temporary; all integers, exact.  psm: a PsmCounts; group: integer array
+    (n,) of 0-based group numbers, empty groups allowed; G: the number of groups (default max(group) + 1, at most
+    BLOCKSUM_GMAX = 2048).  Returns int64 numpy (M, G, G), M = K + (K > 1), the last table being "Overall" when K > 1.
+    There is no CPU path: without a device this raises."""
+    import ctypes as C
+    import torch
+    from ._lib import _check, _ptr, lib
+    cnt = _checked_counts(psm, "block_sums")
+    K, n, _ = cnt.shape
+    grp = np.asarray(group)
+    if grp.shape != (n,) or not np.issubdtype(grp.dtype, np.integer):
+        raise ValueError(f"block_sums: group must be an integer array ({n},)")
+    if grp.min() < 0 or grp.max() >= 2**31:
+        raise ValueError("block_sums: group numbers must lie in 0..G-1")
+    grp = np.ascontiguousarray(grp, dtype=np.int32)
+    G = int(grp.max()) + 1 if G is None else int(G)
+    out = torch.empty((K + (1 if K > 1 else 0), max(G, 0), max(G, 0)), dtype=torch.int64, device=cnt.device)
+    st = torch.cuda.current_stream(cnt.device)
+    _check(lib().pmdi_psm_blocksum_device(cnt.device.index or 0, C.c_void_p(cnt.data_ptr()), int(psm.S), K, n, _ptr(grp), G,
+                                          C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream)))
+    return out.cpu().numpy()
+
+
+def _matrix_names(psm, K):
+    names = list(psm.names) if psm.names is not None else [f"K{i}" for i in range(1, K + 1)]
+    return names + (["Overall"] if K > 1 else [])
+
+
+class BlockSimilarity:
+    """What block_similarity returns: `sums` int64 (M, G, G), the block sums of block_sums over the clusters; `sizes` int64
+    (G,), the cluster sizes; `D` the M divisors (S per dataset, S K for "Overall"); `names` the M matrix names; `labels` the
+    caller's label of every cluster, in order of first appearance (cluster g of the tables)."""
+
+    def __init__(self, sums, sizes, D, names, labels=None):
+        self.sums, self.sizes, self.D, self.names, self.labels = sums, sizes, [int(d) for d in D], names, labels
+
+    def mean(self):
+        """The mean posterior similarity between the members of two clusters, float64 (M, G, G): off the diagonal
+        sums[g][h] / (D |g| |h|); on the diagonal without the self pairs, (sums[g][g] - D |g|) / (D |g| (|g| - 1)), NaN for a
+        singleton.  Every entry is formed from Python integers and divided once."""
+        M, G, _ = self.sums.shape
+        out = np.full((M, G, G), np.nan, dtype=np.float64)
+        sz = [int(x) for x in self.sizes]
+        for m in range(M):
+            D = self.D[m]
+            for g in range(G):
+                for h in range(G):
+                    s = int(self.sums[m, g, h])
+                    if g != h:
+                        out[m, g, h] = s / (D * sz[g] * sz[h])
+                    elif sz[g] > 1:
+                        out[m, g, g] = (s - D * sz[g]) / (D * sz[g] * (sz[g] - 1))
+        return out
+
+
+def block_similarity(psm, labels):
+    """How strongly each cluster of a labelling holds together and how well it separates from the others, in every dataset:
+    the cluster x cluster block sums of the PSMs (block_sums with the clusters as groups).  labels: (n,) integers of any
+    value, e.g. from get_consensus_allocations or refine_allocations; they are renumbered by first appearance.  More than
+    BLOCKSUM_GMAX (2048) distinct labels raise ValueError.  Returns BlockSimilarity."""
+    from ._lib import BLOCKSUM_GMAX
+    if not isinstance(psm, PsmCounts):
+        raise ValueError("block_similarity needs a PsmCounts (the device-resident counts)")
+    K, n = psm.counts.shape[0], psm.counts.shape[1]
+    lab = np.asarray(labels)
+    if lab.shape != (n,) or not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"block_similarity: labels must be an integer array ({n},)")
+    slots, distinct = _first_appearance(lab[None], 0)
+    G = int(distinct[0])
+    if G > BLOCKSUM_GMAX:
+        raise ValueError(f"block_similarity: {G} distinct labels, at most {BLOCKSUM_GMAX} fit")
+    first = np.full(G, -1, dtype=np.int64)
+    for i in range(n - 1, -1, -1):
+        first[slots[0, i]] = i
+    sums = block_sums(psm, slots[0], G)
+    return BlockSimilarity(sums, np.bincount(slots[0], minlength=G).astype(np.int64), [psm.S] * K + ([psm.S * K] if K > 1 else []),
+                           _matrix_names(psm, K), lab[first])
+
+
+class ConsensusMap:
+    """What consensus_map returns -- the data of the reference's figure (consensus_map.jl:125-196), binned to pixels:
+    `maps` float64 (M, H, H): maps[m] is matrix m in leaf order, averaged over H x H pixels (with H = n the matrix itself);
+        it goes straight into any imshow;
+    `sums` int64 (M, H, H) and `area` int64 (H, H): the exact block sums and rows x columns of every pixel,
+        maps[m] = sums[m] / (D[m] area);
+    `D` the M divisors; `names` the M matrix names;
+    `order` the 1-based leaf order (n,) all maps are shown in -- with orderby = -1 a list of M orders, maps[m] in order[m];
+    `cuts` the consensus labels in leaf order, cutree(hc, k or h)[order]; `ticks` the cluster boundaries of :141-144, in
+        observations (multiply by H / n for pixels);
+    `panels` the reference's panel sequence as indices into maps (the leading matrix first) and `panel_names` beside it;
+    `hc` the HClust of the leading matrix."""
+
+    def __init__(self, maps, sums, area, D, names, order, cuts, ticks, panels, hc):
+        self.maps, self.sums, self.area, self.D, self.names = maps, sums, area, D, names
+        self.order, self.cuts, self.ticks, self.panels, self.hc = order, cuts, ticks, panels, hc
+        self.panel_names = [names[m] for m in panels]
+        self.pixels = int(area.shape[0])
+
+
+def consensus_ticks(cuts):
+    """The cluster boundaries of consensus_map.jl:141-144 for labels 1..nclust in leaf order: the first position (1-based) of
+    every label minus 0.5, sorted, and n + 0.5 at the end.  float64 (nclust + 1,)."""
+    cuts = np.asarray(cuts)
+    nclust = len(np.unique(cuts))
+    first = [int(np.flatnonzero(cuts == c)[0]) + 1 - 0.5 for c in range(1, nclust + 1)]
+    return np.array(sorted(first) + [len(cuts) + 0.5], dtype=np.float64)
+
+
+def consensus_map(psm, k=None, h=None, orderby=0, linkage="ward", pixels=None):
+    """consensus_map(psm; k, h, orderby = 0, linkage = :ward) of src/output_analysis/consensus_map.jl:125-196 up to the point
+    where the reference calls its plotting library: the K (+1) posterior-similarity matrices in the leaf order of the
+    dendrogram of the leading matrix, with the consensus clusters' boundaries -- binned to `pixels` x `pixels` cells on the
+    MI355X (pmdi_psm_blocksum_device), because nobody can draw, or hold, 10^8 cells per matrix at n = 10 000.
+    psm: a PsmCounts (a FusionCounts.psm(group) is one).  k or h: as in get_consensus_allocations (k wins).  orderby: 0 or -1 =
+    the last matrix leads ("Overall" when K > 1), otherwise the 1-based matrix; with -1 and K > 1 every matrix is shown in its
+    OWN ward leaf order (the reference hard-codes ward there, :162), the ticks still come from the leading matrix.
+    pixels = H: default min(n, 1024), 1 <= H <= min(n, 2048); position a (0-based) of the leaf order falls into pixel
+    a H // n, so no pixel is empty.  With H = n, maps[m] is Symmetric(psm.psm[m], :L)[order, order] itself: bit-equal to
+    PsmCounts.to_host() for the datasets (the same one division count / S).  "Overall" is the exact mean
+    sum_k count_k / (S K), the definition of pmdi_psm_score_device, not the reference's floating-point order 0.0 + p_1 / K +
+    ...: the two can differ in the last bit.  (Sums beyond 2^53 would round on their way to float64: S K n^2 / H^2 per pixel.)
+    Returns ConsensusMap.  There is no CPU path and no plotting dependency."""
+    from ._lib import BLOCKSUM_GMAX
+    if isinstance(psm, PosteriorSimilarityMatrix) or not isinstance(psm, PsmCounts):
+        raise TypeError("consensus_map needs the device-resident PsmCounts: generate_psm(..., host=False) computes on the device but "
+                        "returns host matrices; take the counts from psm_counts_device / PsmAccumulator.counts() instead")
+    if k is None and h is None:
+        raise ValueError("You must specify either k (number of clusters) or h (height to cut dendrogram)")
+    K, n = psm.counts.shape[0], psm.counts.shape[1]
+    M = K + (1 if K > 1 else 0)
+    lead = M - 1 if orderby in (0, -1) else int(orderby) - 1
+    if not 0 <= lead < M:
+        raise ValueError(f"consensus_map: orderby={orderby}: there are {M} matrices")
+    H = min(n, 1024) if pixels is None else int(pixels)
+    if not 1 <= H <= min(n, BLOCKSUM_GMAX):
+        raise ValueError(f"consensus_map: pixels={H} outside 1..{min(n, BLOCKSUM_GMAX)}")
+    cnt = _checked_counts(psm, "consensus_map")
+    hc = hclust(psm_distance_device(cnt, psm.S, lead), linkage, overwrite=True)
+    order = np.asarray(hc.order, dtype=np.int64)
+    cuts = cutree(hc, k=k, h=h)[order - 1]
+    ticks = consensus_ticks(cuts)
+    pixel_of = np.arange(n, dtype=np.int64) * H // n              # of the positions 0..n-1 of a leaf order
+    width = np.bincount(pixel_of, minlength=H).astype(np.int64)
+    area = width[:, None] * width[None, :]
+    D = [psm.S] * K + ([psm.S * K] if K > 1 else [])
+
+    def sums_in(order_m):
+        group = np.empty(n, dtype=np.int32)
+        group[order_m - 1] = pixel_of
+        return block_sums(psm, group, H)
+
+    if orderby == -1 and M > 1:
+        orders = [np.asarray(hclust(psm_distance_device(cnt, psm.S, m), "ward", overwrite=True).order, dtype=np.int64) for m in range(M)]
+        sums = np.stack([sums_in(orders[m])[m] for m in range(M)])
+        order = orders
+    else:
+        sums = sums_in(order)
+    maps = np.stack([sums[m].astype(np.float64) / (D[m] * area).astype(np.float64) for m in range(M)])
+    panels = [M - 1] + list(range(M - 1)) if M > 1 else [0]
+    return ConsensusMap(maps, sums, area, D, _matrix_names(psm, K), order, cuts, ticks, panels, hc)
