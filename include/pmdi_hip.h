@@ -707,6 +707,21 @@ int pmdi_settled_kernel(pmdi_handle *h, int64_t *given_back4);
  * tests and bench.py's parity_check use it to say which kernel the compared chains ran on. */
 int pmdi_chain_swept_by(pmdi_handle *h, int32_t *out);
 
+/* What pmdi_create settled on for this handle, for diagnostics and tests: which side of each tuning knob a sweep will run on.  Host
+ * only -- no device work, nothing changes.  out32 (32 Int32):
+ *   [0..4]   the general kernel's wide group: threads per workgroup, doubles of the LDS term buffer, and where its per-particle tables
+ *            live (1 LDS / 0 global memory): class ids, step scratch, column indices
+ *   [5..9]   the same for the light group (256 threads), zeros when the handle launches one group (no automatic width)
+ *   [10..14] the same for the general kernel's code inside the settled-chain kernel's workgroup (a chain handed over in place), zeros
+ *            when the handle does not carry chains on in place
+ *   [15] two_per_cu  [16] automatic width (heaviest / heavy / light launches)  [17] K workgroups per chain  [18] chain slots per
+ *   launch of that form (0 = all in one)  [19] chains that get a CU each  [20] 1: the start gate is armed
+ *   [21] 1: the handle has the settled-chain kernel, and then [22] columns and [23] cluster ids per dataset its LDS tables hold after
+ *   the LDS budget has shrunk them, [24] particle classes, [25] class slots whose mutation-CDF rows are in LDS, [26] its threads per
+ *   workgroup, [27] its LDS bytes, [28] 1: handed-over chains are carried on in place (0: swept again from the start),
+ *   [29] 1: ... by K workgroups per chain (requeue_ksplit);  [30..31] 0 */
+int pmdi_sweep_layout(const pmdi_handle *h, int32_t *out32);
+
 int pmdi_sum_D(const pmdi_handle *h);
 int pmdi_block_threads(const pmdi_handle *h);   /* threads per chain workgroup */
 int pmdi_is_split(const pmdi_handle *h);        /* 1: K cooperating workgroups per chain (one per dataset) */

@@ -50,6 +50,7 @@ EXPORTS = [
     "pmdi_psm_blocksum_device",
     "pmdi_fusion_create", "pmdi_fusion_destroy", "pmdi_fusion_reset", "pmdi_fusion_add_samples", "pmdi_fusion_add_gibbs",
     "pmdi_fusion_merge", "pmdi_fusion_samples", "pmdi_fusion_groups", "pmdi_fusion_counts", "pmdi_gibbs_run3",
+    "pmdi_sweep_layout",
 ]
 
 
@@ -287,6 +288,8 @@ def lib():
     L.pmdi_allgather_samples.restype = C.c_int
     L.pmdi_allgather_samples.argtypes = [vp, i32, vp, vp, i64, vp]
     L.pmdi_is_split.argtypes = [vp]
+    L.pmdi_sweep_layout.restype = C.c_int
+    L.pmdi_sweep_layout.argtypes = [vp, vp]
     L.pmdi_settled_kernel.restype = C.c_int
     L.pmdi_settled_kernel.argtypes = [vp, vp]
     L.pmdi_chain_swept_by.restype = C.c_int
@@ -511,6 +514,24 @@ class Sweeper(_Handle):
         _check(lib().pmdi_label_counts_device(self.h, C.c_void_p(ds.data_ptr()), C.c_void_p(out.data_ptr()),
                                               C.c_void_p(st.cuda_stream)))
         return out.cpu().numpy().astype(np.int64)
+
+    def layout(self):
+        """What pmdi_create settled on for this handle (pmdi_sweep_layout; host only, no device work): the general kernel's
+        workgroup width, LDS term buffer and table placement (1 = LDS, 0 = global memory) for the "wide" group, the "light" group
+        (None without the automatic width) and the "handover" group (the general kernel's code inside the settled-chain kernel's
+        workgroup; None when chains are not carried on in place), the launch knobs as they took effect, and "s2": the settled-chain
+        kernel's LDS tables after the budget loop (None when the handle does not have that kernel)."""
+        v = np.zeros(32, dtype=np.int32)
+        _check(lib().pmdi_sweep_layout(self.h, _ptr(v)))
+        v = [int(x) for x in v]
+        group = lambda g: dict(zip(("threads", "terms_cap", "pid_lds", "pp_lds", "col_lds"), g)) if g[0] else None
+        out = {"wide": group(v[0:5]), "light": group(v[5:10]), "handover": group(v[10:15]),
+               "two_per_cu": v[15], "split": v[16], "ksplit": v[17], "ksplit_batch": v[18], "very_heavy": v[19], "start_gate": v[20],
+               "s2_ok": v[21], "s2": None, "continue_inplace": None, "requeue_ksplit": None}
+        if v[21]:
+            out["s2"] = {"cols_l": v[22], "idcap": v[23], "cls": v[24], "cdfl": v[25], "threads": v[26], "lds_bytes": v[27]}
+            out["continue_inplace"], out["requeue_ksplit"] = v[28], v[29]
+        return out
 
     def given_back(self):
         """Chains the settled-chain kernel has handed back to the general kernel so far (include/pmdi_hip.h, pmdi_settled_kernel):

@@ -768,6 +768,31 @@ int64_t pmdi_lds_bytes(const pmdi_handle *h)
     fill_sweep_common(h, a);
     return (int64_t)pmdi_sweep_lds_bytes(a, h->T);
 }
+int pmdi_sweep_layout(const pmdi_handle *h, int32_t *out32)
+{
+    if (!h || !out32) return fail(PMDI_E_ARG, "null argument");
+    for (int i = 0; i < 32; ++i) out32[i] = 0;
+    const bool handover = h->split && h->s2_ok && h->s2_continue;
+    const int g[3][5] = {
+        { h->T, h->terms_cap, h->pid_lds, h->pp_lds, h->col_lds },
+        { h->split ? 256 : 0, h->split ? h->l_terms_cap : 0, h->split ? h->l_pid_lds : 0, h->split ? h->l_pp_lds : 0, h->split ? h->l_col_lds : 0 },
+        { handover ? pmdi_sweep2_threads(h->cfg.K, h->cfg.P) : 0, handover ? h->r_terms_cap : 0, handover ? h->r_pid_lds : 0,
+          handover ? h->r_pp_lds : 0, handover ? h->r_col_lds : 0 },
+    };
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 5; ++j) out32[5 * i + j] = g[i][j];
+    out32[15] = h->two_per_cu; out32[16] = h->split ? 1 : 0; out32[17] = h->ksplit; out32[18] = h->ksplit_batch;
+    out32[19] = h->split ? h->very_heavy : 0;
+    out32[20] = (h->split && h->very_heavy > 0 && h->start_sig != nullptr && !h->ksplit) ? 1 : 0;
+    out32[21] = h->s2_ok ? 1 : 0;
+    if (h->s2_ok) {
+        out32[22] = h->s2.cols_l; out32[23] = h->s2.idcap; out32[24] = h->s2.cls; out32[25] = h->s2.cdfl;
+        out32[26] = pmdi_sweep2_threads(h->cfg.K, h->cfg.P); out32[27] = h->s2.total;
+        out32[28] = h->s2_continue ? 1 : 0;
+        out32[29] = (!h->s2_continue && h->cfg.K > 1 && h->d_xcnt.p && h->tun.requeue_ksplit != 0) ? 1 : 0;
+    }
+    return PMDI_OK;
+}
 int pmdi_sum_D(const pmdi_handle *h) { return h ? h->sumD : 0; }
 int pmdi_settled_kernel(pmdi_handle *h, int64_t *given_back4)
 {

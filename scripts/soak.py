@@ -1,6 +1,6 @@
 """Randomised parity soak: the HIP sweep (through the C ABI) against the oracle on many small random
 configurations -- data types, N (up to 128), P, K, chains, quirk switches (Q1, Q2), flags, workgroup widths, launch-split thresholds, both forms of
-the K > 1 sweep.
+the K > 1 sweep, and where the kernels keep their tables (the settled-chain kernel's LDS columns / ids, the general kernel's LDS target).
 Usage: python scripts/soak.py [seconds] [seed]"""
 import os, sys, time
 import numpy as np
@@ -12,13 +12,16 @@ pkg = G.load_package(); O = G.load_oracle()
 def run(budget, seed, max_cases=10**9, verbose=True):
     rng = np.random.default_rng(seed)
     t_end = time.time() + budget
-    ncase = 0
-    saved = {k: os.environ.get(k) for k in ("PMDI_LIGHT_IDS", "PMDI_VERY_HEAVY", "PMDI_KSPLIT", "PMDI_SETTLED", "PMDI_S2_CLS", "PMDI_STICKY")}
+    ncase = skipped = 0
+    saved = {k: os.environ.get(k) for k in ("PMDI_LIGHT_IDS", "PMDI_VERY_HEAVY", "PMDI_KSPLIT", "PMDI_SETTLED", "PMDI_S2_CLS", "PMDI_STICKY",
+                                               "PMDI_S2_COLS", "PMDI_S2_IDCAP", "PMDI_LDS_TARGET")}
     try:
         while time.time() < t_end and ncase < max_cases:
-            ncase += _one_case(rng)
-            if verbose and ncase % 20 == 0:
-                print(f"{ncase} configurations equal", flush=True)
+            done = _one_case(rng)
+            ncase += done
+            skipped += 1 - done
+            if verbose and done and ncase % 20 == 0:
+                print(f"{ncase} configurations equal ({skipped} drawn that pmdi_create does not take)", flush=True)
     finally:
         for k, v in saved.items():
             if v is None:
@@ -56,11 +59,28 @@ def _one_case(rng):
     sumD = sum(d.shape[1] for d in data)
     flags = (rng.random((Cn, sumD)) < 0.7).astype(np.uint8) if rng.random() < 0.3 else None
     seed = int(rng.integers(0, 2**31))
-    desc = f"K={K} n={n} N={N} P={P} C={Cn} q1={q1} T={block} n1={n1} it={iters} kinds={kinds} sep={sep} light={os.environ['PMDI_LIGHT_IDS']} settled={os.environ['PMDI_SETTLED']} cls={os.environ['PMDI_S2_CLS']} sticky={os.environ['PMDI_STICKY']} vh={os.environ['PMDI_VERY_HEAVY']} flags={'y' if flags is not None else 'n'} q2={q2} split={os.environ['PMDI_KSPLIT']} seed={seed}"
+    # where the tables live: a generator of its own, seeded from the configuration's seed (the draws above stay what they were).
+    # Settled-chain kernel: LDS columns / ids from "next to nothing" over the defaults to "all that fits"; general kernel: an LDS
+    # target of 0 (every per-particle table in global memory), of a few KiB around the tables' sizes, or none (automatic)
+    rng_t = np.random.default_rng([seed, 0x7ab1e5])
+    os.environ["PMDI_S2_COLS"] = str(int(rng_t.choice([-1, 1, 2, 16, 64, P])))
+    os.environ["PMDI_S2_IDCAP"] = str(int(rng_t.choice([-1, 8, 24, 128, 512, 4096])))
+    target = int(rng_t.choice([-1, -1, 0, 1 << 30]) if rng_t.random() < 0.6 else rng_t.integers(4096, 65536))
+    os.environ["PMDI_LDS_TARGET"] = str(target)
+    desc = f"K={K} n={n} N={N} P={P} C={Cn} q1={q1} T={block} n1={n1} it={iters} kinds={kinds} sep={sep} light={os.environ['PMDI_LIGHT_IDS']} settled={os.environ['PMDI_SETTLED']} cls={os.environ['PMDI_S2_CLS']} sticky={os.environ['PMDI_STICKY']} vh={os.environ['PMDI_VERY_HEAVY']} s2cols={os.environ['PMDI_S2_COLS']} s2idcap={os.environ['PMDI_S2_IDCAP']} ldstarget={os.environ['PMDI_LDS_TARGET']} flags={'y' if flags is not None else 'n'} q2={q2} split={os.environ['PMDI_KSPLIT']} seed={seed}"
     try:
         sw = pkg.Sweeper(data, kinds, N, P, n_chains=Cn, seed=seed, q1_mode=q1, q2_mode=q2, block_threads=block)
-    except Exception as e:
-        return 0
+    except Exception:
+        # (a drawn LDS target can ask for more LDS than a workgroup has, e.g. everything in LDS at P = 4 096: the configuration
+        # then runs with the automatic layout, as it did before this knob was drawn; what pmdi_create refuses even so is skipped)
+        if os.environ["PMDI_LDS_TARGET"] == "-1":
+            return 0
+        os.environ["PMDI_LDS_TARGET"] = "-1"
+        desc = desc.replace(f"ldstarget={target}", "ldstarget=-1")
+        try:
+            sw = pkg.Sweeper(data, kinds, N, P, n_chains=Cn, seed=seed, q1_mode=q1, q2_mode=q2, block_threads=block)
+        except Exception:
+            return 0
     orc = [O.Oracle(data, kinds, N, P, seed=seed + c, q1_mode=q1, q2_mode=q2) for c in range(Cn)]
     s = rng.integers(1, N + 1, size=(Cn, n, K))
     Dcum = np.cumsum([d.shape[1] for d in data])[:-1]
@@ -80,7 +100,8 @@ def _one_case(rng):
                 os.makedirs("gpurun_out", exist_ok=True)
                 np.savez("gpurun_out/soak_fail.npz", kinds=np.array(kinds), N=N, P=P, Cn=Cn, q1=q1, q2=q2, block=block, n1=n1, it=it, chain=c, seed=seed,
                          s=s, order=order, Pi=np.stack([h[0] for h in hyp]), Phi=np.stack([h[1] for h in hyp]),
-                         flags=np.zeros(0) if flags is None else flags, env=np.array([os.environ["PMDI_LIGHT_IDS"], os.environ["PMDI_VERY_HEAVY"], os.environ["PMDI_KSPLIT"]]),
+                         flags=np.zeros(0) if flags is None else flags, env=np.array([os.environ["PMDI_LIGHT_IDS"], os.environ["PMDI_VERY_HEAVY"], os.environ["PMDI_KSPLIT"],
+                                                                                         os.environ["PMDI_S2_COLS"], os.environ["PMDI_S2_IDCAP"], os.environ["PMDI_LDS_TARGET"]]),
                          **{f"data{k}": d for k, d in enumerate(data)})
                 raise AssertionError(f"MISMATCH: {desc} iteration {it} chain {c}")
         s = r["s"].copy()

@@ -82,6 +82,49 @@ def check_state_cap(dev, orc, cap, live_only=False):
         assert not orc["cluster_n"][:, cap:].any()
 
 
+STAT_KEYS = ("n_operations", "n_resamples", "n_clones", "max_id", "sum_classes")
+
+
+def chain_result(r, c):
+    """Chain c of a batched Sweeper.sweep result, in the shape of a single-chain one (as the oracle's)."""
+    out = {"s": r["s"][c], "p_star": int(r["p_star"][c]), "logweight": r["logweight"][c], "stats": r["stats"][c]}
+    if "trace" in r:
+        out["trace"] = r["trace"][c]
+    return out
+
+
+def check_sweep_against_oracle(rg, ro, wk, work, rec, N, kernel, all_int=False, clones=False, where=""):
+    """One chain-sweep of the device (rg: chain_result / a single-chain runner's result, with its trace; wk: its work counters (K, 8);
+    kernel: pmdi_chain_swept_by) against the oracle's (ro: Oracle.sweep with trace; work: Oracle.work(); rec: its per-step record):
+    per-observation trace, allocations, picked particle, log-weights, the five counters and the work counters.  all_int: no Gaussian
+    dataset -- the log-predictives are the oracle's bits (host-built tables, same order of additions; the increment's log(f[N]) is
+    the device's log either way).  clones: also the cloned clusters summed over the datasets."""
+    bad = np.where(~np.isclose(rg["trace"], ro["trace"], rtol=1e-9, atol=1e-9).all(axis=1))[0]
+    assert bad.size == 0, f"{where}: first diverging swept observation {bad[0]}: gpu={rg['trace'][bad[0]]} cpu={ro['trace'][bad[0]]}"
+    assert (rg["s"] == ro["s"]).all(), where
+    assert int(rg["p_star"]) == ro["p_star"], where
+    assert np.allclose(rg["logweight"], ro["logweight"], rtol=1e-12 if all_int else 1e-9, atol=1e-9 if all_int else 1e-8), where
+    for key in STAT_KEYS:
+        assert rg["stats"][key] == ro["stats"][key], (where, key)
+    # the work counters behind bench.py's algorithmic byte count: clusters updated / cloned / moved per dataset
+    up, mv = work
+    assert (wk[:, 1] == up).all() and (wk[:, 3] == mv).all(), where
+    if clones:
+        assert wk[:, 2].sum() == ro["stats"]["n_clones"], where
+    # ... and, pinned to the oracle's per-step record: clusters evaluated (the ones a class leader reads at src/pmdi.jl:232),
+    # distinct columns of particle[:, :, k] met by the resampling events, columns made by copy-on-write splits
+    check_work_counters(wk, rec, ro["trace"], N, kernel)
+
+
+def check_state_against_oracle(eg, eo, N, P, K, n, keys=("particle", "max_id")):
+    """The exported device state against the oracle's, and the reference's T5 invariants on it.  The settled-chain kernel exports
+    no sizes above max_id, so the tests of handles that have it compare `particle` and `max_id`; the general kernel's compare all
+    four arrays."""
+    for key in keys:
+        assert (eg[key] == eo[key]).all(), key
+    t5_invariants(eg, N, P, K, n)
+
+
 def check_work_counters(wk, rec, trace, N, kernel):
     """The device's work counters of one chain-sweep (wk: (K, 8)) against the oracle's per-step record.  Clusters evaluated
     (column 0) depends on which kernel swept the chain (pmdi_chain_swept_by): the settled-chain kernel (1) evaluates the reachable

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from _cases import check_work_counters, expected_work_counters, golden_cases, load_golden, replay, t5_invariants
+from _cases import chain_result, check_state_against_oracle, check_sweep_against_oracle, golden_cases, load_golden, replay
 from conftest import make_mixed, random_hypers
 
 pytestmark = pytest.mark.gpu
@@ -48,25 +48,10 @@ def _compare_run(pkg, O, data, kinds, N, P, iters, seed, n1, q1=0, flags=None, b
         Pi, Phi = random_hypers(rng, N, K)
         rg = g.sweep(it, s, order, n1, Pi, Phi, flags, trace=True)
         ro = o.sweep(it, s, order, n1, Pi, Phi, flags=None if flags is None else np.split(flags, Dcum), trace=True)
-        bad = np.where(~np.isclose(rg["trace"], ro["trace"], rtol=1e-9, atol=1e-9).all(axis=1))[0]
-        assert bad.size == 0, f"first diverging swept observation: {bad[0]} gpu={rg['trace'][bad[0]]} cpu={ro['trace'][bad[0]]}"
-        assert (rg["s"] == ro["s"]).all()
-        assert rg["p_star"] == ro["p_star"]
-        assert np.allclose(rg["logweight"], ro["logweight"], rtol=1e-9, atol=1e-8)
-        for key in ("n_operations", "n_resamples", "n_clones", "max_id", "sum_classes"):
-            assert rg["stats"][key] == ro["stats"][key], key
-        # the work counters behind bench.py's algorithmic byte count: clusters updated / cloned / moved per dataset
-        wk, (up, mv) = g.sw.work_counters()[0], o.work()
-        assert (wk[:, 1] == up).all() and (wk[:, 3] == mv).all() and wk[:, 2].sum() == ro["stats"]["n_clones"]
-        # ... and, pinned to the oracle's per-step record: clusters evaluated (the ones a class leader reads at src/pmdi.jl:232),
-        # distinct columns of particle[:, :, k] met by the resampling events, columns made by copy-on-write splits
-        check_work_counters(wk, rec, ro["trace"], N, int(g.sw.swept_by()[0]))
+        check_sweep_against_oracle(rg, ro, g.sw.work_counters()[0], o.work(), rec, N, int(g.sw.swept_by()[0]), clones=True, where=f"iteration {it}")
         s = ro["s"]
     if check_state:
-        eg, eo = g.sw.export_state(0), o.export()
-        for key in ("particle", "counts", "cluster_n", "max_id"):
-            assert (eg[key] == eo[key]).all(), key
-        t5_invariants(eg, N, P, K, n)
+        check_state_against_oracle(g.sw.export_state(0), o.export(), N, P, K, n, keys=("particle", "counts", "cluster_n", "max_id"))
     return g
 
 
@@ -351,18 +336,8 @@ def test_settled_chain_kernel_equals_oracle(pkg, O, monkeypatch, K, P, n, N):
         kern = sw.swept_by()
         for c in range(C):
             ro = orcs[c].sweep(it, s[c], order[c], n1, hyp[c][0], hyp[c][1], trace=True)
-            bad = np.where(~np.isclose(rg["trace"][c], ro["trace"], rtol=1e-9, atol=1e-9).all(axis=1))[0]
-            assert bad.size == 0, f"chain {c} iteration {it}: first diverging swept observation {bad[0]}: gpu={rg['trace'][c][bad[0]]} cpu={ro['trace'][bad[0]]}"
-            assert (rg["s"][c] == ro["s"]).all() and int(rg["p_star"][c]) == ro["p_star"]
-            assert np.allclose(rg["logweight"][c], ro["logweight"], rtol=1e-9, atol=1e-8)
-            for key in ("n_operations", "n_resamples", "n_clones", "max_id", "sum_classes"):
-                assert rg["stats"][c][key] == ro["stats"][key], key
-            up, mv = orcs[c].work()
-            assert (wk[c][:, 1] == up).all() and (wk[c][:, 3] == mv).all()
-            check_work_counters(wk[c], recs[c], ro["trace"], N, int(kern[c]))
-            eg, eo = sw.export_state(c), orcs[c].export()
-            assert (eg["particle"] == eo["particle"]).all() and (eg["max_id"] == eo["max_id"]).all()
-            t5_invariants(eg, N, P, K, n)
+            check_sweep_against_oracle(chain_result(rg, c), ro, wk[c], orcs[c].work(), recs[c], N, int(kern[c]), where=f"chain {c} iteration {it}")
+            check_state_against_oracle(sw.export_state(c), orcs[c].export(), N, P, K, n)
             s[c] = ro["s"]
     gb = sw.given_back()
     print(f"K={K} P={P}: chains handed back to the general kernel (reachable, chosen, classes, total) = {gb.tolist()} of {3 * C} chain-sweeps")
@@ -427,20 +402,8 @@ def test_settled_chain_kernel_mixed_types_equal_oracle(pkg, O, monkeypatch, kind
         kern = sw.swept_by()
         for c in range(C):
             ro = orcs[c].sweep(it, s[c], order[c], n1, hyp[c][0], hyp[c][1], trace=True)
-            bad = np.where(~np.isclose(rg["trace"][c], ro["trace"], rtol=1e-9, atol=1e-9).all(axis=1))[0]
-            assert bad.size == 0, f"chain {c} iteration {it}: first diverging swept observation {bad[0]}: gpu={rg['trace'][c][bad[0]]} cpu={ro['trace'][bad[0]]}"
-            assert (rg["s"][c] == ro["s"]).all() and int(rg["p_star"][c]) == ro["p_star"]
-            # (integer types: the log-predictives are the oracle's bits -- host-built tables, same order of additions; the increment's
-            # log(f[N]) is the device's log either way)
-            assert np.allclose(rg["logweight"][c], ro["logweight"], rtol=1e-12 if all_int else 1e-9, atol=1e-9 if all_int else 1e-8)
-            for key in ("n_operations", "n_resamples", "n_clones", "max_id", "sum_classes"):
-                assert rg["stats"][c][key] == ro["stats"][key], key
-            up, mv = orcs[c].work()
-            assert (wk[c][:, 1] == up).all() and (wk[c][:, 3] == mv).all()
-            check_work_counters(wk[c], recs[c], ro["trace"], N, int(kern[c]))
-            eg, eo = sw.export_state(c), orcs[c].export()
-            assert (eg["particle"] == eo["particle"]).all() and (eg["max_id"] == eo["max_id"]).all()
-            t5_invariants(eg, N, P, K, n)
+            check_sweep_against_oracle(chain_result(rg, c), ro, wk[c], orcs[c].work(), recs[c], N, int(kern[c]), all_int=all_int, where=f"chain {c} iteration {it}")
+            check_state_against_oracle(sw.export_state(c), orcs[c].export(), N, P, K, n)
             s[c] = ro["s"]
     gb = sw.given_back()
     print(f"{'+'.join(kinds)} P={P}: chains handed back (reachable, chosen, classes, total) = {gb.tolist()} of {3 * C} chain-sweeps")
@@ -448,33 +411,61 @@ def test_settled_chain_kernel_mixed_types_equal_oracle(pkg, O, monkeypatch, kind
     sw.close()
 
 
-@pytest.mark.parametrize("kinds,P,N,flags", [
-    (("gaussian", "gaussian", "gaussian", "gaussian"), 1024, 40, False),          # 4-bit class slots (the headline shape): 16 classes
-    (("gaussian", "categorical"), 512, 40, True),                                   # 5-bit slots, tables squeezed to 16 classes
-    (("categorical", "negbinom", "gaussian"), 256, 30, False),
-    (("gaussian", "gaussian", "categorical", "negbinom"), 2048, 50, False),       # 512-thread workgroups
-    (("gaussian",), 512, 40, False),
-], ids=["K4-P1024", "gau+cat-flags", "cat+nb+gau", "cfg4-shape", "K1"])
-def test_hand_over_mid_sweep_equals_oracle(pkg, O, kinds, P, N, flags):
+HAND_OVER = [      # kinds, P, N, feature flags, the settled-chain kernel's LDS tables, n
+    (("gaussian", "gaussian", "gaussian", "gaussian"), 1024, 40, False, None, 260),          # 4-bit class slots (the headline shape): 16 classes
+    (("gaussian", "categorical"), 512, 40, True, None, 260),                                   # 5-bit slots, tables squeezed to 16 classes
+    (("categorical", "negbinom", "gaussian"), 256, 30, False, None, 260),
+    (("gaussian", "gaussian", "categorical", "negbinom"), 2048, 50, False, None, 260),       # 512-thread workgroups
+    (("gaussian",), 512, 40, False, None, 260),
+    # the same with the settled-chain kernel's tables on either side.  (2, 8): next to every column and id is in the chain's arena
+    # when the chain is handed over.  Everything in LDS -- what the headline workload hands over from -- does not fit these shapes
+    # (N = 40 labels and 16 classes leave K4-P1024 24 columns and 64 ids, gau+cat-flags 224 columns beside 64 ids, whatever they ask
+    # for), so that side runs on a smaller one: two Gaussian datasets, 256 particles, 20 labels, 60 observations, whose chains stay
+    # below 496 ids until they are handed over, or for the whole sweep if they are not
+    (("gaussian", "gaussian", "gaussian", "gaussian"), 1024, 40, False, "tiny", 260),
+    (("gaussian", "categorical"), 512, 40, True, "tiny", 260),
+    (("gaussian", "gaussian"), 256, 20, False, "all-LDS", 60),
+]
+HAND_OVER_TABLES = {None: {}, "tiny": {"s2_cols": 2, "s2_idcap": 8}, "all-LDS": {"s2_cols": 256, "s2_idcap": 496}}
+
+
+@pytest.mark.parametrize("kinds,P,N,flags,tables,n", HAND_OVER,
+                         ids=["K4-P1024", "gau+cat-flags", "cat+nb+gau", "cfg4-shape", "K1", "K4-P1024-tiny", "gau+cat-flags-tiny", "K2-P256-all-LDS"])
+def test_hand_over_mid_sweep_equals_oracle(pkg, O, kinds, P, N, flags, tables, n):
     """The settled-chain kernel hands a chain over to the general kernel's code IN PLACE at the observation whose step does not fit its
     tables (here: more than 16 particle classes -- the class capacity is squeezed to 16 and the prior leaves mass on many empty
     labels, so hand-overs happen at assorted positions of the sweep, in one or several datasets of the same observation, and again
     in later iterations after the chain has returned to the settled-chain kernel).  Everything the reference defines is compared with
-    the oracle: per-observation trace, allocations, picked particle, log-weights, counters, work counters, the exported state."""
+    the oracle: per-observation trace, allocations, picked particle, log-weights, counters, work counters, the exported state.
+    The hand-over gathers the general kernel's state from the settled-chain kernel's LDS tables and from the chain's arena: `tables`
+    puts the chain on one side, asserted through layout() and, from the oracle's per-step record, over the steps that kernel can have
+    swept: none beyond the first that STARTS with more classes than its tables hold.  (The kernel counts the classes a step's draws
+    make before the step's resampling thins them, so it may hand over earlier, even in a sweep whose record shows no such step: the
+    steps counted are a superset of the ones it swept.)"""
     kinds = list(kinds)
     K = len(kinds)
     rng = np.random.default_rng(300 + K + P)
-    n = 260
     data, z = _mixed_planted(rng, n, kinds)
     n1 = n // 4
     C = 4
     fl = None
     if flags:
         fl = np.concatenate([(rng.random(d.shape[1]) < 0.7).astype(np.uint8) for d in data])
-    sw = pkg.Sweeper(data, kinds, N, P, n_chains=C, seed=903, tuning={"settled": 2, "sticky": 0, "ksplit": 0, "s2_cls": 16})
+    tuning = {"settled": 2, "sticky": 0, "ksplit": 0, "s2_cls": 16, **HAND_OVER_TABLES[tables]}
+    sw = pkg.Sweeper(data, kinds, N, P, n_chains=C, seed=903, tuning=tuning)
     assert sw.settled
+    lay = sw.layout()
+    assert lay["s2"]["cls"] == 16 and lay["continue_inplace"] == 1 and lay["handover"]["threads"] == lay["s2"]["threads"], lay
+    cols_l, idcap = lay["s2"]["cols_l"], lay["s2"]["idcap"]
+    if tables:
+        assert (cols_l, idcap) == (tuning["s2_cols"], tuning["s2_idcap"]), lay
+    if tables == "all-LDS":
+        assert cols_l == P          # every column a chain can have
     orcs = [O.Oracle(data, kinds, N, P, seed=903 + c) for c in range(C)]
     recs = [o.debug_steps(n - n1 + 1) for o in orcs]
+    # (step, dataset) pairs the settled-chain kernel swept, by the oracle's record: within both of its LDS tables from the start of the
+    # step to its end / beyond both when the step starts
+    inside = beyond = steps = 0
     Dcum = np.cumsum([d.shape[1] for d in data])[:-1]
     s = np.repeat(np.repeat((z + 1)[None, :, None], K, axis=2), C, axis=0)
     idx = rng.random(s.shape) < 0.08
@@ -491,21 +482,28 @@ def test_hand_over_mid_sweep_equals_oracle(pkg, O, kinds, P, N, flags):
         kern = sw.swept_by()
         for c in range(C):
             ro = orcs[c].sweep(it, s[c], order[c], n1, hyp[c][0], hyp[c][1], flags=None if fl is None else np.split(fl, Dcum), trace=True)
-            bad = np.where(~np.isclose(rg["trace"][c], ro["trace"], rtol=1e-9, atol=1e-9).all(axis=1))[0]
-            assert bad.size == 0, f"chain {c} iteration {it} (kernel {kern[c]}): first diverging swept observation {bad[0]}: gpu={rg['trace'][c][bad[0]]} cpu={ro['trace'][bad[0]]}"
-            assert (rg["s"][c] == ro["s"]).all() and int(rg["p_star"][c]) == ro["p_star"]
-            assert np.allclose(rg["logweight"][c], ro["logweight"], rtol=1e-9, atol=1e-8)
-            for key in ("n_operations", "n_resamples", "n_clones", "max_id", "sum_classes"):
-                assert rg["stats"][c][key] == ro["stats"][key], key
-            up, mv = orcs[c].work()
-            assert (wk[c][:, 1] == up).all() and (wk[c][:, 3] == mv).all()
-            check_work_counters(wk[c], recs[c], ro["trace"], N, int(kern[c]))
-            eg, eo = sw.export_state(c), orcs[c].export()
-            assert (eg["particle"] == eo["particle"]).all() and (eg["max_id"] == eo["max_id"]).all()
-            t5_invariants(eg, N, P, K, n)
+            check_sweep_against_oracle(chain_result(rg, c), ro, wk[c], orcs[c].work(), recs[c], N, int(kern[c]), where=f"chain {c} iteration {it} (kernel {kern[c]})")
+            check_state_against_oracle(sw.export_state(c), orcs[c].export(), N, P, K, n)
             seen.add(int(kern[c]))
+            # the steps that kernel can have swept: up to the first that starts with more particle classes than its tables hold; the
+            # most columns a step holds (before its ESS test), the largest id at its start and the largest it can reach (a clone
+            # takes the next id)
+            over = np.where((recs[c][:, :, 0] > lay["s2"]["cls"]).any(axis=1))[0]
+            rec = recs[c][:over[0] + 1] if over.size else recs[c]
+            cols, ids, ids_hi = np.maximum(rec[:, :, 4], rec[:, :, 5]), rec[:, :, 6], rec[:, :, 6] + rec[:, :, 3]
+            inside += int(((cols <= cols_l) & (ids_hi < idcap)).sum())
+            beyond += int(((cols > cols_l) & (ids >= idcap)).sum())
+            steps += cols.size
+            if over.size:
+                assert kern[c] == 2, (it, c, over[0], kern[c])
             s[c] = ro["s"]
     gb = sw.given_back()
+    print(f"{'+'.join(kinds)} P={P} tables={tables}: layout {lay['s2']}, hand-over group {lay['handover']}; of the {steps} (step, dataset) pairs the "
+          f"settled-chain kernel can have swept, inside both LDS tables {inside / steps:.2f}, beyond both {beyond / steps:.2f}")
+    if tables == "tiny":
+        assert beyond / steps >= 0.8
+    elif tables == "all-LDS":
+        assert inside == steps          # every column and id of every step that kernel can have swept was in LDS
     print(f"{'+'.join(kinds)} P={P}: kernels that finished the chain-sweeps {sorted(seen)}; hand-overs {gb.tolist()} of {4 * C} chain-sweeps")
     assert 2 in seen and gb[3] >= 2          # chains were handed over mid-sweep ...
     # ... and the counters mean what include/pmdi_hip.h says: [0] unused, [2] every hand-over (more classes than the capacity, or
