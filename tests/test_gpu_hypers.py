@@ -84,6 +84,26 @@ def test_hypers_kernel_equals_oracle(pkg, O, n, N, K):
     g.close(); sw.close(); hy.close()
 
 
+@pytest.mark.parametrize("n", [24576, 24577])
+def test_shuffle_in_lds_and_in_global_memory_equals_oracle(pkg, O, n):
+    """shuffle!(order_obs) (src/pmdi.jl:172) either side of the size at which order_obs no longer fits the 96 KiB of LDS the shuffle
+    may use (4 n bytes: n = 24 576 is the last in LDS, n = 24 577 the first shuffled in global memory), two chains, two iterations."""
+    rng = np.random.default_rng(n)
+    N, K = 3, 1
+    _, _, sw, g = _mk(pkg, O, rng, n, N, K, P=2, seed=13, chains=2)
+    hys = [O.Hypers(n, N, K, seed=13 + c) for c in range(2)]
+    for it in range(1, 3):
+        g.step(pkg.STEP_BEGIN); g.step(pkg.STEP_HYPERS)
+        for c, hy in enumerate(hys):
+            hy.step(it)
+            order = g.get(c)["order"]
+            assert (np.sort(order) == np.arange(1, n + 1)).all(), "not a permutation"
+            assert (order == np.array(hy.order)).all(), f"order_obs differs (chain {c}, iteration {it})"
+    for hy in hys:
+        hy.close()
+    g.close(); sw.close()
+
+
 @pytest.mark.parametrize("n,N,K,phi", [(400, 6, 2, 3.0), (500, 5, 3, 1.0), (600, 10, 4, 10.0), (300, 4, 5, 0.3), (2000, 30, 3, 2.0),
                                         (1000, 50, 4, 5.0), (3000, 100, 2, 4.0), (2000, 128, 3, 6.0), (3000, 255, 2, 4.0)])
 def test_align_kernel_equals_oracle(pkg, O, n, N, K, phi):
