@@ -4,6 +4,7 @@ There is no CPU fallback in this package: if the HIP library is missing or no
 gfx950 device is usable, the calls raise.
 """
 import ctypes as C
+import glob
 import os
 import subprocess
 
@@ -12,13 +13,9 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("PMDI_LIB_PATH") or os.path.join(_PKG, "libpmdi_hip.so")   # override: A/B builds only
-_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_fusion.hip", "pmdi_summary.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_psm_refine_vi.hip", "pmdi_psm_blocksum.hip", "pmdi_api.cpp", "pmdi_acc.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
-_HEADERS = [os.path.join(_PKG, "csrc", "pmdi_internal.h"), os.path.join(_PKG, "csrc", "pmdi_device.h"),
-            os.path.join(_PKG, "csrc", "pmdi_sweep_body.h"), os.path.join(_PKG, "csrc", "pmdi_sweep2_body.h"),
-            os.path.join(_PKG, "csrc", "pmdi_arith.h"), os.path.join(_PKG, "csrc", "pmdi_psm_device.h"),
-            os.path.join(_PKG, "csrc", "pmdi_host.h"), os.path.join(_PKG, "csrc", "pmdi_vi_log2_table.h"),
-            os.path.join(_PKG, "csrc", "pmdi_psm_blocksum_plan.h"),
-            os.path.join(_ROOT, "include", "pmdi_hip.h")]
+_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_fusion.hip", "pmdi_summary.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_psm_refine_vi.hip", "pmdi_psm_blocksum.hip", "pmdi_api.cpp", "pmdi_plan.cpp", "pmdi_acc.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
+# every header decides when to rebuild: a new one cannot be forgotten
+_HEADERS = sorted(glob.glob(os.path.join(_PKG, "csrc", "*.h"))) + [os.path.join(_ROOT, "include", "pmdi_hip.h")]
 
 GAUSSIAN, CATEGORICAL, NEGBINOM = 0, 1, 2
 KIND_BY_NAME = {"gaussian": GAUSSIAN, "categorical": CATEGORICAL, "negbinom": NEGBINOM,

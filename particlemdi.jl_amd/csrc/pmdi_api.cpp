@@ -5,6 +5,7 @@
 // compute entry point runs on the gfx950 device or fails.
 #include "pmdi_host.h"
 #include "pmdi_psm_blocksum_plan.h"
+#include "pmdi_sweep_carve.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -146,25 +147,43 @@ void fill_sweep_common(const pmdi_handle *h, SweepArgs &a)
     a.K = h->cfg.K; a.N = h->cfg.N; a.P = h->cfg.P; a.cap = (int)h->cap;
     a.Dmax = h->Dmax; a.sumD = h->sumD; a.npairs = h->npairs;
     a.q1 = h->cfg.q1_mode; a.q2 = h->cfg.q2_mode;
-    a.terms_cap = h->terms_cap;
+    const SweepPlan &pl = h->plan;
+    pmdi_put_tables(pl.wide, a);
     a.item_cap = h->cfg.N > 32 ? PMDI_ITEM_CAP_BIGN : PMDI_ITEM_CAP;
-    a.pid_lds = h->pid_lds; a.pp_lds = h->pp_lds; a.col_lds = h->col_lds; a.two_per_cu = h->two_per_cu;
-    a.phase = h->phase_on ? (long long *)h->d_phase.p : nullptr;
+    a.two_per_cu = pl.two_per_cu;
+    a.phase = pl.phase_on ? (long long *)h->d_phase.p : nullptr;
     a.cost = (long long *)h->d_cost.p;
     a.work = (long long *)h->d_work.p;
     a.anclog = (int *)h->d_anclog.p; a.evpos = (int *)h->d_evpos.p;
-    a.ksplit = h->ksplit; a.xcnt = (int *)h->d_xcnt.p; a.xinc = (double *)h->d_xinc.p; a.xlab = (int *)h->d_xlab.p; a.xhdr = (unsigned long long *)h->d_xhdr.p;
+    a.ksplit = pl.ksplit; a.xcnt = (int *)h->d_xcnt.p; a.xinc = (double *)h->d_xinc.p; a.xlab = (int *)h->d_xlab.p; a.xhdr = (unsigned long long *)h->d_xhdr.p;
     a.chain_order = h->have_order ? (const int *)h->d_lorder.p : nullptr;
-    a.s2 = h->s2;
-    a.requeue = h->s2_ok ? (int *)h->d_requeue.p : nullptr;
-    a.requeue_total = h->s2_ok ? (long long *)h->d_requeue_total.p : nullptr;
-    a.handed = h->s2_ok ? (int *)h->d_handed.p : nullptr;
+    a.s2 = pl.s2;
+    a.requeue = pl.s2_ok ? (int *)h->d_requeue.p : nullptr;
+    a.requeue_total = pl.s2_ok ? (long long *)h->d_requeue_total.p : nullptr;
+    a.handed = pl.s2_ok ? (int *)h->d_handed.p : nullptr;
     a.sweep_no = h->sweep_no;
     a.swept_by = (int *)h->d_swept_by.p;
-    a.resume = (h->s2_ok && h->s2_continue) ? (int *)h->d_resume.p : nullptr;
+    a.resume = (pl.s2_ok && pl.s2_continue) ? (int *)h->d_resume.p : nullptr;
     a.n = h->cfg.n;
     a.seed = h->cfg.seed;
     for (int k = 0; k < h->cfg.K; ++k) a.ds[k] = h->ds[k];
+}
+
+// what a call of pmdi_sweep / pmdi_sweep_device adds to the handle's part of the argument block: its inputs and outputs (device
+// pointers; pstar / stats / err null: the handle's own buffers)
+void fill_sweep_call(const pmdi_handle *h, SweepArgs &a, int64_t iter, int64_t n1, double lw_init, const int *s_in, const int *order,
+                     const double *Pi, const double *logphi, const unsigned char *flags, int *s_out, double *lw_out, int *pstar,
+                     long long *stats, int *err, double *trace)
+{
+    fill_sweep_common(h, a);
+    a.iter = (unsigned)iter; a.n1 = n1; a.lw_init = lw_init;
+    a.s_in = s_in; a.order = order; a.Pi = Pi; a.logphi = logphi; a.flags = flags;
+    a.s_out = s_out; a.lw_out = lw_out;
+    a.pstar = pstar ? pstar : (int *)h->d_pstar.p;
+    a.stats = stats ? stats : (long long *)h->d_stats.p;
+    a.err = err ? err : (int *)h->d_err.p;
+    a.trace = trace; a.trace_on = trace ? 1 : 0;
+    a.uscratch = (double *)h->d_usc.p; a.partstar = (int *)h->d_partstar.p; a.kstate = (int *)h->d_kstate.p;
 }
 
 // next pinned staging slot of the handle's ring (waits -- normally not at all -- for the copy that last used it)
@@ -192,11 +211,12 @@ hipError_t launch_one(pmdi_handle *h, const SweepArgs &a, SweepArgs *d_args, int
 // one after the other (a chain whose partners straddle the residency limit would spin until some other chain's whole sweep ends)
 hipError_t launch_maybe_batched(pmdi_handle *h, const SweepArgs &a, SweepArgs *d_args, int n_chains, int T, hipStream_t st)
 {
-    if (!a.ksplit || h->ksplit_batch <= 0 || n_chains <= h->ksplit_batch) return launch_one(h, a, d_args, n_chains, T, st);
-    for (int b0 = 0; b0 < n_chains; b0 += h->ksplit_batch) {
+    const int batch = h->plan.ksplit_batch;
+    if (!a.ksplit || batch <= 0 || n_chains <= batch) return launch_one(h, a, d_args, n_chains, T, st);
+    for (int b0 = 0; b0 < n_chains; b0 += batch) {
         SweepArgs ab = a;
         ab.n_slots = n_chains; ab.slot_base = b0;
-        const int nb = (n_chains - b0 < h->ksplit_batch) ? n_chains - b0 : h->ksplit_batch;
+        const int nb = (n_chains - b0 < batch) ? n_chains - b0 : batch;
         hipError_t e = launch_one(h, ab, d_args, nb, T, st);
         if (e != hipSuccess) return e;
     }
@@ -209,25 +229,27 @@ hipError_t launch_maybe_batched(pmdi_handle *h, const SweepArgs &a, SweepArgs *d
 int launch_sweep_groups(pmdi_handle *h, SweepArgs &a, hipStream_t st)
 {
     const int C = h->cfg.n_chains;
+    const SweepPlan &pl = h->plan;
+    auto args = [&](int which) { return (SweepArgs *)h->d_args[which].p; };
     hipError_t e;
     a.err_keep = h->err_keep;
     a.sweep_no = ++h->sweep_no;        // (counts the sweeps of this handle: how long ago was a chain given back?)
     // nobody is on the list of given-back chains when a sweep starts (a chain whose re-run failed must not be swept by two launches
     // of the next sweep at once)
-    if (h->s2_ok) HIP_TRY(hipMemsetAsync(h->d_requeue.p, 0, (size_t)C * 4, st));
-    if (h->ksplit) {       // arrival counters of the hand-offs; the K workgroups of a chain ADD their counters into stats
+    if (pl.s2_ok) HIP_TRY(hipMemsetAsync(h->d_requeue.p, 0, (size_t)C * 4, st));
+    if (pl.ksplit) {       // arrival counters of the hand-offs; the K workgroups of a chain ADD their counters into stats
         HIP_TRY(hipMemsetAsync(h->d_xcnt.p, 0, (size_t)C * 32 * 4, st));
         HIP_TRY(hipMemsetAsync(a.stats, 0, (size_t)C * 64, st));
         if (!h->err_keep) HIP_TRY(hipMemsetAsync(a.err, 0, (size_t)C * 4, st));
     }
-    if (!h->split) {
-        e = launch_maybe_batched(h, a, (SweepArgs *)h->d_args.p, C, h->T, st);
+    if (!pl.split) {
+        e = launch_maybe_batched(h, a, args(ARGS_MAIN), C, pl.T, st);
         if (e != hipSuccess) return fail(PMDI_E_DEVICE, "sweep launch: %s", hipGetErrorString(e));
     } else {
         HIP_TRY(hipEventRecord(h->ev_fork, st));
         a.group_flag = (const unsigned char *)h->d_group.p;
         a.group_sel = 1;
-        const int vh = h->very_heavy < C ? h->very_heavy : C;
+        const int vh = pl.very_heavy < C ? pl.very_heavy : C;
         if (vh > 0) {
             // the heaviest chains bound the launch: they get the 256-register build, one CU each
             SweepArgs av = a;
@@ -237,9 +259,9 @@ int launch_sweep_groups(pmdi_handle *h, SweepArgs &a, hipStream_t st)
             // smaller workgroups would take a slot on every CU first and the heaviest chains -- the ones that bound the sweep --
             // would start late, one by one, whenever a CU happens to drain (measured at cfg2: 1 020 ms for a launch whose chains
             // take 550 ms).  So its workgroups count themselves in on entry and the other launches wait for that count.
-            const bool gate = h->start_sig != nullptr && !h->ksplit;
+            const bool gate = h->start_sig != nullptr && !pl.ksplit;
             if (gate) av.start_sig = h->start_sig;      // (zero here: reset on `st` behind the previous sweep's join, below)
-            e = launch_one(h, av, (SweepArgs *)h->d_args3.p, vh, h->T, h->stream3);
+            e = launch_one(h, av, args(ARGS_HEAVIEST), vh, pl.T, h->stream3);
             if (e != hipSuccess) return fail(PMDI_E_DEVICE, "sweep launch (heaviest chains): %s", hipGetErrorString(e));
             HIP_TRY(hipEventRecord(h->ev_join3, h->stream3));
             if (gate) {
@@ -250,57 +272,240 @@ int launch_sweep_groups(pmdi_handle *h, SweepArgs &a, hipStream_t st)
             }
         }
         a.rank_lo = vh; a.rank_hi = C;
-        e = launch_maybe_batched(h, a, (SweepArgs *)h->d_args.p, C, h->T, st);
+        e = launch_maybe_batched(h, a, args(ARGS_MAIN), C, pl.T, st);
         if (e != hipSuccess) return fail(PMDI_E_DEVICE, "sweep launch (heavy group): %s", hipGetErrorString(e));
         if (vh > 0) HIP_TRY(hipStreamWaitEvent(st, h->ev_join3, 0));
         SweepArgs al = a;
         al.group_sel = 0; al.rank_lo = 0; al.rank_hi = C;
-        al.terms_cap = h->l_terms_cap; al.pid_lds = h->l_pid_lds; al.pp_lds = h->l_pp_lds; al.col_lds = h->l_col_lds;
+        pmdi_put_tables(pl.light, al);
         HIP_TRY(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-        if (h->s2_ok) {
+        if (pl.s2_ok) {
             // the light chains go to the settled-chain kernel.  A chain whose step does not fit its tables is carried on from that
             // observation by the general kernel's code in the same workgroup: the argument block holds the general kernel's LDS
             // layout for that workgroup width
-            al.terms_cap = h->r_terms_cap; al.pid_lds = h->r_pid_lds; al.pp_lds = h->r_pp_lds; al.col_lds = h->r_col_lds;
+            pmdi_put_tables(pl.resume, al);
             int idx;
             SweepArgs *slot = next_slot(h, h->stream2, &idx);
             SweepArgs as = al;
             // its workgroups draw their positions in the launch order instead of taking blockIdx.x (SweepArgs::ticket; PMDI_TICKET=0: dealt)
             as.ticket = (h->tun.ticket != 0) ? (int *)h->d_ticket.p : nullptr;
-            e = pmdi_launch_sweep2(as, (SweepArgs *)h->d_args4.p, C, h->stream2, slot);
+            e = pmdi_launch_sweep2(as, args(ARGS_SETTLED), C, h->stream2, slot);
             if (e == hipSuccess && idx >= 0) { e = hipEventRecord(h->ring_ev[idx], h->stream2); h->ring_used[idx] = true; }
             if (e != hipSuccess) return fail(PMDI_E_DEVICE, "sweep launch (settled chains): %s", hipGetErrorString(e));
-            if (!h->s2_continue) {
+            if (!pl.s2_continue) {
                 // (PMDI_CONTINUE=0, the round-3 behaviour kept for A/B runs: no hand-over record; the chains that kernel gives back are
                 // swept again FROM THE START by the general kernel right behind it -- with one workgroup per dataset when the model has several)
                 SweepArgs ar = al;
                 ar.group_flag = nullptr; ar.requeue_only = 1;
-                ar.terms_cap = h->l_terms_cap; ar.pid_lds = h->l_pid_lds; ar.pp_lds = h->l_pp_lds; ar.col_lds = h->l_col_lds;
-                if (h->cfg.K > 1 && h->d_xcnt.p && h->tun.requeue_ksplit != 0) {
+                pmdi_put_tables(pl.light, ar);
+                if (h->cfg.K > 1 && h->d_xcnt.p && pl.requeue_ksplit) {
                     ar.ksplit = 1;
                     HIP_TRY(hipMemsetAsync(h->d_xcnt.p, 0, (size_t)C * 32 * 4, h->stream2));
                 }
-                e = launch_one(h, ar, (SweepArgs *)h->d_args5.p, C, 256, h->stream2);
+                e = launch_one(h, ar, args(ARGS_GIVEN_BACK), C, 256, h->stream2);
                 if (e != hipSuccess) return fail(PMDI_E_DEVICE, "sweep launch (chains given back by the settled-chain kernel): %s", hipGetErrorString(e));
             }
         } else {
-            e = launch_maybe_batched(h, al, (SweepArgs *)h->d_args2.p, C, 256, h->stream2);
+            e = launch_maybe_batched(h, al, args(ARGS_LIGHT), C, 256, h->stream2);
             if (e != hipSuccess) return fail(PMDI_E_DEVICE, "sweep launch (light group): %s", hipGetErrorString(e));
         }
         HIP_TRY(hipEventRecord(h->ev_join, h->stream2));
         HIP_TRY(hipStreamWaitEvent(st, h->ev_join, 0));
         // re-arm the start gate only here: `st` has now joined BOTH gated consumers (its own wait and stream2's), so neither can
         // still be waiting for the value that is being reset
-        if (vh > 0 && h->start_sig && !h->ksplit) HIP_TRY(hipStreamWriteValue32(st, h->start_sig, 0, 0));
+        if (vh > 0 && h->start_sig && !pl.ksplit) HIP_TRY(hipStreamWriteValue32(st, h->start_sig, 0, 0));
     }
-    if (C > 1 || h->split) {
+    if (C > 1 || pl.split) {
         const long long steps = (a.n - a.n1 + 1) * (long long)a.K;
         e = pmdi_launch_chain_order((const long long *)h->d_cost.p, (int *)h->d_lorder.p, a.stats,
-                                    h->split ? (unsigned char *)h->d_group.p : nullptr, h->light_ids * steps, C, st,
-                                    h->s2_ok ? (const int *)h->d_handed.p : nullptr, h->sweep_no + 3 - h->sticky);
+                                    pl.split ? (unsigned char *)h->d_group.p : nullptr, pl.light_ids * steps, C, st,
+                                    pl.s2_ok ? (const int *)h->d_handed.p : nullptr, h->sweep_no + 3 - pl.sticky);
         if (e != hipSuccess) return fail(PMDI_E_DEVICE, "chain-order launch: %s", hipGetErrorString(e));
         h->have_order = true;
     }
+    return PMDI_OK;
+}
+
+// ---- pmdi_create, in the order of its parts ----------------------------------------------------------------------------------
+
+// dataset k on the device: the data row-major, the host-built tables of its cluster type, the chains' arenas
+int upload_dataset(pmdi_handle *h, int k, const pmdi_dataset &src)
+{
+    const int N = h->cfg.N, P = h->cfg.P;
+    const long long n = h->cfg.n, cap = h->cap;
+    DsetDev &d = h->ds[k];
+    int rc = 0;
+    if (src.D < 1) return fail(PMDI_E_ARG, "dataset %d: D=%d", k, src.D);
+    if (src.ld < n) return fail(PMDI_E_ARG, "dataset %d: ld=%lld < n. Datasets don't have same number of observations.", k, (long long)src.ld);
+    d.kind = src.kind; d.D = src.D; d.L = 0; d.flag_off = h->sumD;
+    h->sumD += src.D;
+    if (src.D > h->Dmax) h->Dmax = src.D;
+    const int D = src.D;
+    if (src.kind == PMDI_GAUSSIAN) {
+        if (!src.xf) return fail(PMDI_E_ARG, "dataset %d: xf is null", k);
+        std::vector<double> x((size_t)n * D);
+        for (long long i = 0; i < n; ++i)
+            for (int q = 0; q < D; ++q) x[(size_t)i * D + q] = src.xf[(size_t)q * src.ld + i];
+        if ((rc = upload(h, x, &d.xf))) return rc;
+        // gaussian_cluster.jl:38-40 prefix and :76-79 constant, per cluster size
+        std::vector<double> g((size_t)n + 1), lm((size_t)n + 1);
+        for (long long m = 0; m <= n; ++m) {
+            const double nn = (double)m;
+            g[m] = (log(1.0 / sqrt(M_PI)) + lgamma(0.5 * nn + 1.0)) - lgamma(0.5 * nn + 0.5);
+            const double a_n = (nn / 2.0 + 0.5), a_0 = 0.5, b_0 = 0.5, k_0 = 0.001, k_n = nn + k_0;
+            lm[m] = (a_0 * log(b_0)) + lgamma(a_n) - lgamma(a_0) + 0.5 * (log(k_0) - log(k_n)) -
+                    (nn * 0.5) * log(2.0 * M_PI);
+        }
+        if ((rc = upload(h, g, &d.gtab))) return rc;
+        if ((rc = upload(h, lm, &d.lmtab))) return rc;
+    } else if (src.kind == PMDI_CATEGORICAL || src.kind == PMDI_NEGBINOM) {
+        if (!src.xi) return fail(PMDI_E_ARG, "dataset %d: xi is null", k);
+        std::vector<int> x((size_t)n * D);
+        std::vector<int> maxcol(D, 0);
+        std::vector<long long> colsum(D, 0);
+        long long gmax = 0;
+        for (long long i = 0; i < n; ++i)
+            for (int q = 0; q < D; ++q) {
+                const long long v = src.xi[(size_t)q * src.ld + i];
+                if (src.kind == PMDI_CATEGORICAL && v < 1) return fail(PMDI_E_DATA, "dataset %d: categorical level %lld < 1", k, v);
+                if (src.kind == PMDI_NEGBINOM && v < 0) return fail(PMDI_E_DATA, "dataset %d: negative count %lld", k, v);
+                if (v > 0x3fffffff) return fail(PMDI_E_DATA, "dataset %d: value %lld too large", k, v);
+                x[(size_t)i * D + q] = (int)v;
+                if (v > maxcol[q]) maxcol[q] = (int)v;
+                if (v > gmax) gmax = v;
+                colsum[q] += v;
+            }
+        if ((rc = upload(h, x, &d.xi))) return rc;
+        if (src.kind == PMDI_CATEGORICAL) {
+            if (gmax > 4096) return fail(PMDI_E_DATA, "dataset %d: %lld categorical levels (max 4096)", k, gmax);
+            d.L = (int)gmax;                                  // categorical_cluster.jl:8
+            if ((rc = upload(h, maxcol, &d.maxcol))) return rc;
+            std::vector<double> lh((size_t)(2 * n + gmax + 3)), lgh((size_t)(2 * (n + gmax) + 3));
+            for (size_t j = 0; j < lh.size(); ++j) lh[j] = log(0.5 * (double)j);
+            for (size_t j = 0; j < lgh.size(); ++j) lgh[j] = lgamma(0.5 * (double)j);
+            if ((rc = upload(h, lh, &d.lhtab))) return rc;
+            if ((rc = upload(h, lgh, &d.lghtab))) return rc;
+        } else {
+            long long smax = 0;
+            for (int q = 0; q < D; ++q) if (colsum[q] > smax) smax = colsum[q];
+            const long long len = n + gmax + smax + 8;
+            if (len > (1LL << 27)) return fail(PMDI_E_DATA, "dataset %d: NegBinom lgamma table of %lld entries is too large", k, len);
+            std::vector<double> lg((size_t)len);
+            for (long long m = 0; m < len; ++m) lg[m] = lgamma((double)m);
+            if ((rc = upload(h, lg, &d.lgtab))) return rc;
+            d.lgtab_len = len;
+        }
+    } else {
+        return fail(PMDI_E_ARG, "dataset %d: unknown kind %d", k, src.kind);
+    }
+    d.stride = layout_arena(d, N, P, cap, n, true);
+    void *arena = nullptr;
+    if ((rc = dev_alloc(h, &arena, d.stride * (size_t)h->cfg.n_chains))) return rc;
+    d.arena = (char *)arena;
+    if (hipMemset(arena, 0, d.stride * (size_t)h->cfg.n_chains) != hipSuccess) return fail(PMDI_E_DEVICE, "hipMemset failed");
+    return PMDI_OK;
+}
+
+// the streams and events of the heavy / light split, and the start gate's signal memory, as the plan asks
+int create_launch_objects(pmdi_handle *h)
+{
+    if (!h->plan.split) return PMDI_OK;
+    // the slow chains bound the launch, so their workgroups must not queue behind the many
+    // light ones: light launch on a low-priority stream, heaviest chains on a high-priority one
+    int prio_lo = 0, prio_hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);      // (least, greatest); greatest is the smaller number
+    if (hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, prio_lo) != hipSuccess ||
+        hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess ||
+        hipStreamCreateWithPriority(&h->stream3, hipStreamNonBlocking, prio_hi) != hipSuccess ||
+        hipEventCreateWithFlags(&h->ev_join3, hipEventDisableTiming) != hipSuccess)
+        return fail(PMDI_E_DEVICE, "stream/event creation failed");
+    void *sig = nullptr;
+    if (h->plan.want_gate && hipExtMallocWithFlags(&sig, 8, hipMallocSignalMemory) == hipSuccess) {
+        h->start_sig = (unsigned *)sig; h->owned.push_back(sig);
+        (void)hipMemset(sig, 0, 8);
+    }
+    return PMDI_OK;
+}
+
+// per-chain state and scratch of the sweep launches
+int alloc_sweep_state(pmdi_handle *h)
+{
+    const int K = h->cfg.K, P = h->cfg.P;
+    const long long n = h->cfg.n;
+    int rc = 0;
+    const int C = h->cfg.n_chains;
+    for (DevBuf &b : h->d_args) if ((rc = b.ensure(sizeof(SweepArgs)))) return rc;
+    if ((rc = h->d_usc.ensure((size_t)C * K * P * 8)) || (rc = h->d_partstar.ensure((size_t)C * K * P * 4)) ||
+        (rc = h->d_kstate.ensure((size_t)C * PMDI_KMAX_I * 2 * 4)) || (rc = h->d_err.ensure((size_t)C * 4)) ||
+        (rc = h->d_stats.ensure((size_t)C * 8 * 8)) || (rc = h->d_pstar.ensure((size_t)C * 4)) ||
+        (rc = h->d_phase.ensure((size_t)C * 16 * 8)) ||
+        (rc = h->d_cost.ensure((size_t)C * 8)) || (rc = h->d_work.ensure((size_t)C * PMDI_KMAX_I * 8 * 8)) || (rc = h->d_lorder.ensure((size_t)C * 4)) || (rc = h->d_ticket.ensure(((size_t)C + 1) * 4)) ||
+        (rc = h->d_group.ensure((size_t)C)) || (rc = h->d_requeue.ensure((size_t)C * 4)) ||
+        (rc = h->d_requeue_total.ensure(4 * 8)) || (rc = h->d_handed.ensure((size_t)C * 4)) || (rc = h->d_swept_by.ensure((size_t)C * 4)) ||
+        (rc = h->d_resume.ensure((size_t)C * 16 * 4)))
+        return rc;
+    if (hipMemset(h->d_swept_by.p, 0, (size_t)C * 4) != hipSuccess) return fail(PMDI_E_DEVICE, "hipMemset failed");
+    {
+        std::vector<int> never((size_t)C, -1000);
+        if (hipMemcpy(h->d_handed.p, never.data(), (size_t)C * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(PMDI_E_DEVICE, "memcpy failed");
+    }
+    if (hipMemset(h->d_requeue.p, 0, (size_t)C * 4) != hipSuccess || hipMemset(h->d_requeue_total.p, 0, 32) != hipSuccess)
+        return fail(PMDI_E_DEVICE, "hipMemset failed");
+    if (h->plan.want_xchg && ((rc = h->d_xcnt.ensure((size_t)C * 32 * 4)) || (rc = h->d_xinc.ensure((size_t)C * 2 * K * P * 8)) ||
+                      (rc = h->d_xlab.ensure((size_t)C * 2 * K * P * 4)) || (rc = h->d_xhdr.ensure((size_t)C * 2 * K * 16))))
+        return rc;
+    if (h->cfg.q2_mode == 1 &&       // ancestor log of the resampling events: up to one per swept observation
+        ((rc = h->d_anclog.ensure((size_t)C * (size_t)n * P * 4)) || (rc = h->d_evpos.ensure((size_t)C * 2 * (size_t)n * 4))))
+        return rc;
+    // first sweep: every chain is heavy (PMDI_SETTLED=2: every chain starts on the settled-chain kernel -- tests of its hand-back path)
+    if (hipMemset(h->d_group.p, (h->plan.s2_ok && h->tun.settled == 2) ? 0 : 1, (size_t)C) != hipSuccess)
+        return fail(PMDI_E_DEVICE, "hipMemset failed");
+    return PMDI_OK;
+}
+
+// pinned staging ring of the argument blocks (asynchronous launches); without it the copies fall back to pageable memory
+void alloc_staging_ring(pmdi_handle *h)
+{
+    void *ring = nullptr;
+    if (hipHostMalloc(&ring, sizeof(SweepArgs) * pmdi_handle::RING, hipHostMallocDefault) == hipSuccess) {
+        h->ring = (SweepArgs *)ring;
+        for (int i = 0; i < pmdi_handle::RING; ++i)
+            if (hipEventCreateWithFlags(&h->ring_ev[i], hipEventDisableTiming) != hipSuccess) {
+                for (int j = 0; j < i; ++j) { (void)hipEventDestroy(h->ring_ev[j]); h->ring_ev[j] = nullptr; }
+                (void)hipHostFree(ring); h->ring = nullptr;
+                break;
+            }
+    }
+}
+
+// null-cluster marginal (src/pmdi.jl:120-128): all rows in one cluster, all features on
+int null_marginal(pmdi_handle *h)
+{
+    const int K = h->cfg.K, N = h->cfg.N, C = h->cfg.n_chains;
+    const long long n = h->cfg.n;
+    int rc = 0;
+    std::vector<int> traj((size_t)K * n, 0);
+    if ((rc = h->d_traj.ensure((size_t)C * K * n * 4)) || (rc = h->d_lm.ensure((size_t)C * h->sumD * N * 8)) ||
+        (rc = h->d_firstpos.ensure((size_t)C * K * N * 4)) || (rc = h->d_fnull.ensure((size_t)h->sumD * 8)) ||
+        (rc = h->d_fflags.ensure((size_t)C * h->sumD)) || (rc = h->d_fprob.ensure((size_t)C * h->sumD * 8)))
+        return rc;
+    if (hipMemcpy(h->d_traj.p, traj.data(), traj.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(PMDI_E_DEVICE, "memcpy failed");
+    std::vector<double> zero((size_t)h->sumD, 0.0);
+    if (hipMemcpy(h->d_fnull.p, zero.data(), zero.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return fail(PMDI_E_DEVICE, "memcpy failed");
+    FeatSelArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    fa.K = K; fa.N = 1; fa.sumD = h->sumD; fa.n = n; fa.iter = 0; fa.seed = h->cfg.seed;
+    for (int k = 0; k < K; ++k) fa.ds[k] = h->ds[k];
+    fa.traj = (const int *)h->d_traj.p; fa.lm = (double *)h->d_lm.p; fa.firstpos = (int *)h->d_firstpos.p;
+    fa.fnull = (const double *)h->d_fnull.p; fa.flags_out = (unsigned char *)h->d_fflags.p; fa.prob_out = (double *)h->d_fprob.p;
+    hipError_t e = pmdi_launch_featsel(fa, 1, h->stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "null-marginal launch: %s", hipGetErrorString(e));
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(PMDI_E_DEVICE, "null-marginal kernel failed");
+    std::vector<double> lm((size_t)h->sumD);
+    if (hipMemcpy(lm.data(), h->d_lm.p, lm.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(PMDI_E_DEVICE, "memcpy failed");
+    for (double &v : lm) v = -v;                               // featureNull = -calc_logmarginal (:127)
+    if (hipMemcpy(h->d_fnull.p, lm.data(), lm.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return fail(PMDI_E_DEVICE, "memcpy failed");
     return PMDI_OK;
 }
 
@@ -345,17 +550,13 @@ int pmdi_destroy(pmdi_handle *h)
     for (int i = 0; i < pmdi_handle::RING; ++i) if (h->ring_ev[i]) (void)hipEventDestroy(h->ring_ev[i]);
     if (h->ring) (void)hipHostFree(h->ring);
     for (void *p : h->owned) (void)hipFree(p);
-    DevBuf *bufs[] = {&h->d_s_in, &h->d_order, &h->d_Pi, &h->d_logphi, &h->d_flags, &h->d_s_out, &h->d_lw,
-                      &h->d_pstar, &h->d_stats, &h->d_err, &h->d_trace, &h->d_usc, &h->d_partstar, &h->d_kstate, &h->d_phase, &h->d_args, &h->d_args2, &h->d_args3, &h->d_args4, &h->d_args5, &h->d_requeue, &h->d_requeue_total, &h->d_handed, &h->d_group, &h->d_cost, &h->d_lorder, &h->d_ticket, &h->d_work, &h->d_anclog, &h->d_evpos, &h->d_xcnt, &h->d_xinc, &h->d_xlab, &h->d_xhdr,
-                      &h->d_swept_by, &h->d_resume, &h->d_traj, &h->d_lm, &h->d_firstpos, &h->d_fnull, &h->d_fflags, &h->d_fprob};
-    for (DevBuf *b : bufs) b->release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
     if (h->stream3) { (void)hipStreamSynchronize(h->stream3); (void)hipStreamDestroy(h->stream3); }
     if (h->ev_join3) (void)hipEventDestroy(h->ev_join3);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    delete h;
+    delete h;                   // (frees every DevBuf of the handle: its device is current)
     return PMDI_OK;
 }
 
@@ -395,328 +596,25 @@ int pmdi_create(const pmdi_config *cfg, const pmdi_dataset *datasets, pmdi_handl
     h->cfg = *cfg;
     if (cfg->tuning) h->tun = *cfg->tuning; else pmdi_tuning_default(&h->tun);
     h->cfg.tuning = nullptr;
-    const pmdi_tuning &tn = h->tun;
     h->cap = cap;
     h->npairs = K > 1 ? K * (K - 1) / 2 : 1;
     int rc = 0;
     auto bail = [&](int code) { pmdi_destroy(h); return code; };
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(PMDI_E_DEVICE, "hipStreamCreate failed"));
 
-    int flag_off = 0;
-    for (int k = 0; k < K; ++k) {
-        const pmdi_dataset &src = datasets[k];
-        DsetDev &d = h->ds[k];
-        if (src.D < 1) return bail(fail(PMDI_E_ARG, "dataset %d: D=%d", k, src.D));
-        if (src.ld < n) return bail(fail(PMDI_E_ARG, "dataset %d: ld=%lld < n. Datasets don't have same number of observations.", k, (long long)src.ld));
-        d.kind = src.kind; d.D = src.D; d.L = 0; d.flag_off = flag_off;
-        flag_off += src.D;
-        if (src.D > h->Dmax) h->Dmax = src.D;
-        const int D = src.D;
-        if (src.kind == PMDI_GAUSSIAN) {
-            if (!src.xf) return bail(fail(PMDI_E_ARG, "dataset %d: xf is null", k));
-            std::vector<double> x((size_t)n * D);
-            for (long long i = 0; i < n; ++i)
-                for (int q = 0; q < D; ++q) x[(size_t)i * D + q] = src.xf[(size_t)q * src.ld + i];
-            if ((rc = upload(h, x, &d.xf))) return bail(rc);
-            // gaussian_cluster.jl:38-40 prefix and :76-79 constant, per cluster size
-            std::vector<double> g((size_t)n + 1), lm((size_t)n + 1);
-            for (long long m = 0; m <= n; ++m) {
-                const double nn = (double)m;
-                g[m] = (log(1.0 / sqrt(M_PI)) + lgamma(0.5 * nn + 1.0)) - lgamma(0.5 * nn + 0.5);
-                const double a_n = (nn / 2.0 + 0.5), a_0 = 0.5, b_0 = 0.5, k_0 = 0.001, k_n = nn + k_0;
-                lm[m] = (a_0 * log(b_0)) + lgamma(a_n) - lgamma(a_0) + 0.5 * (log(k_0) - log(k_n)) -
-                        (nn * 0.5) * log(2.0 * M_PI);
-            }
-            if ((rc = upload(h, g, &d.gtab))) return bail(rc);
-            if ((rc = upload(h, lm, &d.lmtab))) return bail(rc);
-        } else if (src.kind == PMDI_CATEGORICAL || src.kind == PMDI_NEGBINOM) {
-            if (!src.xi) return bail(fail(PMDI_E_ARG, "dataset %d: xi is null", k));
-            std::vector<int> x((size_t)n * D);
-            std::vector<int> maxcol(D, 0);
-            std::vector<long long> colsum(D, 0);
-            long long gmax = 0;
-            for (long long i = 0; i < n; ++i)
-                for (int q = 0; q < D; ++q) {
-                    const long long v = src.xi[(size_t)q * src.ld + i];
-                    if (src.kind == PMDI_CATEGORICAL && v < 1) return bail(fail(PMDI_E_DATA, "dataset %d: categorical level %lld < 1", k, v));
-                    if (src.kind == PMDI_NEGBINOM && v < 0) return bail(fail(PMDI_E_DATA, "dataset %d: negative count %lld", k, v));
-                    if (v > 0x3fffffff) return bail(fail(PMDI_E_DATA, "dataset %d: value %lld too large", k, v));
-                    x[(size_t)i * D + q] = (int)v;
-                    if (v > maxcol[q]) maxcol[q] = (int)v;
-                    if (v > gmax) gmax = v;
-                    colsum[q] += v;
-                }
-            if ((rc = upload(h, x, &d.xi))) return bail(rc);
-            if (src.kind == PMDI_CATEGORICAL) {
-                if (gmax > 4096) return bail(fail(PMDI_E_DATA, "dataset %d: %lld categorical levels (max 4096)", k, gmax));
-                d.L = (int)gmax;                                  // categorical_cluster.jl:8
-                if ((rc = upload(h, maxcol, &d.maxcol))) return bail(rc);
-                std::vector<double> lh((size_t)(2 * n + gmax + 3)), lgh((size_t)(2 * (n + gmax) + 3));
-                for (size_t j = 0; j < lh.size(); ++j) lh[j] = log(0.5 * (double)j);
-                for (size_t j = 0; j < lgh.size(); ++j) lgh[j] = lgamma(0.5 * (double)j);
-                if ((rc = upload(h, lh, &d.lhtab))) return bail(rc);
-                if ((rc = upload(h, lgh, &d.lghtab))) return bail(rc);
-            } else {
-                long long smax = 0;
-                for (int q = 0; q < D; ++q) if (colsum[q] > smax) smax = colsum[q];
-                const long long len = n + gmax + smax + 8;
-                if (len > (1LL << 27)) return bail(fail(PMDI_E_DATA, "dataset %d: NegBinom lgamma table of %lld entries is too large", k, len));
-                std::vector<double> lg((size_t)len);
-                for (long long m = 0; m < len; ++m) lg[m] = lgamma((double)m);
-                if ((rc = upload(h, lg, &d.lgtab))) return bail(rc);
-                d.lgtab_len = len;
-            }
-        } else {
-            return bail(fail(PMDI_E_ARG, "dataset %d: unknown kind %d", k, src.kind));
-        }
-        d.stride = layout_arena(d, N, P, cap, n, true);
-        void *arena = nullptr;
-        if ((rc = dev_alloc(h, &arena, d.stride * (size_t)cfg->n_chains))) return bail(rc);
-        d.arena = (char *)arena;
-        if (hipMemset(arena, 0, d.stride * (size_t)cfg->n_chains) != hipSuccess) return bail(fail(PMDI_E_DEVICE, "hipMemset failed"));
-    }
-    h->sumD = flag_off;
-    h->T = cfg->block_threads ? cfg->block_threads : (P >= 2048 ? 1024 : (P > 256 ? 512 : 256));
-    if (!cfg->block_threads && h->T > 256 && tn.heavy_threads > 0) h->T = tn.heavy_threads;   // tuning knob: width of the heavy group
-    if (h->T != 128 && h->T != 256 && h->T != 512 && h->T != 1024) return bail(fail(PMDI_E_ARG, "block_threads must be 128, 256, 512 or 1024"));
-    {
-        auto knob = [](int32_t v, int dflt) { return v >= 0 ? (int)v : dflt; };      // (-1 = automatic)
-        // (a step whose particle classes' (class, label) items outgrow the LDS tables takes the general route through global memory;
-        // one class always fits: N <= 255 < 384)
-        if (N > (N > 32 ? PMDI_ITEM_CAP_BIGN : PMDI_ITEM_CAP)) return bail(fail(PMDI_E_ARG, "N=%d too large for the LDS tables", N));
-        // K > 1: one workgroup per (chain, dataset), meeting once per swept observation (pmdi_sweep.hip): 2.2x shorter sweeps per
-        // chain, but the partners repeat the per-observation serial work (weights, ESS, resampling indices), so when the chains alone
-        // can fill the GPU the single-workgroup form has the higher aggregate throughput.  Default: split while every workgroup of
-        // the split launch is RESIDENT at once -- decided below, after the LDS layout and the register-capped / uncapped build are
-        // known, from the occupancy of the kernel that will actually run (a chain whose K workgroups straddle the residency limit
-        // would spin in its hand-off until some other chain's whole sweep has ended).  PMDI_KSPLIT=0/1 forces either form (a forced
-        // split launch that is not resident at once goes out in residency-sized batches).  The history-permuting __pmdi mode
-        // (q2_mode = 1) always keeps the single-workgroup form: its ancestor log is per chain.
-        const bool ks_ok = K > 1 && cfg->q2_mode == 0 && (long long)K * n < (1LL << 27);
-        const int ks_env = tn.ksplit;
-        // ... unless the handle can have the settled-chain kernel (round 4): ONE workgroup of it sweeps a settled chain faster than the K
-        // cooperating workgroups of the general kernel do (HL, one chain alone on the GPU: 3.18 against 2.98-3.00 iterations/s,
-        // bench.py `one_chain_alone`), on a quarter of the workgroup slots
-        const bool s2_possible = knob(tn.settled, 1) != 0 && K >= 2 && cfg->block_threads == 0 && cfg->q1_mode == 0 && cfg->q2_mode == 0 &&
-                                 pmdi_sweep2_supports(K, N, P, h->Dmax, cap);
-        h->ksplit = (ks_ok && ks_env != 0 && !(ks_env < 0 && s2_possible)) ? 1 : 0;      // tentative: the layout below is the split form's
-        h->phase_on = tn.phase_timers > 0;
-        // per workgroup width: LDS term buffer (at least P doubles for the resampling weights, the
-        // per-wave CDF exchange areas, a few rows of 2*D+1) and which per-particle tables fit LDS
-        auto configure = [&](int T, int &terms_cap, int &pid_lds, int &pp_lds, int &col_lds) -> int {
-            int tc = knob(tn.terms_cap, 1024);
-            if (tc < P) tc = P;
-            if (tc < (T / 64) * (N > 64 ? 512 : 128)) tc = (T / 64) * (N > 64 ? 512 : 128);   // per-wave exchange areas of the CDF stage
-            if (tc < 4 * (2 * h->Dmax + 1)) tc = 4 * (2 * h->Dmax + 1);
-            if (tc < 384) tc = 384;                                   // the known-prefix label table (3 x 256 ints) lives there
-            terms_cap = tc;
-            SweepArgs a;
-            fill_sweep_common(h, a);
-            a.terms_cap = tc; a.pid_lds = 1; a.pp_lds = 1;
-            const int col_ok = 1;
-            a.col_lds = col_ok;
-            // Two chains per CU (<= 80 KiB each) hide each other's dependent latencies: +40 % aggregate throughput on the
-            // headline workload even with the per-particle tables in global memory.  So: the largest set of per-particle
-            // tables that still fits 80 KiB; if none does, one chain per CU with everything that fits 150 KiB in LDS.
-            const bool tgt = tn.lds_target >= 0;
-            const size_t half = 80 * 1024 - 256;      // half a CU's 160 KiB, less the kernel's static LDS (256 bytes of reduction scratch)
-            bool fits_half = false;
-            if (!tgt) {
-                // (what a step reads of them, most often first: the column indices -- every step --, the step scratch, the class ids
-                // -- only in steps with more than one particle class)
-                for (int opt = 0; opt < 4 && !fits_half; ++opt) {
-                    a.pid_lds = opt < 1; a.pp_lds = opt < 3; a.col_lds = (opt < 2) ? col_ok : 0;
-                    fits_half = pmdi_sweep_lds_bytes(a, T) <= half;
-                }
-            }
-            if (!fits_half) {
-                a.pid_lds = 1; a.pp_lds = 1; a.col_lds = col_ok;
-                const size_t lds_target = tgt ? (size_t)tn.lds_target : (size_t)150 * 1024;
-                if (pmdi_sweep_lds_bytes(a, T) > lds_target) a.pid_lds = 0;   // class ids of K*P particles do not fit: global memory
-                if (pmdi_sweep_lds_bytes(a, T) > lds_target) a.pp_lds = 0;    // nor does the per-particle step scratch
-                if (pmdi_sweep_lds_bytes(a, T) > lds_target) a.col_lds = 0;   // nor do the column indices
-            }
-            pid_lds = a.pid_lds; pp_lds = a.pp_lds; col_lds = a.col_lds;
-            if (pmdi_sweep_lds_bytes(a, T) > 160 * 1024)
-                return fail(PMDI_E_ARG, "configuration needs %zu bytes of LDS (> 160 KiB)", pmdi_sweep_lds_bytes(a, T));
-            return 0;
-        };
-        auto configure_wide = [&]() -> int {
-            h->two_per_cu = knob(tn.two_per_cu, 1);
-            const int r = configure(h->T, h->terms_cap, h->pid_lds, h->pp_lds, h->col_lds);
-            if (r) return r;
-            // one chain per CU anyway: the 256-register build (no spills) instead of the register-capped one
-            SweepArgs a;
-            fill_sweep_common(h, a);
-            if (tn.two_per_cu < 0 && pmdi_sweep_lds_bytes(a, h->T) > 80 * 1024 - 256) h->two_per_cu = 0;
-            return 0;
-        };
-        if ((rc = configure_wide())) return bail(rc);
-        if (h->ksplit) {
-            SweepArgs a;
-            fill_sweep_common(h, a);
-            int blocks = 0;
-            if (pmdi_sweep_blocks_per_cu(a, h->T, &blocks) != hipSuccess || blocks < 1) blocks = 1;
-            const long long capacity = (long long)blocks * prop.multiProcessorCount;
-            const long long grid = ((long long)(cfg->n_chains + 7) / 8) * 8 * K;       // chain slots are dealt in groups of eight
-            if (grid > capacity) {
-                if (ks_env < 0) {                        // default: the single-workgroup form (and its own LDS layout)
-                    h->ksplit = 0;
-                    if ((rc = configure_wide())) return bail(rc);
-                } else {                                 // forced: whole groups of eight chain slots that are resident together
-                    long long b = capacity / (8LL * K) * 8;
-                    h->ksplit_batch = (int)(b < 8 ? 8 : b);
-                }
-            }
-        }
-        // the settled-chain kernel: configurations of the shapes it is built for (any mix of the three cluster types), the reference's
-        // default quirk modes, one workgroup per chain; its LDS tables sized so that two 256-thread chains share a CU (fewer LDS columns /
-        // ids if need be); a 512-thread chain (P = 2 048) has a CU's registers to itself and may take its LDS too
-        {
-            // (K = 1: three of its four waves would idle through the cluster phases -- cfg2 runs 2 812 it/s on the general kernel's
-            // one-dataset build and 2 086 with this kernel; PMDI_SETTLED=2 forces it for the tests of its K = 1 instantiations)
-            bool ok = knob(tn.settled, 1) != 0 && (K >= 2 || knob(tn.settled, 1) == 2) && cfg->block_threads == 0 && !h->ksplit && cfg->q1_mode == 0 && cfg->q2_mode == 0 &&
-                      pmdi_sweep2_supports(K, N, P, h->Dmax, cap);
-            if (ok) {
-                const size_t budget = pmdi_sweep2_threads(K, P) > 256 ? (size_t)159 * 1024 : (size_t)80 * 1024;
-                int cols_l = knob(tn.s2_cols, 64), idcap = knob(tn.s2_idcap, 128);
-                if (cols_l < 1) cols_l = 1;
-                if (cols_l > P) cols_l = P;
-                if (idcap < 8) idcap = 8;
-                if (idcap > 4096) idcap = 4096;
-                // particle classes per dataset the LDS tables hold: as many as the budget allows, 32 at most (a step with more hands the
-                // chain over to the general kernel: with N labels a single ambiguous observation fans one class out into up to N)
-                int cls = knob(tn.s2_cls, 32);
-                if (cls < 16) cls = 16;
-                if (cls > pmdi_sweep2_max_classes(K, P)) cls = pmdi_sweep2_max_classes(K, P);
-                cls &= ~3;
-                // (the mutation-CDF rows of the class slots beyond the first 16 go to the chain's arena before the class count shrinks: a
-                // step with that many classes is rare, a hand-over costs the rest of the chain's sweep at the general kernel's speed)
-                int cdfl = cls;
-                pmdi_sweep2_layout(K, N, P, h->Dmax, cols_l, idcap, cls, cdfl, &h->s2);
-                if ((size_t)h->s2.total > budget && cls > 16 && pmdi_sweep2_cdf_arena(K, P)) { cdfl = 16; pmdi_sweep2_layout(K, N, P, h->Dmax, cols_l, idcap, cls, cdfl, &h->s2); }
-                while ((size_t)h->s2.total > budget && cls > 16) { cls -= 4; if (cdfl > cls) cdfl = cls; pmdi_sweep2_layout(K, N, P, h->Dmax, cols_l, idcap, cls, cdfl, &h->s2); }
-                while ((size_t)h->s2.total > budget && (cols_l > 16 || idcap > 64)) {
-                    // (a settled chain holds 6-40 columns and ids below ~40 at the 99th percentile of its steps: the id tables go first)
-                    if (idcap > 96) idcap -= 16; else if (cols_l > 32) cols_l -= 8; else if (idcap > 64) idcap -= 16; else cols_l -= 8;
-                    pmdi_sweep2_layout(K, N, P, h->Dmax, cols_l, idcap, cls, cdfl, &h->s2);
-                }
-                ok = (size_t)h->s2.total <= budget;
-            }
-            h->s2_ok = ok;
-        }
-        // automatic width: split the chains of a sweep into a heavy and a light launch
-        h->split = cfg->block_threads == 0 && (h->T > 256 || h->s2_ok) && knob(tn.split, 1) != 0;
-        if (!h->split) h->s2_ok = false;
-        // A chain is "light" when its last sweep met few live clusters per step.  With the settled-chain kernel: as many as that kernel's
-        // LDS id tables hold (it evaluates any number in place -- HL's busiest chains, 40-90 ids per step, run 20 % faster there than
-        // in the general kernel -- but a K = 1 chain that never resamples keeps thousands of private clusters, and those steps belong to
-        // the general kernel's hash tables: cfg2 with every chain light took 3.4 s per sweep instead of 0.8).  Without it: 40.
-        h->light_ids = knob(tn.light_ids, h->s2_ok ? h->s2.idcap : 40);
-        if (h->s2_ok && knob(tn.settled, 1) == 2) h->light_ids = 1LL << 40;      // (tests: every chain starts every sweep on the settled-chain kernel)
-        h->sticky = knob(tn.sticky, 3);
-        h->s2_continue = knob(tn.continue_inplace, 1) != 0;
-        if (h->split) {
-            if (configure(256, h->l_terms_cap, h->l_pid_lds, h->l_pp_lds, h->l_col_lds)) h->split = false;
-        }
-        if (h->split && h->s2_ok) {
-            const int thr = pmdi_sweep2_threads(K, P);
-            if (thr == 256) { h->r_terms_cap = h->l_terms_cap; h->r_pid_lds = h->l_pid_lds; h->r_pp_lds = h->l_pp_lds; h->r_col_lds = h->l_col_lds; }
-            else if (configure(thr, h->r_terms_cap, h->r_pid_lds, h->r_pp_lds, h->r_col_lds)) h->s2_continue = false;
-        }
-        if (!h->split) h->s2_ok = false;
-        if (h->split) {
-            // the slow chains bound the launch, so their workgroups must not queue behind the many
-            // light ones: light launch on a low-priority stream, heaviest chains on a high-priority one
-            int prio_lo = 0, prio_hi = 0;
-            (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);      // (least, greatest); greatest is the smaller number
-            if (hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, prio_lo) != hipSuccess ||
-                hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess ||
-                hipStreamCreateWithPriority(&h->stream3, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-                hipEventCreateWithFlags(&h->ev_join3, hipEventDisableTiming) != hipSuccess)
-                return bail(fail(PMDI_E_DEVICE, "stream/event creation failed"));
-            // (with the settled-chain kernel only the few chains it gave back lately are heavy at all: no CU-each launch for them --
-            // HL 1 160 it/s without against 1 146 with it -- and so no start gate either, which a profiler would switch off)
-            h->very_heavy = (h->T == 512 && h->two_per_cu) ? knob(tn.very_heavy, h->s2_ok ? 0 : 128) : 0;
-            int can_wait = 0;
-            (void)hipDeviceGetAttribute(&can_wait, hipDeviceAttributeCanUseStreamWaitValue, cfg->device);
-            // (not under a profiler that collects counters: rocprofv3 --pmc runs the kernels of all queues one at a time, and a launch
-            // that waits for another launch's workgroups then never starts -- observed as a hang of the FETCH_SIZE pass)
-            const bool profiled = tn.profiled > 0;
-            if (h->very_heavy > 0 && can_wait && !profiled && knob(tn.start_gate, 1) != 0) {
-                void *sig = nullptr;
-                if (hipExtMallocWithFlags(&sig, 8, hipMallocSignalMemory) == hipSuccess) {
-                    h->start_sig = (unsigned *)sig; h->owned.push_back(sig);
-                    (void)hipMemset(sig, 0, 8);
-                }
-            }
-        }
-    }
-    const int C = cfg->n_chains;
-    if ((rc = h->d_usc.ensure((size_t)C * K * P * 8)) || (rc = h->d_partstar.ensure((size_t)C * K * P * 4)) ||
-        (rc = h->d_kstate.ensure((size_t)C * PMDI_KMAX_I * 2 * 4)) || (rc = h->d_err.ensure((size_t)C * 4)) ||
-        (rc = h->d_stats.ensure((size_t)C * 8 * 8)) || (rc = h->d_pstar.ensure((size_t)C * 4)) ||
-        (rc = h->d_phase.ensure((size_t)C * 16 * 8)) || (rc = h->d_args.ensure(sizeof(SweepArgs))) ||
-        (rc = h->d_cost.ensure((size_t)C * 8)) || (rc = h->d_work.ensure((size_t)C * PMDI_KMAX_I * 8 * 8)) || (rc = h->d_lorder.ensure((size_t)C * 4)) || (rc = h->d_ticket.ensure(((size_t)C + 1) * 4)) ||
-        (rc = h->d_args2.ensure(sizeof(SweepArgs))) || (rc = h->d_args3.ensure(sizeof(SweepArgs))) || (rc = h->d_group.ensure((size_t)C)) ||
-        (rc = h->d_args4.ensure(sizeof(SweepArgs))) || (rc = h->d_args5.ensure(sizeof(SweepArgs))) || (rc = h->d_requeue.ensure((size_t)C * 4)) ||
-        (rc = h->d_requeue_total.ensure(4 * 8)) || (rc = h->d_handed.ensure((size_t)C * 4)) || (rc = h->d_swept_by.ensure((size_t)C * 4)) ||
-        (rc = h->d_resume.ensure((size_t)C * 16 * 4)))
+    for (int k = 0; k < K; ++k)
+        if ((rc = upload_dataset(h, k, datasets[k]))) return bail(rc);
+    PlanDevice dev;              // what the plan needs to know about the device
+    dev.cus = prop.multiProcessorCount;
+    int can_wait = 0;
+    (void)hipDeviceGetAttribute(&can_wait, hipDeviceAttributeCanUseStreamWaitValue, cfg->device);
+    dev.wait_value = can_wait != 0;
+    dev.blocks_per_cu = [](const SweepArgs &a, int T) { int blocks = 0; return pmdi_sweep_blocks_per_cu(a, T, &blocks) == hipSuccess ? blocks : 0; };
+    if ((rc = pmdi_plan_sweep(h->cfg, h->tun, h->Dmax, cap, dev, &h->plan)) ||
+        (rc = create_launch_objects(h)) || (rc = alloc_sweep_state(h)))
         return bail(rc);
-    if (hipMemset(h->d_swept_by.p, 0, (size_t)C * 4) != hipSuccess) return bail(fail(PMDI_E_DEVICE, "hipMemset failed"));
-    {
-        std::vector<int> never((size_t)C, -1000);
-        if (hipMemcpy(h->d_handed.p, never.data(), (size_t)C * 4, hipMemcpyHostToDevice) != hipSuccess) return bail(fail(PMDI_E_DEVICE, "memcpy failed"));
-    }
-    if (hipMemset(h->d_requeue.p, 0, (size_t)C * 4) != hipSuccess || hipMemset(h->d_requeue_total.p, 0, 32) != hipSuccess)
-        return bail(fail(PMDI_E_DEVICE, "hipMemset failed"));
-    {   // pinned staging ring of the argument blocks (asynchronous launches); without it the copies fall back to pageable memory
-        void *ring = nullptr;
-        if (hipHostMalloc(&ring, sizeof(SweepArgs) * pmdi_handle::RING, hipHostMallocDefault) == hipSuccess) {
-            h->ring = (SweepArgs *)ring;
-            for (int i = 0; i < pmdi_handle::RING; ++i)
-                if (hipEventCreateWithFlags(&h->ring_ev[i], hipEventDisableTiming) != hipSuccess) {
-                    for (int j = 0; j < i; ++j) { (void)hipEventDestroy(h->ring_ev[j]); h->ring_ev[j] = nullptr; }
-                    (void)hipHostFree(ring); h->ring = nullptr;
-                    break;
-                }
-        }
-    }
-    if ((h->ksplit || (h->s2_ok && K > 1 && (long long)K * n < (1LL << 27))) && ((rc = h->d_xcnt.ensure((size_t)C * 32 * 4)) || (rc = h->d_xinc.ensure((size_t)C * 2 * K * P * 8)) ||
-                      (rc = h->d_xlab.ensure((size_t)C * 2 * K * P * 4)) || (rc = h->d_xhdr.ensure((size_t)C * 2 * K * 16))))
-        return bail(rc);
-    if (cfg->q2_mode == 1 &&       // ancestor log of the resampling events: up to one per swept observation
-        ((rc = h->d_anclog.ensure((size_t)C * (size_t)n * P * 4)) || (rc = h->d_evpos.ensure((size_t)C * 2 * (size_t)n * 4))))
-        return bail(rc);
-    // first sweep: every chain is heavy (PMDI_SETTLED=2: every chain starts on the settled-chain kernel -- tests of its hand-back path)
-    if (hipMemset(h->d_group.p, (h->s2_ok && tn.settled == 2) ? 0 : 1, (size_t)C) != hipSuccess)
-        return bail(fail(PMDI_E_DEVICE, "hipMemset failed"));
-
-    // null-cluster marginal (src/pmdi.jl:120-128): all rows in one cluster, all features on
-    {
-        std::vector<int> traj((size_t)K * n, 0);
-        if ((rc = h->d_traj.ensure((size_t)C * K * n * 4)) || (rc = h->d_lm.ensure((size_t)C * h->sumD * N * 8)) ||
-            (rc = h->d_firstpos.ensure((size_t)C * K * N * 4)) || (rc = h->d_fnull.ensure((size_t)h->sumD * 8)) ||
-            (rc = h->d_fflags.ensure((size_t)C * h->sumD)) || (rc = h->d_fprob.ensure((size_t)C * h->sumD * 8)))
-            return bail(rc);
-        if (hipMemcpy(h->d_traj.p, traj.data(), traj.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return bail(fail(PMDI_E_DEVICE, "memcpy failed"));
-        std::vector<double> zero((size_t)h->sumD, 0.0);
-        if (hipMemcpy(h->d_fnull.p, zero.data(), zero.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return bail(fail(PMDI_E_DEVICE, "memcpy failed"));
-        FeatSelArgs fa;
-        memset(&fa, 0, sizeof(fa));
-        fa.K = K; fa.N = 1; fa.sumD = h->sumD; fa.n = n; fa.iter = 0; fa.seed = cfg->seed;
-        for (int k = 0; k < K; ++k) fa.ds[k] = h->ds[k];
-        fa.traj = (const int *)h->d_traj.p; fa.lm = (double *)h->d_lm.p; fa.firstpos = (int *)h->d_firstpos.p;
-        fa.fnull = (const double *)h->d_fnull.p; fa.flags_out = (unsigned char *)h->d_fflags.p; fa.prob_out = (double *)h->d_fprob.p;
-        hipError_t e = pmdi_launch_featsel(fa, 1, h->stream);
-        if (e != hipSuccess) return bail(fail(PMDI_E_DEVICE, "null-marginal launch: %s", hipGetErrorString(e)));
-        if (hipStreamSynchronize(h->stream) != hipSuccess) return bail(fail(PMDI_E_DEVICE, "null-marginal kernel failed"));
-        std::vector<double> lm((size_t)h->sumD);
-        if (hipMemcpy(lm.data(), h->d_lm.p, lm.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return bail(fail(PMDI_E_DEVICE, "memcpy failed"));
-        for (double &v : lm) v = -v;                               // featureNull = -calc_logmarginal (:127)
-        if (hipMemcpy(h->d_fnull.p, lm.data(), lm.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return bail(fail(PMDI_E_DEVICE, "memcpy failed"));
-    }
+    alloc_staging_ring(h);
+    if ((rc = null_marginal(h))) return bail(rc);
     *out = h;
     return PMDI_OK;
 }
@@ -724,7 +622,7 @@ int pmdi_create(const pmdi_config *cfg, const pmdi_dataset *datasets, pmdi_handl
 int pmdi_phase_timers(pmdi_handle *h, int32_t chain, int64_t *out16)
 {
     if (!h || !out16 || chain < 0 || chain >= h->cfg.n_chains) return fail(PMDI_E_ARG, "bad argument");
-    if (!h->phase_on) return fail(PMDI_E_STATE, "set PMDI_PHASE_TIMERS=1 before pmdi_create");
+    if (!h->plan.phase_on) return fail(PMDI_E_STATE, "set PMDI_PHASE_TIMERS=1 before pmdi_create");
     HIP_TRY(hipSetDevice(h->cfg.device));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out16, (char *)h->d_phase.p + (size_t)chain * 16 * 8, 16 * 8, hipMemcpyDeviceToHost));
@@ -752,8 +650,8 @@ int pmdi_work_counters(pmdi_handle *h, int64_t *out)
             for (int j = 0; j < 8; ++j) out[((size_t)c * K + k) * 8 + j] = w[((size_t)c * PMDI_KMAX_I + k) * 8 + j];
     return PMDI_OK;
 }
-int pmdi_block_threads(const pmdi_handle *h) { return h ? h->T : 0; }
-int pmdi_is_split(const pmdi_handle *h) { return h ? h->ksplit : 0; }
+int pmdi_block_threads(const pmdi_handle *h) { return h ? h->plan.T : 0; }
+int pmdi_is_split(const pmdi_handle *h) { return h ? h->plan.ksplit : 0; }
 int64_t pmdi_shader_clock_hz(const pmdi_handle *h)
 {
     if (!h) return 0;
@@ -766,31 +664,12 @@ int64_t pmdi_lds_bytes(const pmdi_handle *h)
     if (!h) return 0;
     SweepArgs a;
     fill_sweep_common(h, a);
-    return (int64_t)pmdi_sweep_lds_bytes(a, h->T);
+    return (int64_t)pmdi_sweep_lds_bytes(a, h->plan.T);
 }
 int pmdi_sweep_layout(const pmdi_handle *h, int32_t *out32)
 {
     if (!h || !out32) return fail(PMDI_E_ARG, "null argument");
-    for (int i = 0; i < 32; ++i) out32[i] = 0;
-    const bool handover = h->split && h->s2_ok && h->s2_continue;
-    const int g[3][5] = {
-        { h->T, h->terms_cap, h->pid_lds, h->pp_lds, h->col_lds },
-        { h->split ? 256 : 0, h->split ? h->l_terms_cap : 0, h->split ? h->l_pid_lds : 0, h->split ? h->l_pp_lds : 0, h->split ? h->l_col_lds : 0 },
-        { handover ? pmdi_sweep2_threads(h->cfg.K, h->cfg.P) : 0, handover ? h->r_terms_cap : 0, handover ? h->r_pid_lds : 0,
-          handover ? h->r_pp_lds : 0, handover ? h->r_col_lds : 0 },
-    };
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 5; ++j) out32[5 * i + j] = g[i][j];
-    out32[15] = h->two_per_cu; out32[16] = h->split ? 1 : 0; out32[17] = h->ksplit; out32[18] = h->ksplit_batch;
-    out32[19] = h->split ? h->very_heavy : 0;
-    out32[20] = (h->split && h->very_heavy > 0 && h->start_sig != nullptr && !h->ksplit) ? 1 : 0;
-    out32[21] = h->s2_ok ? 1 : 0;
-    if (h->s2_ok) {
-        out32[22] = h->s2.cols_l; out32[23] = h->s2.idcap; out32[24] = h->s2.cls; out32[25] = h->s2.cdfl;
-        out32[26] = pmdi_sweep2_threads(h->cfg.K, h->cfg.P); out32[27] = h->s2.total;
-        out32[28] = h->s2_continue ? 1 : 0;
-        out32[29] = (!h->s2_continue && h->cfg.K > 1 && h->d_xcnt.p && h->tun.requeue_ksplit != 0) ? 1 : 0;
-    }
+    pmdi_plan_layout32(h->plan, h->start_sig != nullptr, h->d_xcnt.p != nullptr, h->cfg.K, h->cfg.P, out32);
     return PMDI_OK;
 }
 int pmdi_sum_D(const pmdi_handle *h) { return h ? h->sumD : 0; }
@@ -799,13 +678,13 @@ int pmdi_settled_kernel(pmdi_handle *h, int64_t *given_back4)
     if (!h) return 0;
     if (given_back4) {
         given_back4[0] = given_back4[1] = given_back4[2] = given_back4[3] = 0;
-        if (h->s2_ok) {
+        if (h->plan.s2_ok) {
             if (hipSetDevice(h->cfg.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
                 hipMemcpy(given_back4, h->d_requeue_total.p, 32, hipMemcpyDeviceToHost) != hipSuccess)
                 return fail(PMDI_E_DEVICE, "pmdi_settled_kernel: reading the counters failed");
         }
     }
-    return h->s2_ok ? 1 : 0;
+    return h->plan.s2_ok ? 1 : 0;
 }
 int pmdi_chain_swept_by(pmdi_handle *h, int32_t *out)
 {
@@ -826,15 +705,7 @@ int pmdi_sweep_device(pmdi_handle *h, int64_t iter, const int32_t *s_in, const i
     if (n1 < 1 || n1 > h->cfg.n) return fail(PMDI_E_ARG, "n1=%lld outside 1..n (rho*n < 1 is undefined in the reference)", (long long)n1);
     HIP_TRY(hipSetDevice(h->cfg.device));
     SweepArgs a;
-    fill_sweep_common(h, a);
-    a.iter = (unsigned)iter; a.n1 = n1; a.lw_init = lw_init;
-    a.s_in = s_in; a.order = order_obs; a.Pi = Pi; a.logphi = log1p_phi; a.flags = feature_flag;
-    a.s_out = s_out; a.lw_out = logweight;
-    a.pstar = p_star ? p_star : (int *)h->d_pstar.p;
-    a.stats = stats ? (long long *)stats : (long long *)h->d_stats.p;
-    a.err = err ? err : (int *)h->d_err.p;
-    a.trace = nullptr; a.trace_on = 0;
-    a.uscratch = (double *)h->d_usc.p; a.partstar = (int *)h->d_partstar.p; a.kstate = (int *)h->d_kstate.p;
+    fill_sweep_call(h, a, iter, n1, lw_init, s_in, order_obs, Pi, log1p_phi, feature_flag, s_out, logweight, p_star, (long long *)stats, err, nullptr);
     hipStream_t st = (hipStream_t)stream;   // used verbatim: NULL is the device's default (null) stream
     const int lrc = launch_sweep_groups(h, a, st);
     if (lrc) return lrc;
@@ -1071,14 +942,9 @@ int pmdi_sweep(pmdi_handle *h, int64_t iter, const int64_t *s_in, const int64_t 
     if (feature_flag) HIP_TRY(hipMemcpyAsync(h->d_flags.p, feature_flag, (size_t)C * h->sumD, hipMemcpyHostToDevice, h->stream));
 
     SweepArgs a;
-    fill_sweep_common(h, a);
-    a.iter = (unsigned)iter; a.n1 = n1; a.lw_init = lw_init;
-    a.s_in = (const int *)h->d_s_in.p; a.order = (const int *)h->d_order.p; a.Pi = (const double *)h->d_Pi.p;
-    a.logphi = (const double *)h->d_logphi.p; a.flags = feature_flag ? (const unsigned char *)h->d_flags.p : nullptr;
-    a.s_out = (int *)h->d_s_out.p; a.lw_out = (double *)h->d_lw.p; a.pstar = (int *)h->d_pstar.p;
-    a.stats = (long long *)h->d_stats.p; a.err = (int *)h->d_err.p;
-    a.trace = trace ? (double *)h->d_trace.p : nullptr; a.trace_on = trace ? 1 : 0;
-    a.uscratch = (double *)h->d_usc.p; a.partstar = (int *)h->d_partstar.p; a.kstate = (int *)h->d_kstate.p;
+    fill_sweep_call(h, a, iter, n1, lw_init, (const int *)h->d_s_in.p, (const int *)h->d_order.p, (const double *)h->d_Pi.p,
+                    (const double *)h->d_logphi.p, feature_flag ? (const unsigned char *)h->d_flags.p : nullptr, (int *)h->d_s_out.p,
+                    (double *)h->d_lw.p, nullptr, nullptr, nullptr, trace ? (double *)h->d_trace.p : nullptr);
     if ((rc = launch_sweep_groups(h, a, h->stream))) return rc;
     std::vector<int> so(s32.size()), ps(C), er(C);
     std::vector<long long> stv((size_t)C * 8);
@@ -1209,9 +1075,8 @@ int pmdi_clusters_free(pmdi_cluster_batch *cb)
     if (!cb) return PMDI_OK;
     (void)hipSetDevice(cb->h->cfg.device);
     if (cb->arena) (void)hipFree(cb->arena);
-    cb->d_rows.release(); cb->d_flags.release(); cb->d_out.release();
     if (cb->h->children > 0) cb->h->children -= 1;
-    delete cb;
+    delete cb;                  // (and its DevBufs)
     return PMDI_OK;
 }
 

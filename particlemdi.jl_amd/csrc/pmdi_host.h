@@ -2,12 +2,12 @@
 // buffers, and the two handle types that more than one of them reads.  Host-only: no .hip file includes it.
 #pragma once
 #include "pmdi_internal.h"
+#include "pmdi_plan.h"
 #include "../../include/pmdi_hip.h"
 
 #include <vector>
 
-// sets the text of pmdi_last_error for this thread and returns `code` (pmdi_api.cpp)
-int pmdi_set_error(int code, const char *fmt, ...);
+// pmdi_set_error (declared in pmdi_plan.h; pmdi_api.cpp): sets the text of pmdi_last_error for this thread and returns `code`
 constexpr auto fail = pmdi_set_error;       // (the name at the call sites)
 
 #define HIP_TRY(expr)                                                                  \
@@ -18,9 +18,14 @@ constexpr auto fail = pmdi_set_error;       // (the name at the call sites)
                         "%s: %s", #expr, hipGetErrorString(e__));                      \
     } while (0)
 
+// device memory an object owns: freed with its owner (which makes its device current before it is deleted)
 struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
     int ensure(size_t b)
     {
         if (b <= bytes && p) return 0;
@@ -31,7 +36,6 @@ struct DevBuf {
         bytes = b;
         return 0;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
 };
 
 // device memory of one call, freed on return
@@ -40,35 +44,25 @@ struct Scratch {
     ~Scratch() { if (p) (void)hipFree(p); }
 };
 
+// the launches of a sweep, each with an argument block of its own on the device
+enum { ARGS_MAIN = 0, ARGS_LIGHT, ARGS_HEAVIEST, ARGS_SETTLED, ARGS_GIVEN_BACK, ARGS_COUNT };
+
 struct pmdi_handle {
     pmdi_config cfg{};
     pmdi_tuning tun{};           // the creator's knobs (a copy: cfg.tuning is not kept), -1 = automatic
-    int T = 0;
     long long cap = 0;
     int Dmax = 0, sumD = 0, npairs = 1;
-    int terms_cap = 0, pid_lds = 0, pp_lds = 0, col_lds = 0, two_per_cu = 0;
-    // light group (block_threads == 0 only): chains whose last sweep met few live clusters per step are
-    // swept by 256-thread workgroups on a second stream, concurrently with the wide workgroups of the rest
-    bool split = false;
-    int l_terms_cap = 0, l_pid_lds = 0, l_pp_lds = 0, l_col_lds = 0;
-    int r_terms_cap = 0, r_pid_lds = 0, r_pp_lds = 0, r_col_lds = 0;     // the general kernel's LDS layout at the settled-chain kernel's workgroup width (hand-over in place)
-    long long light_ids = 0;
-    hipStream_t stream2 = nullptr, stream3 = nullptr;
+    SweepPlan plan;              // how every sweep is launched (pmdi_plan.h), decided once by pmdi_create
+    hipStream_t stream = nullptr, stream2 = nullptr, stream3 = nullptr;      // the handle's own; the light launch; the heaviest chains
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join3 = nullptr;
     unsigned *start_sig = nullptr;   // signal memory: workgroups of the heaviest-chains launch that have started (hipStreamWaitValue32)
-    int very_heavy = 0;          // the first `very_heavy` heavy chains of the launch order get a CU each (256-register build)
-    bool phase_on = false;
-    hipStream_t stream = nullptr;
     DsetDev ds[PMDI_KMAX_I]{};
     std::vector<void *> owned;          // device allocations freed in destroy
     // per-call staging (device)
     DevBuf d_s_in, d_order, d_Pi, d_logphi, d_flags, d_s_out, d_lw, d_pstar, d_stats, d_err, d_trace;
     DevBuf d_swept_by, d_resume;
-    bool s2_continue = true;     // a chain the settled-chain kernel gives back is carried on by the general kernel at that observation
-                                 // (false: swept again from the start -- the round-3 behaviour, kept for A/B runs)
-    DevBuf d_usc, d_partstar, d_kstate, d_phase, d_args, d_args2, d_args3, d_args4, d_args5, d_requeue, d_requeue_total, d_handed, d_group, d_cost, d_lorder, d_ticket, d_work, d_anclog, d_evpos, d_xcnt, d_xinc, d_xlab, d_xhdr;
-    int ksplit = 0;
-    int ksplit_batch = 0;        // split mode: chain slots per launch when n_chains * K workgroups are not resident at once (0 = one launch)
+    DevBuf d_args[ARGS_COUNT];
+    DevBuf d_usc, d_partstar, d_kstate, d_phase, d_requeue, d_requeue_total, d_handed, d_group, d_cost, d_lorder, d_ticket, d_work, d_anclog, d_evpos, d_xcnt, d_xinc, d_xlab, d_xhdr;
     bool have_order = false;
     // argument blocks travel through a ring of pinned host slots: the stream-ordered copy is then asynchronous for the host too
     static constexpr int RING = 64;
@@ -76,11 +70,7 @@ struct pmdi_handle {
     hipEvent_t ring_ev[RING] = {};
     bool ring_used[RING] = {};
     int ring_head = 0;
-    // settled-chain kernel (pmdi_sweep2.hip): takes the light group of a sweep when the configuration is one it is built for
-    bool s2_ok = false;
-    S2Layout s2{};
     int sweep_no = 0;
-    int sticky = 3;              // sweeps a chain stays with the general kernel after the settled-chain kernel gave it back (PMDI_STICKY)
     int err_keep = 0;            // set by the device-resident driver around its sweeps (pmdi_gibbs_step)
     int children = 0;            // live pmdi_gibbs / cluster-batch objects: pmdi_destroy refuses while > 0
     // feature selection

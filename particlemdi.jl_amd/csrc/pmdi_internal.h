@@ -208,17 +208,12 @@ hipError_t pmdi_launch_hypers(const GibbsArgs &a, int do_shuffle, hipStream_t st
 hipError_t pmdi_launch_align(const GibbsArgs &a, hipStream_t stream);
 hipError_t pmdi_launch_pack_samples(const int *s, unsigned char *out, long long count, hipStream_t stream);
 
-size_t pmdi_sweep_lds_bytes(const SweepArgs &a, int T);
+// (pmdi_sweep_lds_bytes: pmdi_sweep_carve.h)
 // `staging`: a pinned host slot the argument block is copied through (truly asynchronous), or null (pageable copy: host-synchronous)
 hipError_t pmdi_launch_sweep(const SweepArgs &a, SweepArgs *d_args, int n_chains, int T, hipStream_t stream, SweepArgs *staging = nullptr);
 // workgroups of the sweep kernel build (T threads, the argument block's LDS layout) that one CU holds at once
 hipError_t pmdi_sweep_blocks_per_cu(const SweepArgs &a, int T, int *blocks);
-// the settled-chain kernel (pmdi_sweep2.hip)
-void pmdi_sweep2_layout(int K, int N, int P, int Dmax, int cols_l, int idcap, int cls, int cdfl, S2Layout *L);
-bool pmdi_sweep2_supports(int K, int N, int P, int Dmax, long long cap);
-int pmdi_sweep2_threads(int K, int P);
-bool pmdi_sweep2_cdf_arena(int K, int P);     // that shape's build takes S2Layout::cdfl < cls
-int pmdi_sweep2_max_classes(int K, int P);  // particle classes per dataset the class slots of that shape can name (16 or 32)      // threads of the workgroup that sweeps a chain of P particles (0: no build for it)
+// the settled-chain kernel (pmdi_sweep2.hip; its shapes and LDS layout: pmdi_sweep2_layout.h)
 hipError_t pmdi_sweep2_blocks_per_cu(const SweepArgs &a, int *blocks);
 hipError_t pmdi_launch_sweep2(const SweepArgs &a, SweepArgs *d_args, int n_chains, hipStream_t stream, SweepArgs *staging = nullptr);
 hipError_t pmdi_launch_cluster_add(const ClusterBatchArgs &a, hipStream_t stream);

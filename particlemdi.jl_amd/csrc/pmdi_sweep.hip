@@ -64,14 +64,6 @@ hipError_t pmdi_launch_chain_order(const long long *cost, int *order, const long
 }
 
 // ---------------------------------------------------------------------------
-size_t pmdi_sweep_lds_bytes(const SweepArgs &a, int T)
-{
-    (void)T;
-    Carve c;
-    carve_lds(a, c);
-    return c.total;
-}
-
 static const void *sweep_kernel_for(const SweepArgs &a, int T)
 {
     const bool two = a.two_per_cu != 0;

@@ -16,6 +16,7 @@ __device__ __noinline__ void pmdi_resume_general(const SweepArgs *ap)
 #define PM2_RESUME_GENERAL(K_, NW_, ap_) pmdi_resume_general<K_, NW_>(ap_)
 #endif
 #include "pmdi_sweep2_body.h"
+#include "pmdi_sweep_carve.h"      // pmdi_sweep_lds_bytes (the build without the general kernel's code has not seen it yet)
 
 namespace {
 
@@ -48,22 +49,22 @@ __global__ void __launch_bounds__(64 * NW, 2) pmdi_sweep2_kernel(const SweepArgs
     s.run(ap, chain);
 }
 
-// the instantiations: P = 256 / 512 / 1024 particles on four waves (1, 2, 4 particles per lane), P = 2048 on eight waves (4 per lane)
+// the instantiations: one per shape of pmdi_s2::shape_for (pmdi_sweep2_layout.h)
 // (gauss_only: every dataset of the handle is Gaussian -- the build without the integer cluster types' code; 4-wave shapes only)
 template <int K>
 const void *kernel_for_k(int P, int *nw, bool gauss_only)
 {
-    *nw = 4;
-    if (gauss_only) {
-        if (P == 256) return (const void *)pmdi_sweep2_kernel<K, 1, 4, true>;
-        if (P == 512) return (const void *)pmdi_sweep2_kernel<K, 2, 4, true>;
-        if (P == 1024) return (const void *)pmdi_sweep2_kernel<K, 4, 4, true>;
+    const pmdi_s2::Shape s = pmdi_s2::shape_for(P);
+    *nw = s.nw;
+    if (s.nw == 4 && gauss_only) {
+        if (s.ppl == 1) return (const void *)pmdi_sweep2_kernel<K, 1, 4, true>;
+        if (s.ppl == 2) return (const void *)pmdi_sweep2_kernel<K, 2, 4, true>;
+        if (s.ppl == 4) return (const void *)pmdi_sweep2_kernel<K, 4, 4, true>;
     }
-    if (P == 256) return (const void *)pmdi_sweep2_kernel<K, 1, 4, false>;
-    if (P == 512) return (const void *)pmdi_sweep2_kernel<K, 2, 4, false>;
-    if (P == 1024) return (const void *)pmdi_sweep2_kernel<K, 4, 4, false>;
-    *nw = 8;
-    if (P == 2048) return (const void *)pmdi_sweep2_kernel<K, 4, 8, false>;
+    if (s.nw == 4 && s.ppl == 1) return (const void *)pmdi_sweep2_kernel<K, 1, 4, false>;
+    if (s.nw == 4 && s.ppl == 2) return (const void *)pmdi_sweep2_kernel<K, 2, 4, false>;
+    if (s.nw == 4 && s.ppl == 4) return (const void *)pmdi_sweep2_kernel<K, 4, 4, false>;
+    if (s.nw == 8 && s.ppl == 4) return (const void *)pmdi_sweep2_kernel<K, 4, 8, false>;
     return nullptr;
 }
 
@@ -85,40 +86,6 @@ bool all_gaussian(const SweepArgs &a)
 }
 
 }  // namespace
-
-void pmdi_sweep2_layout(int K, int N, int P, int Dmax, int cols_l, int idcap, int cls, int cdfl, S2Layout *L)
-{
-    pmdi_s2::make_layout(K, N, P, Dmax, cols_l, idcap, cls, cdfl, *L);
-}
-
-// particle classes per dataset the class slots of that shape's lanes can name (the LDS tables may hold fewer: S2Layout::cls)
-int pmdi_sweep2_max_classes(int K, int P)
-{
-    int nw = 0;
-    if (!kernel_for(K, P, &nw)) return 0;
-    return pmdi_s2::class_slots_max(K, P / (64 * nw), nw);
-}
-
-// whether that shape's build lets the mutation-CDF rows of the class slots beyond S2Layout::cdfl continue in the chain's arena
-bool pmdi_sweep2_cdf_arena(int K, int P)
-{
-    int nw = 0;
-    return kernel_for(K, P, &nw) && pmdi_s2::cdf_rows_in_arena(nw);
-}
-
-int pmdi_sweep2_threads(int K, int P)
-{
-    int nw = 0;
-    return kernel_for(K, P, &nw) ? 64 * nw : 0;
-}
-
-// shapes the kernel is built for (the rest stays with pmdi_sweep.hip)
-bool pmdi_sweep2_supports(int K, int N, int P, int Dmax, long long cap)
-{
-    (void)cap;      // (cluster ids travel as 16-bit values in the LDS tables: a chain whose ids would outgrow them is given back, pmdi_sweep2_body.h)
-    int nw;
-    return K >= 1 && K <= pmdi_s2::KMAX2 && N >= 2 && N <= 64 && Dmax <= 64 && kernel_for(K, P, &nw) != nullptr;
-}
 
 // dynamic LDS of a launch: this kernel's layout, or the general kernel's for the same workgroup width when a handed-over chain is
 // carried on in place and that layout is the larger one

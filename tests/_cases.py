@@ -8,7 +8,8 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def golden_cases():
-    return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "*.npz")))
+    """The sweep vectors of tests/golden/make_golden.py (sweep_plans.npz beside them is another kind of record: _plan_cases.py)."""
+    return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "*.npz")) if os.path.basename(p) != "sweep_plans.npz")
 
 
 def load_golden(name):

@@ -2,6 +2,7 @@
 (particlemdi.jl_amd/csrc/pmdi_sweep2_body.h) compiled for the HOST and run in a lock-step workgroup emulator (tests/emu/wavesim.h).
 Checks kernel logic against the oracle without a GPU; the product library never sees any of this."""
 import ctypes as C
+import glob
 import os
 import subprocess
 
@@ -19,7 +20,7 @@ VARIANTS = {"": [], "xcap2": ["-DPM2_XCAP=2"]}      # (xcap2: two LDS entries fo
 def build(force=False, variant=""):
     _LIB = os.path.join(_EMU, f"libpmdi_emu{'_' + variant if variant else ''}.so")
     deps = [os.path.join(_EMU, "emu_sweep2.cpp"), os.path.join(_EMU, "wavesim.h"), os.path.join(_EMU, "lane_api_emu.h")] + \
-           [os.path.join(_CSRC, f) for f in ("pmdi_sweep2_body.h", "pmdi_arith.h", "pmdi_internal.h")]
+           glob.glob(os.path.join(_CSRC, "*.h"))
     if not force and os.path.exists(_LIB) and os.path.getmtime(_LIB) >= max(os.path.getmtime(d) for d in deps):
         return _LIB
     subprocess.check_call(["g++", "-std=c++17", "-O2", "-g", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unknown-pragmas",

@@ -100,18 +100,17 @@ enum { EMU_E_GUARD = -100 };
 void *emu_create(int K, long long n, int N, int P, const int *D, const double *const *data, unsigned long long seed, int q1,
                  int cols_l, int idcap, const int *kinds, int cls, int cdfl, long long cap)
 {
-    if (K < 1 || K > pmdi_s2::KMAX2 || (P != 256 && P != 512 && P != 1024 && P != 2048) || N > 64) return nullptr;
+    if (pmdi_s2::shape_for(K, P).nw == 0 || N > 64) return nullptr;
     if (cap == 0) cap = (long long)N * P + 1;
     if (cap < N + 2 || cap > (long long)N * P + 1) return nullptr;
     Emu *e = new Emu();
     e->K = K; e->N = N; e->P = P; e->n = n; e->cap = cap; e->seed = seed; e->q1 = q1;
     {
-        const int nw = P > 1024 ? 8 : 4;
-        const int mx = pmdi_s2::class_slots_max(K, P / (64 * nw), nw);
+        const int mx = pmdi_sweep2_max_classes(K, P);
         if (cls > mx) cls = mx;
     }
     e->cols_l = cols_l; e->idcap = idcap; e->cls = cls;
-    e->cdfl = (cdfl > 0 && cdfl < cls && pmdi_s2::cdf_rows_in_arena(P > 1024 ? 8 : 4)) ? cdfl : cls;     // (only the 8-wave builds carry that path)
+    e->cdfl = (cdfl > 0 && cdfl < cls && pmdi_sweep2_cdf_arena(K, P)) ? cdfl : cls;     // (only the 8-wave builds carry that path)
     memset(e->ds, 0, sizeof(e->ds));
     e->x.resize(K); e->gtab.resize(K); e->arena.resize(K); e->lhtab.resize(K); e->lgtab.resize(K); e->xi.resize(K); e->maxcol.resize(K);
     int flag_off = 0;
@@ -212,11 +211,11 @@ int emu_sweep(void *h, long long iter, const int *s_in, const int *order, long l
     std::vector<long long> wk(PMDI_KMAX_I * 8, 0);
     a.err = &err; a.cost = &cost; a.kstate = kstate.data(); a.work = wk.data();
     pmdi_s2::make_layout(e->K, e->N, e->P, e->Dmax, e->cols_l, e->idcap, e->cls, e->cdfl, a.s2);
-    const int nw = e->P > 1024 ? 8 : 4;
+    const pmdi_s2::Shape shape = pmdi_s2::shape_for(e->K, e->P);
     bool go = true;
     for (int k = 0; k < e->K; ++k) go = go && e->ds[k].kind == K_GAUSSIAN;
-    RunArg r{&a, e->K, e->P / (64 * nw), nw, go};
-    wavesim::run_block(64 * nw, 0, (size_t)a.s2.total, entry, &r);
+    RunArg r{&a, e->K, shape.ppl, shape.nw, go};
+    wavesim::run_block(64 * shape.nw, 0, (size_t)a.s2.total, entry, &r);
     for (int k = 0; k < e->K; ++k) {
         const long long at = guard_broken(e, k);
         if (at) {
