@@ -3,6 +3,7 @@
 // boundary, owns device memory, builds the exact-arithmetic lookup tables and
 // launches the kernels of pmdi_kernels.hip.  No CPU fallback exists: every
 // compute entry point runs on the gfx950 device or fails.
+#include "pmdi_arith.h"           // uniform01: the initial feature flags
 #include "pmdi_host.h"
 #include "pmdi_psm_blocksum_plan.h"
 #include "pmdi_sweep_carve.h"
@@ -26,22 +27,6 @@ namespace {
 thread_local char g_err[512] = "";
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// the device generator (pmdi_device.h uniform01) on the host: Philox4x32-10, ctr = (p, pos, site<<16|k, iter)
-double host_uniform01(unsigned long long seed, unsigned iter, unsigned pos, unsigned k, unsigned p, unsigned site)
-{
-    unsigned c0 = p, c1 = pos, c2 = (site << 16) | k, c3 = iter;
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long m0 = (unsigned long long)0xD2511F53u * c0, m1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned hi0 = (unsigned)(m0 >> 32), lo0 = (unsigned)m0, hi1 = (unsigned)(m1 >> 32), lo1 = (unsigned)m1;
-        const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    const unsigned long long m = ((unsigned long long)(c0 >> 6) << 26) | (unsigned long long)(c1 >> 6);
-    return (double)(2 * m + 1) * (1.0 / 9007199254740992.0);
-}
 
 // the divisor of the `which` matrix of counts (pmdi_psm_*_device): S, or S K for the Overall one
 unsigned __int128 psm_divisor(int64_t S, int32_t K, int32_t which) { return (unsigned __int128)S * (unsigned)(which == K ? K : 1); }
@@ -1275,7 +1260,7 @@ int pmdi_gibbs_create(pmdi_handle *h, double rho, int32_t feature_select, pmdi_g
                 for (int k = 0; k < K; ++k)
                     for (int q = 0; q < h->ds[k].D; ++q)
                         fl[(size_t)c * h->sumD + h->ds[k].flag_off + q] =
-                            host_uniform01(h->cfg.seed + (unsigned long long)c, 0, 0, (unsigned)k, (unsigned)q, SITE_INIT_FLAGS) < 0.5 ? 1 : 0;
+                            pmdi_arith::uniform01(h->cfg.seed + (unsigned long long)c, 0, 0, (unsigned)k, (unsigned)q, SITE_INIT_FLAGS) < 0.5 ? 1 : 0;
         if (hipMemcpy(g->flags, fl.data(), fl.size(), hipMemcpyHostToDevice) != hipSuccess) { pmdi_gibbs_destroy(g); return fail(PMDI_E_DEVICE, "memcpy failed"); }
     }
     if (hipMemset(g->err, 0, (size_t)C * 4) != hipSuccess || hipMemset(g->stats, 0, (size_t)C * 64) != hipSuccess ||

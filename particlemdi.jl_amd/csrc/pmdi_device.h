@@ -1,31 +1,18 @@
 // pmdi_device.h -- device helpers shared by the sweep kernel (pmdi_sweep.hip) and the
-// unit / feature-selection kernels (pmdi_kernels.hip).  Compile with -ffp-contract=off.
-// Reference lines are cited as file:line relative to /root/reference.
+// unit / feature-selection kernels (pmdi_kernels.hip): typed arena pointers, block-level
+// primitives, the statistics update.  The result-defining arithmetic is stated in pmdi_arith.h
+// and the DPP wave reductions in pmdi_wave.h; this file only adapts them (double2 pairs, names).
+// Compile with -ffp-contract=off.  Reference lines are cited as file:line relative to /root/reference.
 #pragma once
+#define PMDI_ARITH_MULHI true      // uniform01 with __umulhi: the form these kernels' spill budgets were measured with (pmdi_arith.h)
+#include "pmdi_arith.h"
 #include "pmdi_internal.h"
+#include "pmdi_wave.h"
 
 namespace pmdi_dev {
 
 // ---------------------------------------------------------------------------
-// Counter-based RNG (specification shared with oracle/pmdi_oracle.c):
-// Philox4x32-10, key = (seed lo, seed hi), ctr = (p, pos, site<<16|k, iter).
-__device__ __forceinline__ double uniform01(unsigned long long seed, unsigned iter, unsigned pos,
-                                            unsigned k, unsigned p, unsigned site)
-{
-    unsigned c0 = p, c1 = pos, c2 = (site << 16) | k, c3 = iter;
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    // 52 random bits -> odd multiple of 2^-53: uniform on the open interval (0,1), never 0
-    unsigned long long m = ((unsigned long long)(c0 >> 6) << 26) | (unsigned long long)(c1 >> 6);
-    return (double)(2 * m + 1) * (1.0 / 9007199254740992.0);
-}
+using pmdi_arith::uniform01;      // the counter-based RNG, in its __umulhi form here (PMDI_ARITH_MULHI above)
 
 // ---------------------------------------------------------------------------
 // Arena pointers carry the global address space: the compiler then emits global_load/global_store
@@ -217,40 +204,8 @@ __device__ __forceinline__ unsigned long long block_flag_scan(bool f0, bool f1, 
     return base + mine;
 }
 
-// Wave-level all-reduce of a double on the DPP network (no LDS round trips): xor-1 and xor-2 inside
-// quads, half-row and row mirrors give every lane its 16-lane row total; the four row totals are
-// read with v_readlane and combined as (r0 op r1) op (r2 op r3).  All 64 lanes must be active.
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false);
-    hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double readlane_f64(double v, int l)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-    v += dpp_f64<0xB1>(v);      // quad_perm [1,0,3,2]
-    v += dpp_f64<0x4E>(v);      // quad_perm [2,3,0,1]
-    v += dpp_f64<0x141>(v);     // row_half_mirror
-    v += dpp_f64<0x140>(v);     // row_mirror
-    return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
-}
-__device__ __forceinline__ double wave_max_f64(double v)
-{
-    double t;
-    t = dpp_f64<0xB1>(v); v = (t > v) ? t : v;
-    t = dpp_f64<0x4E>(v); v = (t > v) ? t : v;
-    t = dpp_f64<0x141>(v); v = (t > v) ? t : v;
-    t = dpp_f64<0x140>(v); v = (t > v) ? t : v;
-    const double r0 = readlane_f64(v, 0), r1 = readlane_f64(v, 16), r2 = readlane_f64(v, 32), r3 = readlane_f64(v, 48);
-    const double m01 = (r1 > r0) ? r1 : r0, m23 = (r3 > r2) ? r3 : r2;
-    return (m23 > m01) ? m23 : m01;
-}
+using pmdi_wave::wave_sum_f64;      // the wave-level reductions on the DPP network: pmdi_wave.h
+using pmdi_wave::wave_max_f64;
 
 // Block-wide max / pair of sums.  scr: 48 doubles; the max uses [32,48), the sums [0,32), so the two
 // can follow each other with one barrier each (the caller's next use of scr is barriers away).
@@ -398,45 +353,11 @@ __device__ void jl_cumsum_inplace(double *c, int n)
 // ---------------------------------------------------------------------------
 // Per-type arithmetic, restating the reference expression by expression.
 
-// cluster_add!(::GaussianCluster): gaussian_cluster.jl:54-66 (one feature)
-__device__ __forceinline__ void gauss_add(double x, int nnew, double2 &ml, double2 &sb)
-{
-    const double n = (double)nnew;
-    sb.x = sb.x + x;
-    const double d = x - ml.x;
-    sb.y = sb.y + ((double)(nnew - 1) + 0.001) * (d * d) / (2.0 * (n + 0.001));
-    ml.x = sb.x / (n + 0.001);
-    ml.y = ((0.5 * n + 0.5) * (n + 0.001)) / (sb.y * (n + 1.001));
-}
-
-// The sweep's pool stores only (Sigma, beta) per feature: mu and lambda are pure functions of
-// (Sigma, beta, n) -- gaussian_cluster.jl:60-63 recomputes them from exactly these values at
-// every add -- so they are derived on demand, bit-identically, and an update touches 16 bytes
-// instead of 64.  (Valid while the feature flags are fixed for the lifetime of the pool, which
-// holds inside a sweep: a feature is either updated at every add or never read.)
-__device__ __forceinline__ void gauss_add_sb(double x, int nnew, double2 &sb)
-{
-    const double n = (double)nnew;
-    const double mu_prev = (nnew == 1) ? 0.0 : sb.x / ((double)(nnew - 1) + 0.001);
-    sb.x = sb.x + x;
-    const double d = x - mu_prev;
-    sb.y = sb.y + ((double)(nnew - 1) + 0.001) * (d * d) / (2.0 * (n + 0.001));
-}
-
-__device__ __forceinline__ double2 gauss_ml(int cn, double2 sb)
-{
-    if (cn == 0) return make_double2(0.0, 1.0);          // GaussianCluster(dataFile): mu = 0, lambda = 1
-    const double n = (double)cn;
-    return make_double2(sb.x / (n + 0.001), ((0.5 * n + 0.5) * (n + 0.001)) / (sb.y * (n + 1.001)));
-}
-
-// the two per-feature terms of calc_logprob(::GaussianCluster): gaussian_cluster.jl:45-48
-__device__ __forceinline__ void gauss_terms(double x, double n, double2 ml, double &ta, double &tb)
-{
-    ta = 0.5 * log(ml.y / (n + 1.0));
-    const double d = x - ml.x;
-    tb = (0.5 * n + 1.0) * log(1.0 + (1.0 / (n + 1.0)) * (d * d) * ml.y);
-}
+// The Gaussian recurrences and terms are pmdi_arith.h's; here on the (mu, lambda) and (Sigma, beta) pairs as the arena stores them.
+__device__ __forceinline__ void gauss_add(double x, int nnew, double2 &ml, double2 &sb) { pmdi_arith::gauss_add(x, nnew, ml.x, ml.y, sb.x, sb.y); }
+__device__ __forceinline__ void gauss_add_sb(double x, int nnew, double2 &sb) { pmdi_arith::gauss_add_sb(x, nnew, sb.x, sb.y); }
+__device__ __forceinline__ double2 gauss_ml(int cn, double2 sb) { double2 ml; pmdi_arith::gauss_ml(cn, sb.x, sb.y, ml.x, ml.y); return ml; }
+__device__ __forceinline__ void gauss_terms(double x, double n, double2 ml, double &ta, double &tb) { pmdi_arith::gauss_terms(x, n, ml.x, ml.y, ta, tb); }
 
 // deepcopy (src/pmdi.jl:297) + cluster_add! (:300) of one feature of one chosen cluster:
 // statistics of pool id `src` plus the observation go to pool id `dst` (dst == src: in place).
@@ -459,11 +380,6 @@ __device__ __forceinline__ void stats_update_one(const DsetDev &d, const KS &s, 
     }
 }
 
-// calc_logprob(::NegBinomCluster) per-feature term: negbinom_cluster.jl:33-37;
-// loggamma of integers comes from the host-built table LG[m] = lgamma(m)
-__device__ __forceinline__ double negbin_term(gcdbl lg, long long n, long long x, long long S)
-{
-    return lg[1 + n + 1] + lg[1 + x + S] + lg[1 + n + 1 + S] - lg[1 + n + 1 + 1 + x + S] -
-           lg[1 + n] - lg[1 + S];
-}
+// calc_logprob(::NegBinomCluster) per-feature term: pmdi_arith.h (the table as a typed global pointer)
+using pmdi_arith::negbin_term;
 }  // namespace pmdi_dev

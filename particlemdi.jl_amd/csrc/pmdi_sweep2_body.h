@@ -22,6 +22,10 @@
 // OVER: the bookkeeping phase checks before it commits, hand_over() writes the chain's state where the general kernel keeps it, and
 // the same workgroup carries on with the general kernel's code from that observation (PM2_RESUME_GENERAL, defined by pmdi_sweep2.hip).
 //
+// The arithmetic that defines results -- uniforms, Gaussian recurrences and terms, the NegBinom term, the u += 1/P replay, the
+// resampling decision -- is pmdi_arith.h's, shared with the general kernel; the DPP wave reductions of the gfx950 lane API are
+// pmdi_wave.h's.  What is written out here is data placement and control flow only.
+//
 // Everything here is written against a small lane API (PM2_* macros).  This header defines it for gfx950; a translation unit that
 // defines PM2_LANE_API_PROVIDED first brings its own -- tests/emu/ does, to run the same source on the CPU in a lock-step workgroup
 // emulator (test infrastructure; the product build is hipcc for gfx950 only and never sees it).
@@ -34,6 +38,7 @@
 // The lane API of this file for gfx950.  (A translation unit that defines PM2_LANE_API_PROVIDED before including this header brings
 // its own: that is how the test suite runs this source on a CPU, see tests/emu/.  The product build never does.)
 #ifndef PM2_LANE_API_PROVIDED
+#include "pmdi_wave.h"
 #define PM2_DEV __device__ __forceinline__
 #define PM2_COLD __device__ __noinline__          // out of line: a cold path must not cost the sweep loop registers
 extern __shared__ __attribute__((aligned(16))) unsigned char pm2_smem_[];
@@ -105,65 +110,12 @@ PM2_DEV u64 readlane_u64(u64 v, int src)
     const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, s_), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), s_);
     return ((u64)hi << 32) | (u64)lo;
 }
-// wave-level reductions of a double on the DPP network: xor-1 and xor-2 inside quads, half-row and row mirrors give every lane its
-// 16-lane row total; the four row totals are read with v_readlane.  All 64 lanes must be active.
-template <int CTRL> PM2_DEV double dpp_d(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false);
-    hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-PM2_DEV double readlane_d(double v, int l)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-PM2_DEV double wave_sum_d(double v)
-{
-    v += dpp_d<0xB1>(v);      // quad_perm [1,0,3,2]
-    v += dpp_d<0x4E>(v);      // quad_perm [2,3,0,1]
-    v += dpp_d<0x141>(v);     // row_half_mirror
-    v += dpp_d<0x140>(v);     // row_mirror
-    return (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + readlane_d(v, 48));
-}
-PM2_DEV double wave_max_d(double v)
-{
-    double t;
-    t = dpp_d<0xB1>(v); v = (t > v) ? t : v;
-    t = dpp_d<0x4E>(v); v = (t > v) ? t : v;
-    t = dpp_d<0x141>(v); v = (t > v) ? t : v;
-    t = dpp_d<0x140>(v); v = (t > v) ? t : v;
-    const double r0 = readlane_d(v, 0), r1 = readlane_d(v, 16), r2 = readlane_d(v, 32), r3 = readlane_d(v, 48);
-    const double m01 = (r1 > r0) ? r1 : r0, m23 = (r3 > r2) ? r3 : r2;
-    return (m23 > m01) ? m23 : m01;
-}
-// the value of the lane below (lane 0 keeps its own): one DPP shift across the whole wave, no LDS round trip
-PM2_DEV double prev_lane_d(double v) { return dpp_d<0x138>(v); }      // wave_shr:1
-PM2_DEV double wave_min_d(double v)
-{
-    double t;
-    t = dpp_d<0xB1>(v); v = (t < v) ? t : v;
-    t = dpp_d<0x4E>(v); v = (t < v) ? t : v;
-    t = dpp_d<0x141>(v); v = (t < v) ? t : v;
-    t = dpp_d<0x140>(v); v = (t < v) ? t : v;
-    const double r0 = readlane_d(v, 0), r1 = readlane_d(v, 16), r2 = readlane_d(v, 32), r3 = readlane_d(v, 48);
-    const double m01 = (r1 < r0) ? r1 : r0, m23 = (r3 < r2) ? r3 : r2;
-    return (m23 < m01) ? m23 : m01;
-}
-// exclusive prefix sum of an int over the wave, and the total (the DPP network: shifts inside the rows of sixteen lanes, then the
-// row totals broadcast into the rows above; all lanes active)
-PM2_DEV int wave_excl_scan_i(int v, int &total)
-{
-    int inc = v;
-    inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xF, 0xF, false);      // row_shr:1
-    inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xF, 0xF, false);      // row_shr:2
-    inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xF, 0xF, false);      // row_shr:4
-    inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xF, 0xF, false);      // row_shr:8
-    inc += __builtin_amdgcn_update_dpp(0, inc, 0x142, 0xA, 0xF, false);      // row_bcast:15 into rows 1 and 3
-    inc += __builtin_amdgcn_update_dpp(0, inc, 0x143, 0xC, 0xF, false);      // row_bcast:31 into rows 2 and 3
-    total = __builtin_amdgcn_readlane(inc, 63);
-    return inc - v;
-}
+// the reductions on the DPP network: pmdi_wave.h, under the names of this lane API
+PM2_DEV double wave_sum_d(double v) { return pmdi_wave::wave_sum_f64(v); }
+PM2_DEV double wave_max_d(double v) { return pmdi_wave::wave_max_f64(v); }
+PM2_DEV double wave_min_d(double v) { return pmdi_wave::wave_min_f64(v); }
+PM2_DEV double prev_lane_d(double v) { return pmdi_wave::prev_lane_f64(v); }
+using pmdi_wave::wave_excl_scan_i;
 }  // namespace pmdi_s2
 #endif  // PM2_LANE_API_PROVIDED
 
@@ -468,17 +420,16 @@ struct Sweep2 {
             double mu, lam;
             pmdi_arith::gauss_ml(cn, st.a, st.b, mu, lam);
             const double nd_ = (double)cn, dd = x - mu;
-            ta = 0.5 * log(lam / (nd_ + 1.0));
-            tb = (0.5 * nd_ + 1.0) * log(1.0 + (1.0 / (nd_ + 1.0)) * (dd * dd) * lam);
+            ta = pmdi_arith::gauss_term_a(nd_, lam);
+            tb = pmdi_arith::gauss_term_b(dd, nd_, lam);
         } else if ((!GO && v.kind == K_CATEGORICAL)) {
             auto lh = PM2_G(const double, d.lhtab);
             ta = lh[PM2_G(const int, d.maxcol)[lane] + 2 * cn];
             tb = (cn == 0) ? lh[1] : lh[2 * (int)st.a + 1];
         } else {
             auto lg = PM2_G(const double, d.lgtab);
-            const long long n_ = cn, x_ = (long long)x, S_ = (long long)st.a;
             ta = 0.0;
-            tb = lg[1 + n_ + 1] + lg[1 + x_ + S_] + lg[1 + n_ + 1 + S_] - lg[1 + n_ + 1 + 1 + x_ + S_] - lg[1 + n_] - lg[1 + S_];
+            tb = pmdi_arith::negbin_term(lg, cn, (long long)x, (long long)st.a);
         }
     }
     // calc_logprob's sum over the features that are switched on, in feature order (one lane): the same terms in the same order as
@@ -528,7 +479,7 @@ struct Sweep2 {
 #pragma unroll
         for (int s = 0; s < NS; ++s)
             if (s == s0) { c_mu.set(s, mu); c_lam.set(s, lam); }
-        if (lane < v.D) v.ta_row(s0)[lane] = 0.5 * log(lam / ((double)cnv + 1.0));            // gaussian_cluster.jl:45
+        if (lane < v.D) v.ta_row(s0)[lane] = pmdi_arith::gauss_term_a((double)cnv, lam);
         if (lane == 0) {
             lds<int>(v.base + L.slot_cn)[s0] = cnv;
             const double g = have_g ? g_in : PM2_G(const double, ap->ds[k].gtab)[cnv];            // gaussian_cluster.jl:38-40
@@ -1485,8 +1436,8 @@ struct Sweep2 {
         double w[PPL];
 #pragma unroll
         for (int u = 0; u < PPL; ++u) w[u] = exp(lw[u] - mx);        // pprob before the cumsum (src/misc.jl:29), as calc_ESS formed it
-        const double u01 = pmdi_arith::uniform01(seed, iter, (unsigned)pos, 0, 0, SITE_RESAMPLE_U);
-        const double usl = pmdi_arith::uniform01(seed, iter, (unsigned)pos, 0, 0, SITE_RESAMPLE_SLOT);
+        const double u01 = pmdi_arith::uniform01<false>(seed, iter, (unsigned)pos, 0, 0, SITE_RESAMPLE_U);
+        const double usl = pmdi_arith::uniform01<false>(seed, iter, (unsigned)pos, 0, 0, SITE_RESAMPLE_SLOT);
         double c[PPL];
         PHR(1);
         cumsum_pairwise(w, c);
@@ -1495,25 +1446,12 @@ struct Sweep2 {
         u16 *jtab = lds<u16>(L.tr + L.rs_jtab), *raw = lds<u16>(L.tr + L.rs_raw), *anc = lds<u16>(L.tr + L.rs_anc);
         double *red = lds<double>(L.red);
         if (tid == T - 1) red[0] = c[PPL - 1];
-        // u += 1/particles by repeated addition (:34), exactly: h = 1/P is a power of two, so inside a binade every u + h is exact
-        // and only the additions that cross into the next binade round.  The lane replays the crossings up to its first slot
-        // and adds h for the following ones as the reference does.
+        // u += 1/particles by repeated addition (:34), exactly: the lane jumps to its first slot (pmdi_arith::resample_u_at) and adds
+        // h for the following ones as the reference does
         {
             const double h = 1.0 / (double)P;
             const int j = tid * PPL;
-            double u = u01 / (double)P;
-            int done = 0;
-            while (done < j) {
-                int e;
-                (void)frexp(u, &e);                          // u in [2^(e-1), 2^e)
-                const double B = ldexp(1.0, e);
-                const double xx = (B - u) * (double)P;       // exact: B - u (same binade) and the power-of-two scale
-                double m = floor(xx);
-                if (m == xx) m -= 1.0;                       // largest m with u + m*h < B
-                if (m > (double)(j - done)) m = (double)(j - done);
-                if (m >= 1.0) { u = u + m * h; done += (int)m; }
-                if (done < j) { u = u + h; done += 1; }
-            }
+            double u = pmdi_arith::resample_u_at(u01, P, j);
 #pragma unroll
             for (int uu = 0; uu < PPL; ++uu) { utab[j + uu] = u; u = u + h; }
         }
@@ -1919,7 +1857,7 @@ struct Sweep2 {
                         if (nsv[u] < 0) {
                             const int p = tid * PPL + u;
                             const int rr = csl_get(k, u);
-                            const double u01 = pmdi_arith::uniform01(seed, iter, (unsigned)pos, (unsigned)k, (unsigned)p, SITE_DRAW);
+                            const double u01 = pmdi_arith::uniform01<false>(seed, iter, (unsigned)pos, (unsigned)k, (unsigned)p, SITE_DRAW);
                             // first label whose CDF exceeds u (:252-260) = the number of leading entries that do not exceed it
                             int ns = 0, t = 0;
                             if (!CDFA || rr < v.cdfl) {
@@ -2064,10 +2002,7 @@ struct Sweep2 {
                 for (int w_ = 0; w_ < NW; ++w_) { sa += red[RD_SA + w_]; sq += red[RD_SQ + w_]; }
                 ess = (sa * sa) / sq;
             }
-            // The tree-ordered sums agree with calc_ESS's sequential loop to ~1e-13 relative; the decision is a comparison, so when
-            // ESS lands that close to P/2 (k equal weights and the rest negligible give exactly k in the reference's order, and
-            // k = P/2 does happen) the sums are redone in the reference's order by one lane.
-            if (fabs(ess - 0.5 * (double)P) <= 1e-9 * (double)P) {
+            if (pmdi_arith::ess_needs_sequential_redo(ess, P)) {      // the sums again, in the reference's order, by one lane
                 double *wt = lds<double>(L.tr);
                 PM2_BARRIER();
 #pragma unroll
@@ -2082,7 +2017,7 @@ struct Sweep2 {
                 ess = red[120];
                 PM2_BARRIER();
             }
-            const bool res = ess <= 0.5 * (double)P;              // src/pmdi.jl:317
+            const bool res = pmdi_arith::ess_resamples(ess, P);
             if (res) {
                 PH2(8);
                 if (tid == 0) stat()[1] += 1;
@@ -2245,7 +2180,7 @@ struct Sweep2 {
         if (tid == 0) {   // StatsBase.sample(::Weights): sequential sum and scan, as the oracle
             double sum = 0.0;
             for (int p = 0; p < P; ++p) sum += wt[p];
-            const double t = pmdi_arith::uniform01(seed, iter, 0, 0, 0, SITE_PSTAR) * sum;
+            const double t = pmdi_arith::uniform01<false>(seed, iter, 0, 0, 0, SITE_PSTAR) * sum;
             int ip = 0;
             double cw = wt[0];
             while (cw < t && ip < P - 1) { ++ip; cw += wt[ip]; }

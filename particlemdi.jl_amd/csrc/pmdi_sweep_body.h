@@ -908,6 +908,32 @@ __device__ PMDI_COLD_SLOW void sweep_slow(const SweepArgs *__restrict__ ap, int 
 #undef PHS
 }
 
+// calc_ESS (src/misc.jl:15-25) of the log-weights in sh.lw and the resampling decision (src/pmdi.jl:317; the predicates are
+// pmdi_arith.h's): sets mx_ (the largest log-weight), ess_ and resample_.  For sweep_replay and the step loop.  A macro, like
+// PMDI_BUILD_LEAF_PROGRAM: as a function -- __forceinline__, whatever its signature -- the step loop's registers are allocated
+// differently and 9 of the 20 builds of pmdi_sweep.hip gain 1 to 6 VGPR spill slots; as text the device code is what it was.
+#define PMDI_SWEEP_ESS(mx_, ess_, resample_)                                                                                      \
+    do {                                                                                                                          \
+        mx_ = -INFINITY;                                                                                                          \
+        for (int p = tid; p < P; p += T) { const double v = sh.lw[p]; mx_ = (v > mx_) ? v : mx_; }                                \
+        mx_ = block_max<T>(mx_, gen(sh.red));                                                                                     \
+        double sa = 0.0, sb2 = 0.0;                                                                                               \
+        for (int p = tid; p < P; p += T) { const double w = exp(sh.lw[p] - mx_); sa += w; sb2 += w * w; }                         \
+        block_sum2<T>(sa, sb2, gen(sh.red));                                                                                      \
+        ess_ = (sa * sa) / sb2;                                                                                                   \
+        if (pmdi_arith::ess_needs_sequential_redo(ess_, P)) {      /* the sums again, in the reference's order, by one lane */    \
+            __syncthreads();                                                                                                      \
+            if (tid == 0) {                                                                                                       \
+                double na = 0.0, nb = 0.0;                                                                                        \
+                for (int p = 0; p < P; ++p) { const double w = exp(sh.lw[p] - mx_); na += w; nb += w * w; }                       \
+                sh.red[40] = (na * na) / nb;                                                                                      \
+            }                                                                                                                     \
+            __syncthreads();                                                                                                      \
+            ess_ = sh.red[40];                                                                                                    \
+        }                                                                                                                         \
+        resample_ = pmdi_arith::ess_resamples(ess_, P);                                                                           \
+    } while (0)
+
 // draw_partstar (src/misc.jl:27-47), gather and compact renumbering (src/pmdi.jl:318-340)
 template <int T>
 __device__ PMDI_COLD_RESAMPLE void sweep_resample(const SweepArgs *__restrict__ ap, long long pos, double mx)
@@ -951,27 +977,8 @@ __device__ PMDI_COLD_RESAMPLE void sweep_resample(const SweepArgs *__restrict__ 
             }
             const bool p_pow2 = (P & (P - 1)) == 0;
             if (p_pow2) {
-                // u += 1/particles by repeated addition (:34), in parallel and still bit-exact: h = 1/P is a
-                // power of two, so inside a binade [2^e, 2^(e+1)) every u + h is exact (h is a multiple of
-                // ulp(u)); only the additions that cross into the next binade round.  Each lane replays the
-                // crossings (about ten of them) and jumps over the exact runs in between.
-                const double h = 1.0 / (double)P;
-                for (int j = tid; j < P; j += T) {
-                    double u = u01 / (double)P;
-                    int done = 0;
-                    while (done < j) {
-                        int e;
-                        (void)frexp(u, &e);                          // u in [2^(e-1), 2^e)
-                        const double B = ldexp(1.0, e);
-                        const double x = (B - u) * (double)P;        // exact: B - u (same binade) and the power-of-two scale
-                        double m = floor(x);
-                        if (m == x) m -= 1.0;                        // largest m with u + m*h < B
-                        if (m > (double)(j - done)) m = (double)(j - done);
-                        if (m >= 1.0) { u = u + m * h; done += (int)m; }      // exact run inside the binade
-                        if (done < j) { u = u + h; done += 1; }               // the crossing step rounds like the loop's
-                    }
-                    usc[j] = u;
-                }
+                // u += 1/particles by repeated addition (:34), in parallel and still bit-exact
+                for (int j = tid; j < P; j += T) usc[j] = pmdi_arith::resample_u_at(u01, P, j);
             } else if (tid == T - 64) {                           // general P: the additions round, one lane replays them
                 double u = u01 / (double)P;
                 const double h = 1.0 / (double)P;
@@ -1347,24 +1354,9 @@ __device__ __noinline__ void sweep_replay(const SweepArgs *__restrict__ ap, long
         __syncthreads();
     }
     // calc_ESS (src/misc.jl:15-25) and the resampling decision (src/pmdi.jl:317) of this observation, as the step loop does them
-    double mx = -INFINITY;
-    for (int p = tid; p < P; p += T) { const double v = sh.lw[p]; mx = (v > mx) ? v : mx; }
-    mx = block_max<T>(mx, gen(sh.red));
-    double sa = 0.0, sb2 = 0.0;
-    for (int p = tid; p < P; p += T) { const double w = exp(sh.lw[p] - mx); sa += w; sb2 += w * w; }
-    block_sum2<T>(sa, sb2, gen(sh.red));
-    double ess = (sa * sa) / sb2;
-    if (fabs(ess - 0.5 * (double)P) <= 1e-9 * (double)P) {         // (the reference's order of additions when the comparison is that close)
-        __syncthreads();
-        if (tid == 0) {
-            double na = 0.0, nb = 0.0;
-            for (int p = 0; p < P; ++p) { const double w = exp(sh.lw[p] - mx); na += w; nb += w * w; }
-            sh.red[40] = (na * na) / nb;
-        }
-        __syncthreads();
-        ess = sh.red[40];
-    }
-    const bool resample = ess <= 0.5 * (double)P;
+    double mx, ess;
+    bool resample;
+    PMDI_SWEEP_ESS(mx, ess, resample);
     if (resample) {
         if (tid == 0) sh.stat[1] += 1;
         sweep_resample<T>(ap, pos, mx);
@@ -2163,29 +2155,7 @@ __device__ __forceinline__ void pmdi_sweep_body(const SweepArgs *__restrict__ ap
         double ess = (double)P;
         bool resample = false;
         double mx = 0.0;
-        if (!lw_uniform) {
-            mx = -INFINITY;
-            for (int p = tid; p < P; p += T) { const double v = sh.lw[p]; mx = (v > mx) ? v : mx; }
-            mx = block_max<T>(mx, gen(sh.red));
-            double sa = 0.0, sb2 = 0.0;
-            for (int p = tid; p < P; p += T) { const double w = exp(sh.lw[p] - mx); sa += w; sb2 += w * w; }
-            block_sum2<T>(sa, sb2, gen(sh.red));
-            ess = (sa * sa) / sb2;
-            // The tree-ordered sums agree with calc_ESS's sequential loop (src/misc.jl:19-23) to ~1e-13 relative; the decision
-            // below is a comparison, so when ESS lands that close to P/2 -- k equal weights and the rest negligible give exactly k in
-            // the reference's order, and k = P/2 does happen -- the sums are redone in the reference's order by one lane.
-            if (fabs(ess - 0.5 * (double)P) <= 1e-9 * (double)P) {
-                __syncthreads();
-                if (tid == 0) {
-                    double na = 0.0, nb = 0.0;
-                    for (int p = 0; p < P; ++p) { const double w = exp(sh.lw[p] - mx); na += w; nb += w * w; }
-                    sh.red[40] = (na * na) / nb;
-                }
-                __syncthreads();
-                ess = sh.red[40];
-            }
-            resample = ess <= 0.5 * (double)P;            // src/pmdi.jl:317
-        }
+        if (!lw_uniform) PMDI_SWEEP_ESS(mx, ess, resample);
 
         if (resample) {
             PH(10);
