@@ -125,9 +125,11 @@ namespace pmdi_s2 {
 // sixteen slots of the phase-timer record then hold: 0 need set, 1 terms, 2 ordered sums, 3 uncached clusters, 4 CDF, 5 class rows,
 // 6 random draws, 7 chosen clusters + history, 8 census, 9 Phi + maximum, 10 ESS sums, 11 lists of the bookkeeping phase, 12 its
 // fast path / clone, class and column work, 13 statistics, 15 clean-up, 14 the whole sweep
-// -DPM2_DETAIL_TIMERS=2: the resampling event instead -- 0 weights + uniforms, 1 pairwise cumsum, 2 u table, 3 slot counts, 4 slot
-// search, 5 ancestors, 6 per dataset: scatter + gather, 7 particles per column + class leaders, 8 column ranks, 9 id occupancy,
-// 10 id ranks, 11 counts move, 12 statistics move, 13 cache + column compaction + classes; 15 everything outside resampling
+// -DPM2_DETAIL_TIMERS=2: the resampling event instead -- 0 weights + uniforms, 1 pairwise cumsum, 2 u table, 3 slot counts, 4 particles
+// ending per slot, 5 slot owners + ancestors, 6 per dataset: scatter + gather, 7 particles per column + class leaders, 8 column ranks
+// (all rounds but the last: its ballot only), 9 id occupancy + the last round's column ranks, 10 id ranks (per batch: occupancy read,
+// ballot, barrier), 11 counts move + list of the moved ids, 12 statistics move of the batch, 13 cache + column compaction + classes;
+// 15 everything outside resampling
 #ifdef PM2_DETAIL_TIMERS
 #define PHX(i_) do { if (ap->phase && tid == 0) { const long long t_ = PM2_CLOCK(); lds<long long>(L.ph)[phd_cur] += t_ - phd_last; phd_last = t_; phd_cur = (i_); } } while (0)
 // -DPM2_DETAIL_TIMERS=3: the bookkeeping phase of dataset 0 -- 0 lists, 1 fast-path test, 2 clone-or-in-place, 3 class ids, 4 class
@@ -1429,6 +1431,39 @@ struct Sweep2 {
         }
     }
 
+    // ---- the renumbering's statistics move: clusters[k][i] = deepcopy(clusters[k][id]) for the `cnt` moved ids of a batch (src/pmdi.jl:
+    //      336).  The batch's targets are the consecutive ids nid0 .. nid0 + cnt - 1, src[j] is the id that moves to nid0 + j (ascending),
+    //      a pool row is W items of WPI words.  Items in rounds of T; the loads of up to four rounds are in flight before the one barrier
+    //      that separates them from their stores: a target lies below its source, so what a later group reads no earlier group writes ----
+    template <int WPI, class GP>
+    PM2_DEV void move_rows(GP g, int W, int cnt, int nid0, const int *src)
+    {
+        const int nitems = cnt * W;
+        for (int b = 0; b < nitems; b += 4 * T) {
+            decltype(g[0] + g[0]) val[4][WPI];
+            long long dst[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int it = b + r * T + tid;
+                dst[r] = -1;
+                if (it < nitems) {
+                    const int j = it / W, q = it - j * W;
+                    const size_t so = ((size_t)src[j] * W + q) * WPI;
+                    dst[r] = (long long)(((size_t)(nid0 + j) * W + q) * WPI);
+#pragma unroll
+                    for (int w_ = 0; w_ < WPI; ++w_) val[r][w_] = g[so + w_];
+                }
+            }
+            PM2_BARRIER();
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (dst[r] >= 0) {
+#pragma unroll
+                    for (int w_ = 0; w_ < WPI; ++w_) g[(size_t)dst[r] + w_] = val[r][w_];
+                }
+        }
+    }
+
     // ---- draw_partstar + gather + compact renumbering (src/misc.jl:27-47, src/pmdi.jl:318-340) ---------------------------------------
     PM2_DEV void resample(long long pos, double mx)
     {
@@ -1443,8 +1478,9 @@ struct Sweep2 {
         cumsum_pairwise(w, c);
         PHR(2);
         double *utab = lds<double>(L.tr);
-        u16 *jtab = lds<u16>(L.tr + L.rs_jtab), *raw = lds<u16>(L.tr + L.rs_raw), *anc = lds<u16>(L.tr + L.rs_anc);
+        u16 *nown = lds<u16>(L.tr + L.rs_jtab), *anc = lds<u16>(L.tr + L.rs_anc);
         double *red = lds<double>(L.red);
+        int *redi = lds<int>(L.red);
         if (tid == T - 1) red[0] = c[PPL - 1];
         // u += 1/particles by repeated addition (:34), exactly: the lane jumps to its first slot (pmdi_arith::resample_u_at) and adds
         // h for the following ones as the reference does
@@ -1453,49 +1489,91 @@ struct Sweep2 {
             const int j = tid * PPL;
             double u = pmdi_arith::resample_u_at(u01, P, j);
 #pragma unroll
-            for (int uu = 0; uu < PPL; ++uu) { utab[j + uu] = u; u = u + h; }
+            for (int uu = 0; uu < PPL; ++uu) { utab[j + uu] = u; nown[j + uu] = 0; u = u + h; }
         }
+        if (tid < NW) redi[RI_WBASE + tid] = 0;
         PM2_BARRIER();
         PHR(3);
-        // slots taken up to and including particle p: J_p = #{ j : pprob[p] / last >= u_j } (:32-36)
+        // slots taken up to and including particle p: J_p = #{ j : pprob[p] / last >= u_j } (:32-36).  The lane's PPL particles side by
+        // side: all the guesses first, then rounds that read both neighbours of every guess before any compare (the u table rises
+        // strictly, so the J with u[J - 1] <= q < u[J] is the only fixed point, whichever way it is approached)
+        int J[PPL];
         {
-            const double last = red[0];
+            const double last = red[0], u0 = utab[0];
+            double q[PPL];
 #pragma unroll
             for (int uu = 0; uu < PPL; ++uu) {
-                const double q = c[uu] / last;
-                int J = (int)((q - utab[0]) * (double)P) + 1;
-                if (J < 0) J = 0;
-                if (J > P) J = P;
-                while (J < P && q >= utab[J]) ++J;
-                while (J > 0 && !(q >= utab[J - 1])) --J;
-                jtab[tid * PPL + uu] = (u16)J;
+                q[uu] = c[uu] / last;
+                int g = (int)((q[uu] - u0) * (double)P) + 1;
+                if (g < 0) g = 0;
+                if (g > P) g = P;
+                J[uu] = g;
+            }
+            bool moving = true;
+            while (moving) {
+                double ua[PPL], ub[PPL];
+#pragma unroll
+                for (int uu = 0; uu < PPL; ++uu) {
+                    ua[uu] = (J[uu] < P) ? utab[J[uu]] : 0.0;
+                    ub[uu] = (J[uu] > 0) ? utab[J[uu] - 1] : 0.0;
+                }
+                moving = false;
+#pragma unroll
+                for (int uu = 0; uu < PPL; ++uu) {
+                    const bool up = J[uu] < P && q[uu] >= ua[uu];
+                    const bool dn = !up && J[uu] > 0 && !(q[uu] >= ub[uu]);
+                    J[uu] += (up ? 1 : 0) - (dn ? 1 : 0);
+                    moving = moving || up || dn;
+                }
             }
         }
-        PM2_BARRIER();
         PHR(4);
-        // slot j belongs to the first particle with J_p > j
+        // slot j belongs to the first particle with J_p > j: particle number #{ p : J_p <= j } (J rises with p), the running sum over
+        // the slots of how many particles END at each.  Every particle counts itself in at slot J_p (u16 table, 32-bit LDS atomics: two
+        // slots share a word; equal neighbours of a lane count once); the sums of the slots before a wave's are counted by ballots
+        // here, so one barrier separates the counting from the sums
         {
-            // (the lane's slots are consecutive: the answer never moves down, and the same heavy particle usually owns the next slot too)
-            int lo = 0;
 #pragma unroll
             for (int uu = 0; uu < PPL; ++uu) {
-                const int j = tid * PPL + uu;
-                if (uu == 0 || !((int)jtab[lo] > j)) {
-                    int hi = P - 1;
-                    while (lo < hi) { const int mid = (lo + hi) >> 1; if ((int)jtab[mid] > j) hi = mid; else lo = mid + 1; }
+                int cnt = 1;
+                bool start = true;
+                if (uu > 0) start = J[uu] != J[uu - 1];
+                {
+                    bool go = true;
+#pragma unroll
+                    for (int u2 = uu + 1; u2 < PPL; ++u2) { go = go && J[u2] == J[uu]; cnt += go ? 1 : 0; }
                 }
-                raw[j] = (u16)lo;
+                if (start && J[uu] < P) pm2_atomic_add((unsigned *)nown + (J[uu] >> 1), (unsigned)cnt << ((J[uu] & 1) * 16));
+            }
+#pragma unroll
+            for (int w_ = 1; w_ < NW; ++w_) {
+                int below = 0;
+#pragma unroll
+                for (int uu = 0; uu < PPL; ++uu) below += pm2_popc64(PM2_BALLOT(J[uu] < w_ * 64 * PPL));
+                if (lane == 0 && below) pm2_atomic_add(&redi[RI_WBASE + w_], below);
             }
         }
         int js = (int)(usl * (double)P);                      // shuffle!, partstar[1] = 1, sort! (:43-45)
         if (js >= P) js = P - 1;
         PM2_BARRIER();
         PHR(5);
+        {
+            int own[PPL + 1];                                 // owner of the slot before the lane's, then of the lane's slots
+            int tot_ = 0, run = 0;
 #pragma unroll
-        for (int uu = 0; uu < PPL; ++uu) {
-            const int p = tid * PPL + uu;
-            anc[p] = (p == 0) ? (u16)0 : (p <= js ? raw[p - 1] : raw[p]);
-            lw.set(uu, 1.0);                                  // src/pmdi.jl:319
+            for (int uu = 0; uu < PPL; ++uu) { run += (int)nown[tid * PPL + uu]; own[uu + 1] = run; }
+            const int ex = redi[RI_WBASE + wave] + wave_excl_scan_i(run, tot_);
+            own[0] = ex;
+#pragma unroll
+            for (int uu = 0; uu < PPL; ++uu) own[uu + 1] += ex;
+#pragma unroll
+            for (int uu = 0; uu <= PPL; ++uu) if (own[uu] > P - 1) own[uu] = P - 1;
+#pragma unroll
+            for (int uu = 0; uu < PPL; ++uu) {
+                const int p = tid * PPL + uu;
+                anc[p] = (p == 0) ? (u16)0 : (u16)(p <= js ? own[uu] : own[uu + 1]);
+                lw.set(uu, 1.0);                              // src/pmdi.jl:319
+            }
         }
         PM2_BARRIER();
         // per dataset (:320-340); the u table is dead: its LDS holds the gather tables
@@ -1562,20 +1640,27 @@ struct Sweep2 {
             }
             PM2_BARRIER();
             PHR(8);
-            // new index of every column that kept a particle
+            // new index of every column that kept a particle.  Column ranks and id ranks have per-wave count words of their own, so the
+            // barrier behind a round's counts is the only one the round needs; the last round of the columns -- the only one while
+            // ncol_old <= T -- shares its barrier with the id occupancy below (both only read mult)
             int ncol_new = 0;
-            for (int b = 0; b < ncol_old; b += T) {
-                const int cc = b + tid;
-                const bool live = cc < ncol_old && mult[cc] != 0;
+            const int cb_last = ncol_old > 0 ? ((ncol_old - 1) / T) * T : 0;
+            for (int b = 0; b < cb_last; b += T) {
+                const int cc = b + tid;                               // (cc < ncol_old: not the last round)
+                const bool live = mult[cc] != 0;
                 const u64 bal = PM2_BALLOT(live);
-                if (lane == 0) lds<int>(L.red)[RI_WCNT + wave] = pm2_popc64(bal);
+                if (lane == 0) redi[RI_WCNTC + wave] = pm2_popc64(bal);
                 PM2_BARRIER();
                 int basew = ncol_new, tot = 0;
-                for (int w_ = 0; w_ < T / 64; ++w_) { const int cnt = lds<int>(L.red)[RI_WCNT + w_]; if (w_ < wave) basew += cnt; tot += cnt; }
+                for (int w_ = 0; w_ < T / 64; ++w_) { const int cnt = redi[RI_WCNTC + w_]; if (w_ < wave) basew += cnt; tot += cnt; }
                 if (live) cmap[cc] = (u16)(basew + pm2_popc64(bal & ((1ull << lane) - 1ull)));
                 ncol_new += tot;
-                PM2_BARRIER();
+                PM2_BARRIER();                                        // (the count words are written again)
             }
+            const int ccl = cb_last + tid;
+            const bool livec = ccl < ncol_old && mult[ccl] != 0;
+            const u64 balc = PM2_BALLOT(livec);
+            if (lane == 0) redi[RI_WCNTC + wave] = pm2_popc64(balc);
             PHR(9);
             // occupancy of every old id = sum over the live columns of (particles on the column) x (entries holding the id) (:338)
             for (int idx = tid; idx < ncol_old * N; idx += T) {
@@ -1587,96 +1672,63 @@ struct Sweep2 {
                 }
             }
             PM2_BARRIER();
-            PHR(10);
-            // sort(unique(particle)) ascending -> 1..U' (:329): ranks of the live ids; the map goes to the tgt table
-            int newmax = 0;
-            for (int b = 0; b < oldmax; b += T) {
+            {
+                int basew = ncol_new, tot = 0;
+                for (int w_ = 0; w_ < T / 64; ++w_) { const int cnt = redi[RI_WCNTC + w_]; if (w_ < wave) basew += cnt; tot += cnt; }
+                if (livec) cmap[ccl] = (u16)(basew + pm2_popc64(balc & ((1ull << lane) - 1ull)));
+                ncol_new += tot;
+            }
+            // sort(unique(particle)) ascending -> 1..U' (:329): ranks of the live ids, the map goes to the tgt table; counts and cluster
+            // sizes move down with their ids (:336,:338) in the thread that ranked the id; the ids that move (every live id above the
+            // first dead one: their new ids are consecutive) are listed by new id, and their statistics follow batch by batch
+            int newmax = 0, moved = 0;
+            int *src = lds<int>(L.tr + L.rs_jtab);                    // the batch's moved ids (T ints: the slot tables are dead)
+            for (int b = 0; b < oldmax || b == 0; b += T) {
+                PHR(10);
                 const int id = 1 + b + tid;
                 int occ = 0;
                 if (id <= oldmax) occ = (id < v.idcap) ? hist[id] : PM2_G(int, v.ar.ncop())[id];
                 const bool live = occ != 0;
                 const u64 bal = PM2_BALLOT(live);
-                if (lane == 0) lds<int>(L.red)[RI_WCNT + wave] = pm2_popc64(bal);
+                if (lane == 0) redi[RI_WCNTI + wave] = pm2_popc64(bal);
                 PM2_BARRIER();
+                PHR(11);
                 int basew = newmax, tot = 0;
-                for (int w_ = 0; w_ < T / 64; ++w_) { const int cnt = lds<int>(L.red)[RI_WCNT + w_]; if (w_ < wave) basew += cnt; tot += cnt; }
-                if (id <= oldmax) v.tgt_set(id, live ? basew + pm2_popc64(bal & ((1ull << lane) - 1ull)) + 1 : 0);
-                newmax += tot;
-                PM2_BARRIER();
-            }
-            // counts and cluster sizes move down with their ids, ascending (:336,:338): read a batch, barrier, write it
-            PHR(11);
-            for (int b = 0; b < oldmax; b += T) {
-                const int id = 1 + b + tid;
-                int nid = 0, occ = 0, cnv = 0;
+                for (int w_ = 0; w_ < T / 64; ++w_) { const int cnt = redi[RI_WCNTI + w_]; if (w_ < wave) basew += cnt; tot += cnt; }
+                const int nid = live ? basew + pm2_popc64(bal & ((1ull << lane) - 1ull)) + 1 : 0;
+                int cnv = 0;
                 if (id <= oldmax) {
-                    nid = v.tgt_get(id);
-                    occ = (id < v.idcap) ? hist[id] : PM2_G(int, v.ar.ncop())[id];
+                    v.tgt_set(id, nid);
                     cnv = v.cn_get(id);
                     if (id >= v.idcap) PM2_G(int, v.ar.ncop())[id] = 0;
                 }
+                const bool mv = nid != 0 && nid != id;
                 {
-                    const u64 mvb = PM2_BALLOT(nid != 0 && nid != id);
+                    const u64 mvb = PM2_BALLOT(mv);
                     if (lane == 0 && mvb) pm2_atomic_add(&sc()[SC_TMP0], pm2_popc64(mvb));
                 }
-                PM2_BARRIER();
-                if (id <= oldmax) {
-                    if (nid) { v.counts_set(nid, occ); v.cn_set(nid, cnv); }
-                    if (id > newmax) v.counts_set(id, 0);
+                if (mv) src[nid - newmax - 1] = id;
+                PM2_BARRIER();                                        // (reads of the batch before its writes; the count words free again)
+                if (nid) { v.counts_set(nid, occ); v.cn_set(nid, cnv); }
+                const int mvall = sc()[SC_TMP0], mvr = mvall - moved;
+                moved = mvall;
+                PHR(12);
+                if (mvr != 0) {
+                    // one pool row = W items per id: Gaussian D pairs of doubles, Categorical D x L counts, NegBinom D 64-bit sums
+                    const int D = ap->ds[k].D;
+                    const int nid0 = newmax + tot - mvr + 1;
+                    const int *srcb = src + (tot - mvr);
+                    if ((GO || v.kind == K_GAUSSIAN)) move_rows<2>(PM2_G(double, v.ar.sb()), D, mvr, nid0, srcb);
+                    else if ((!GO && v.kind == K_CATEGORICAL)) move_rows<1>(PM2_G(int, v.ar.cnt()), D * v.Lc, mvr, nid0, srcb);
+                    else move_rows<1>(PM2_G(long long, v.ar.nbs()), D, mvr, nid0, srcb);
                 }
-                PM2_BARRIER();
+                newmax += tot;
             }
-            // ... and the statistics: clusters[k][i] = deepcopy(clusters[k][id]) for id > i, ascending batches (:336)
-            PHR(12);
-            if (sc()[SC_TMP0] != 0) {                         // (uniform: written before the barriers of the loop above)
-                // one pool row = W words per id: Gaussian D pairs of doubles, Categorical D x L counts, NegBinom D 64-bit sums
-                const int D = ap->ds[k].D;
-                if ((GO || v.kind == K_GAUSSIAN)) {
-                    auto sb = PM2_G(double, v.ar.sb());
-                    const long long nitems = (long long)oldmax * D;
-                    for (long long b = 0; b < nitems; b += T) {
-                        const long long it = b + tid;
-                        const int id = 1 + (int)(it / D), q = (int)(it - (long long)(id - 1) * D);
-                        const int nid = (it < nitems) ? v.tgt_get(id) : 0;
-                        const bool mv = nid != 0 && nid != id;
-                        double sg = 0.0, bt = 0.0;
-                        if (mv) { sg = sb[((size_t)id * D + q) * 2]; bt = sb[((size_t)id * D + q) * 2 + 1]; }
-                        PM2_BARRIER();
-                        if (mv) { sb[((size_t)nid * D + q) * 2] = sg; sb[((size_t)nid * D + q) * 2 + 1] = bt; }
-                    }
-                } else if ((!GO && v.kind == K_CATEGORICAL)) {
-                    auto cn_ = PM2_G(int, v.ar.cnt());
-                    const int W = D * v.Lc;
-                    const long long nitems = (long long)oldmax * W;
-                    for (long long b = 0; b < nitems; b += T) {
-                        const long long it = b + tid;
-                        const int id = 1 + (int)(it / W), q = (int)(it - (long long)(id - 1) * W);
-                        const int nid = (it < nitems) ? v.tgt_get(id) : 0;
-                        const bool mv = nid != 0 && nid != id;
-                        int c_ = 0;
-                        if (mv) c_ = cn_[(size_t)id * W + q];
-                        PM2_BARRIER();
-                        if (mv) cn_[(size_t)nid * W + q] = c_;
-                    }
-                } else {
-                    auto nb_ = PM2_G(long long, v.ar.nbs());
-                    const long long nitems = (long long)oldmax * D;
-                    for (long long b = 0; b < nitems; b += T) {
-                        const long long it = b + tid;
-                        const int id = 1 + (int)(it / D), q = (int)(it - (long long)(id - 1) * D);
-                        const int nid = (it < nitems) ? v.tgt_get(id) : 0;
-                        const bool mv = nid != 0 && nid != id;
-                        long long S_ = 0;
-                        if (mv) S_ = nb_[(size_t)id * D + q];
-                        PM2_BARRIER();
-                        if (mv) nb_[(size_t)nid * D + q] = S_;
-                    }
-                }
-            }
-            PM2_BARRIER();
+            for (int id = newmax + 1 + tid; id <= oldmax; id += T) v.counts_set(id, 0);
             PHR(13);
-            // the cache follows the renumbering (same clusters under new ids)
-            if (wave == k) {
+            // the cache follows the renumbering (same clusters under new ids; nothing to follow when no id moved and none died -- ids that
+            // die above every live one move nothing, but their slots are given up here)
+            if ((moved != 0 || newmax != oldmax) && wave == k) {
                 int *slot_id = lds<int>(v.base + L.slot_id);
                 int olds = 0, news = 0;
                 if (lane < NS) { olds = slot_id[lane]; news = olds ? v.tgt_get(olds) : 0; }
@@ -1686,8 +1738,9 @@ struct Sweep2 {
                 if (lane < NS) { slot_id[lane] = news; if (news) v.slot_set(news, lane); }
             }
             // the live columns, compacted and relabelled (:331-337), in rounds of whole columns (a round's targets lie at or below
-            // its sources, later rounds' sources above them)
-            {
+            // its sources, later rounds' sources above them).  No id moved and no column died: the identity, skipped; no id moved:
+            // the entries keep their values
+            if (moved != 0 || ncol_new != ncol_old) {
                 const int cpr = (2 * T) / N;                       // columns per round: two entries per lane
                 for (int c0 = 0; c0 < ncol_old; c0 += cpr) {
                     int nv[2], dc[2], dn[2];
@@ -1696,7 +1749,7 @@ struct Sweep2 {
                         const int idx = h * T + tid;
                         const int cc = c0 + idx / N, nn = idx - (idx / N) * N;
                         nv[h] = 0; dc[h] = -1; dn[h] = nn;
-                        if (idx < cpr * N && cc < ncol_old && mult[cc] != 0) { nv[h] = v.tgt_get(v.tab_get(cc, nn)); dc[h] = cmap[cc]; }
+                        if (idx < cpr * N && cc < ncol_old && mult[cc] != 0) { nv[h] = v.tab_get(cc, nn); if (moved != 0) nv[h] = v.tgt_get(nv[h]); dc[h] = cmap[cc]; }
                     }
                     PM2_BARRIER();
 #pragma unroll
@@ -1733,7 +1786,6 @@ struct Sweep2 {
 #pragma unroll
                 for (int uu = 0; uu < PPL; ++uu) csl_put(k, uu, rk[uu]);
                 if (tid == 0) {
-                    const int moved = sc()[SC_TMP0];
                     dsc[DS_NCLS] = nc2; dsc[DS_NCOL] = ncol_new; dsc[DS_MAXID] = newmax; dsc[DS_DIRTY] = 1;
                     long long *w_ = wk(k);
                     w_[WK_COLS] += ncol_old; w_[WK_MOVED] += moved; w_[WK_MOVE_EVENTS] += moved ? 1 : 0;

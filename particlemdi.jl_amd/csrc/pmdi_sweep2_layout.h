@@ -35,6 +35,8 @@ PM2_HD constexpr bool cdf_rows_in_arena(int NW) { return NW > 4; }
 constexpr int KCAPMAX = 256;    // (class, label) keys a step may touch at most (the key lists of the bookkeeping phase; Layout::kcap)
 constexpr int RI_CLSMIN = 64, RI_NEWSLOT = 96, RI_CLSVAL = 128;     // resampling: per-class scratch (CLSMAX ints each), int offsets into the reduction area
 constexpr int RI_WCNT = 160;                                         // ... and per-wave counts of the block scans (NWMAX ints)
+constexpr int RI_WBASE = 168;                                        // ... particles that end below each wave's first slot (NWMAX ints)
+constexpr int RI_WCNTC = 176, RI_WCNTI = 184;                        // ... per-wave counts of the column ranks and of the id ranks (NWMAX ints each)
 constexpr int RD_MAX = 0, RD_MIN = NWMAX, RD_SA = 2 * NWMAX, RD_SQ = 3 * NWMAX;      // doubles of the reduction area: per-wave maxima, minima, sums
 constexpr int KMAX2 = 4;        // datasets (one owner wave each)
 constexpr int NONE8 = 0xFF;
@@ -58,7 +60,7 @@ PM2_HD void make_layout(int K, int N, int P, int Dmax, int cols_l, int idcap, in
     auto take = [&](int bytes) { const int at = o; o = (o + bytes + 15) & ~15; return at; };
     const int Dp = (Dmax + 1) & ~1;
     L.Dp = Dp; L.cols_l = cols_l; L.idcap = idcap;
-    L.red = take(128 * 8);       // reductions: doubles [0,32) per-wave maxima / minima / sums (RD_*), ints [64,168) resampling scratch (RI_*), doubles [120] tie, [121] carry
+    L.red = take(128 * 8);       // reductions: doubles [0,32) per-wave maxima / minima / sums (RD_*), ints [64,192) resampling scratch (RI_*), doubles [120] tie, [121] carry
     L.sc = take(SC_COUNT * 4);
     L.stat = take(8 * 8);
     L.wk = take(KMAX2 * 8 * 8);

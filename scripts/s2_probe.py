@@ -47,8 +47,8 @@ for it in range(burn + iters):
 if os.environ.get("PMDI_PHASE_TIMERS"):
     names = ["prefix", "cluster", "wait1", "particle", "wait2", "ess+book", "wait3", "follow", "resample", "finish"]
     if os.environ.get("PM2_DETAIL") == "2":   # -DPM2_DETAIL_TIMERS=2: inside the resampling events
-        names = ["exp+uniforms", "cumsum", "utab", "slotcounts", "search", "ancestors", "scatter+gather", "percolumn+leaders", "colranks", "idocc",
-                 "idranks", "countsmove", "statsmove", "cache+cols+classes", None, "outside"]
+        names = ["exp+uniforms", "cumsum", "utab", "slotcounts", "slotends", "owners+ancestors", "scatter+gather", "percolumn+leaders", "colranks-early", "idocc+colranks",
+                 "idranks", "countsmove+list", "statsmove", "cache+cols+classes", None, "outside"]
     elif os.environ.get("PM2_DETAIL") == "3":   # -DPM2_DETAIL_TIMERS=3: inside the bookkeeping phase of dataset 0
         names = ["lists", "fasttest", "clone-or-inplace", "classids", "classreps", "colsplits", "classlist", "chosenstats", "cleanup", "barrier3",
                  None, None, None, None, None, "outside"]
