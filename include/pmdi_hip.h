@@ -431,6 +431,47 @@ int pmdi_psm_blocksum_device(int32_t device, const int32_t *counts, int64_t S, i
                              const int32_t *group /* host, n */, int32_t G,
                              int64_t *out /* device, [M][G][G], M = K + (K > 1) */, void *stream);
 
+/* ---- plot_pmdi_data (src/output_analysis/feature_select_plots.jl:27-166): sums of a data matrix over a grouping of its rows ----
+ * The reference gathers dataFile[order_rows, order_cols], optionally z-scored and discretised (:39-46), and hands n x D cells
+ * to a plotting library.  pmdi_data_groupsum_device sums a device-resident data matrix over a grouping of its rows instead.
+ * With the pixel bins of the leaf order as groups the result is the figure's data binned to pixels (one group per observation:
+ * the permuted matrix itself); with cluster labels it is, per cluster and feature, the sufficient statistics of cluster_add!
+ * (src/datatypes/) for a clustering of the caller's choice: size, sum and spread for Gaussian data, level counts for
+ * Categorical data, sums for NegBinom data.
+ *
+ * x: DEVICE memory, row-major: element (i, d) at x[i * ld + d], ld >= D -- the layout pmdi_create keeps the data in (a
+ * column-major caller transposes once, as pmdi_create does).  kind: PMDI_GAUSSIAN = Float64, PMDI_CATEGORICAL or PMDI_NEGBINOM
+ * = Int64.  No alignment beyond 8 bytes is assumed and ld may be odd.  group: HOST int32 [n], values 0..G-1; a group may be
+ * empty.  device: the HIP device ordinal; the call is stateless.
+ * The value v(i, d) of an element, by mode:
+ *   PMDI_DATA_RAW     x                                                            Float64 or Int64
+ *   PMDI_DATA_SQDEV   t = x - shift[d], then v = t * t: two IEEE operations, never fused   Gaussian only
+ *   PMDI_DATA_ZBIN    z = floor((x - shift[d]) / scale[d]) clamped to -2..2, as an integer (:41-45)   Gaussian only; a non-finite
+ *                     x raises a device flag: PMDI_E_DATA, out undefined
+ *   PMDI_DATA_LEVELS  one count into level x - 1 of L levels                       Categorical only; a level outside 1..L:
+ *                     PMDI_E_DATA, out undefined
+ * The host plan is that of pmdi_psm_blocksum_device: the observations sorted by group with a stable counting sort (ascending
+ * observation index inside a group), every group's run cut into chunks of at most 32 rows; a chunk never spans two groups.
+ * out for RAW or SQDEV on Gaussian data: DEVICE Float64 [G][D], BIT-DEFINED by this order: the partial of chunk c and column d
+ * is p(c, d) = ((0.0 + v(r0, d)) + v(r1, d)) + ... over the chunk's rows in plan order, and out[g][d] = ((0.0 + p(c0, d)) +
+ * p(c1, d)) + ... over the chunks of g in plan order; an empty group gives 0.0; a NaN in the data propagates as IEEE says.
+ * out for RAW on Int64 data and for ZBIN: DEVICE Int64 [G][D]; for LEVELS: DEVICE Int32 [G][D][L].  These are exact in any
+ * order.  An Int64 sum that leaves the int64 range is the caller's error and is not checked.
+ * EVERY element of out is written, whatever it held before.  The call allocates the plan tables (4 n + 8 ceil(n / 32) + 12 G +
+ * 16 D + 64 bytes at the most) and, for a Float64 result, nchunks D doubles of partials (nchunks <= n / 32 + G); it frees them
+ * before it returns and therefore SYNCHRONISES `stream`, which also lets it report the data flag.  An allocation that fails is
+ * PMDI_E_MEMORY.
+ * PMDI_E_ARG, before any device use: a null x, group or out; n outside 1..65535; D outside 1..65535; ld < D; G outside
+ * 1..PMDI_BLOCKSUM_GMAX; a group value outside 0..G-1; an unknown kind or mode; SQDEV or ZBIN on integer data; LEVELS on anything
+ * but Categorical; SQDEV without shift; ZBIN without shift and scale, or with a shift that is not finite, or a scale that is not
+ * finite and > 0; LEVELS with L outside 1..4096 or G D L > 2^28.  shift, scale and L are not read by the modes that do not name
+ * them. */
+enum { PMDI_DATA_RAW = 0, PMDI_DATA_SQDEV = 1, PMDI_DATA_ZBIN = 2, PMDI_DATA_LEVELS = 3 };
+int pmdi_data_groupsum_device(int32_t device, int32_t kind, const void *x, int64_t n, int32_t D, int64_t ld,
+                              const int32_t *group /* host, n */, int32_t G, int32_t mode,
+                              const double *shift /* host, D, or NULL */, const double *scale /* host, D, or NULL */,
+                              int32_t L, void *out /* device */, void *stream);
+
 /* ---- device-resident Gibbs chains -----------------------------------------
  * Everything pmdi() does per iteration AROUND the sweep, for every chain of the handle, without leaving the
  * device: shuffle!(order_obs) (src/pmdi.jl:172), update_M!, update_gamma!, Pi, update_Phi!, update_Z, update_v

@@ -14,6 +14,9 @@ from .psm import (  # noqa: F401,E402
     block_similarity, block_sums, consensus_map, refine_allocations,
     retained_iterations, row_scores, score_allocations, search_consensus_allocation, select_consensus_allocations, vi_log2_table,
 )
+from .datamap import (  # noqa: F401,E402
+    ClusterProfiles, DataMap, cluster_profiles, column_moments, data_map, group_sums,
+)
 from .fusion import FusionAccumulator, FusionCounts, fused_consensus_allocations  # noqa: F401,E402
 from .summary import (  # noqa: F401,E402
     PosteriorSummary, SummaryAccumulator, get_feature_select_probs, get_nclust, get_phi,

@@ -13,7 +13,7 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("PMDI_LIB_PATH") or os.path.join(_PKG, "libpmdi_hip.so")   # override: A/B builds only
-_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_fusion.hip", "pmdi_summary.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_psm_refine_vi.hip", "pmdi_psm_blocksum.hip", "pmdi_api.cpp", "pmdi_plan.cpp", "pmdi_acc.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
+_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_fusion.hip", "pmdi_summary.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_psm_refine_vi.hip", "pmdi_psm_blocksum.hip", "pmdi_data_groupsum.hip", "pmdi_api.cpp", "pmdi_plan.cpp", "pmdi_acc.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
 # every header decides when to rebuild: a new one cannot be forgotten
 _HEADERS = sorted(glob.glob(os.path.join(_PKG, "csrc", "*.h"))) + [os.path.join(_ROOT, "include", "pmdi_hip.h")]
 
@@ -25,6 +25,7 @@ ABI_VERSION = 2
 KMAX = 8
 REFINE_GMAX = 4096      # PMDI_REFINE_GMAX of include/pmdi_hip.h
 BLOCKSUM_GMAX = 2048    # PMDI_BLOCKSUM_GMAX of include/pmdi_hip.h
+DATA_RAW, DATA_SQDEV, DATA_ZBIN, DATA_LEVELS = 0, 1, 2, 3      # PMDI_DATA_* of include/pmdi_hip.h
 
 EXPORTS = [
     "pmdi_create", "pmdi_destroy", "pmdi_last_error", "pmdi_abi_version", "pmdi_sweep",
@@ -44,7 +45,7 @@ EXPORTS = [
     "pmdi_summary_create", "pmdi_summary_destroy", "pmdi_summary_reset", "pmdi_summary_add_gibbs", "pmdi_summary_add_arrays",
     "pmdi_summary_samples", "pmdi_summary_get", "pmdi_gibbs_run2",
     "pmdi_psm_score_device", "pmdi_psm_rowscore_device", "pmdi_psm_refine_device", "pmdi_vi_log2_table", "pmdi_psm_refine_vi_device",
-    "pmdi_psm_blocksum_device",
+    "pmdi_psm_blocksum_device", "pmdi_data_groupsum_device",
     "pmdi_fusion_create", "pmdi_fusion_destroy", "pmdi_fusion_reset", "pmdi_fusion_add_samples", "pmdi_fusion_add_gibbs",
     "pmdi_fusion_merge", "pmdi_fusion_samples", "pmdi_fusion_groups", "pmdi_fusion_counts", "pmdi_gibbs_run3",
     "pmdi_sweep_layout",
@@ -218,6 +219,8 @@ def lib():
     L.pmdi_psm_refine_vi_device.argtypes = [i32, vp, i64, i32, i64, i32, vp, i64, i64, i32, vp, vp, vp, vp, vp]
     L.pmdi_psm_blocksum_device.restype = C.c_int
     L.pmdi_psm_blocksum_device.argtypes = [i32, vp, i64, i32, i64, vp, i32, vp, vp]
+    L.pmdi_data_groupsum_device.restype = C.c_int
+    L.pmdi_data_groupsum_device.argtypes = [i32, i32, vp, i64, i32, i64, vp, i32, i32, vp, vp, i32, vp, vp]
     L.pmdi_cutree.restype = C.c_int
     L.pmdi_cutree.argtypes = [i64, vp, vp, i64, dbl, vp]
     L.pmdi_psm_acc_create.restype = C.c_int

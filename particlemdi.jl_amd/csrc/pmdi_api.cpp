@@ -5,6 +5,7 @@
 // compute entry point runs on the gfx950 device or fails.
 #include "pmdi_arith.h"           // uniform01: the initial feature flags
 #include "pmdi_host.h"
+#include "pmdi_data_groupsum_plan.h"
 #include "pmdi_psm_blocksum_plan.h"
 #include "pmdi_sweep_carve.h"
 
@@ -878,6 +879,69 @@ int pmdi_psm_blocksum_device(int32_t device, const int32_t *counts, int64_t S, i
                                                   (unsigned long long *)out, st);
     if (e != hipSuccess) return fail(PMDI_E_DEVICE, "psm-blocksum launch: %s", hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(st));               // the tables (and the plan they were copied from) are freed on return
+    return PMDI_OK;
+}
+
+static_assert(PMDI_DATA_RAW == PMDI_DATA_RAW_I && PMDI_DATA_SQDEV == PMDI_DATA_SQDEV_I && PMDI_DATA_ZBIN == PMDI_DATA_ZBIN_I &&
+                  PMDI_DATA_LEVELS == PMDI_DATA_LEVELS_I, "the header's modes are the kernels'");
+
+int pmdi_data_groupsum_device(int32_t device, int32_t kind, const void *x, int64_t n, int32_t D, int64_t ld, const int32_t *group,
+                              int32_t G, int32_t mode, const double *shift, const double *scale, int32_t L, void *out, void *stream)
+{
+    const char *who = "pmdi_data_groupsum_device";
+    if (!x || !group || !out) return fail(PMDI_E_ARG, "%s: null argument", who);
+    if (n < 1 || n > 65535 || D < 1 || D > 65535 || ld < D || G < 1 || G > PMDI_BLOCKSUM_GMAX)
+        return fail(PMDI_E_ARG, "%s: n=%lld D=%d ld=%lld G=%d out of range (n, D <= 65535, ld >= D, G <= %d)", who, (long long)n, D,
+                    (long long)ld, G, PMDI_BLOCKSUM_GMAX);
+    if (kind != PMDI_GAUSSIAN && kind != PMDI_CATEGORICAL && kind != PMDI_NEGBINOM) return fail(PMDI_E_ARG, "%s: unknown kind %d", who, kind);
+    if (mode != PMDI_DATA_RAW && mode != PMDI_DATA_SQDEV && mode != PMDI_DATA_ZBIN && mode != PMDI_DATA_LEVELS)
+        return fail(PMDI_E_ARG, "%s: unknown mode %d", who, mode);
+    const bool is_float = kind == PMDI_GAUSSIAN;
+    if ((mode == PMDI_DATA_SQDEV || mode == PMDI_DATA_ZBIN) && !is_float)
+        return fail(PMDI_E_ARG, "%s: mode %d needs Gaussian (Float64) data, not kind %d", who, mode, kind);
+    if (mode == PMDI_DATA_LEVELS && kind != PMDI_CATEGORICAL) return fail(PMDI_E_ARG, "%s: PMDI_DATA_LEVELS needs Categorical data, not kind %d", who, kind);
+    if (mode == PMDI_DATA_SQDEV && !shift) return fail(PMDI_E_ARG, "%s: PMDI_DATA_SQDEV without shift", who);
+    if (mode == PMDI_DATA_ZBIN) {
+        if (!shift || !scale) return fail(PMDI_E_ARG, "%s: PMDI_DATA_ZBIN without shift and scale", who);
+        for (int d = 0; d < D; ++d)
+            if (!std::isfinite(shift[d]) || !std::isfinite(scale[d]) || !(scale[d] > 0.0))
+                return fail(PMDI_E_ARG, "%s: shift[%d]=%g, scale[%d]=%g: not finite, or scale <= 0", who, d, shift[d], d, scale[d]);
+    }
+    if (mode == PMDI_DATA_LEVELS && (L < 1 || L > 4096 || (long long)G * D * L > (1LL << 28)))
+        return fail(PMDI_E_ARG, "%s: L=%d outside 1..4096, or G D L = %lld > 2^28", who, L, (long long)G * D * L);
+    PsmBlocksumPlan plan;
+    const long long bad = psm_blocksum_plan(group, n, G, plan);
+    if (bad >= 0) return fail(PMDI_E_ARG, "%s: group[%lld]=%d outside 0..%d", who, bad, group[bad], G - 1);
+    const int nchunks = plan.nchunks();
+    const std::vector<int> chunks_at = data_groupsum_chunks_at(plan);      // the first chunk of every group
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const bool f_out = is_float && (mode == PMDI_DATA_RAW || mode == PMDI_DATA_SQDEV);
+    const bool up_shift = mode == PMDI_DATA_SQDEV || mode == PMDI_DATA_ZBIN, up_scale = mode == PMDI_DATA_ZBIN;
+    // one allocation: the doubles first, then the int tables (the plan's 16-bit label copies are not uploaded), then the flag
+    const size_t o_scale = (size_t)D * 8, o_perm = 2 * (size_t)D * 8, o_at = o_perm + (size_t)n * 4, o_info = o_at + ((size_t)nchunks + 1) * 4,
+                 o_gat = o_info + (size_t)nchunks * 4, o_flag = o_gat + ((size_t)G + 1) * 4, bytes = o_flag + 4;
+    Scratch tab, part;
+    HIP_TRY(hipMalloc(&tab.p, bytes));
+    if (f_out) HIP_TRY(hipMalloc(&part.p, (size_t)nchunks * D * 8));
+    char *d = (char *)tab.p;
+    if (up_shift) HIP_TRY(hipMemcpyAsync(d, shift, (size_t)D * 8, hipMemcpyHostToDevice, st));
+    if (up_scale) HIP_TRY(hipMemcpyAsync(d + o_scale, scale, (size_t)D * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d + o_perm, plan.perm.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d + o_at, plan.chunk_at.data(), ((size_t)nchunks + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d + o_info, plan.chunk_info.data(), (size_t)nchunks * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d + o_gat, chunks_at.data(), ((size_t)G + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d + o_flag, 0, 4, st));
+    const hipError_t e = pmdi_launch_data_groupsum(is_float ? 1 : 0, x, D, ld, G, mode, (const int *)(d + o_perm), (const int *)(d + o_at),
+                                                   (const int *)(d + o_info), nchunks, (const int *)(d + o_gat),
+                                                   up_shift ? (const double *)d : nullptr, up_scale ? (const double *)(d + o_scale) : nullptr,
+                                                   L, (double *)part.p, out, (int *)(d + o_flag), st);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "data-groupsum launch: %s", hipGetErrorString(e));
+    int flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, d + o_flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));               // the tables and the partials are freed on return
+    if (flag && mode == PMDI_DATA_ZBIN) return fail(PMDI_E_DATA, "%s: a non-finite element in PMDI_DATA_ZBIN", who);
+    if (flag) return fail(PMDI_E_DATA, "%s: a level outside 1..%d in PMDI_DATA_LEVELS", who, L);
     return PMDI_OK;
 }
 

@@ -265,6 +265,14 @@ void pmdi_vi_log2_table_host(int *out);
 hipError_t pmdi_launch_psm_blocksum(const int *counts, long long S, int K, long long n, int G, const unsigned short *g16, long long npad,
                                     const int *perm, const int *chunk_at, const int *chunk_info, int nchunks, const int *gsize,
                                     unsigned long long *out, hipStream_t stream);
+// sums of a data matrix over a grouping of its rows (pmdi_data_groupsum.hip): perm, chunk_at, chunk_info of PsmBlocksumPlan and
+// chunks_at [G + 1], the first chunk of every group, on the device; x row-major with leading dimension ld, doubles (is_float) or
+// int64; shift, scale [D] or null as the mode needs; part [nchunks][D] doubles for a Float64 result (RAW or SQDEV on doubles),
+// else null; flag [1] zeroed by the caller.  out: [G][D] doubles or int64, or [G][D][L] int32 (LEVELS), every element written
+enum { PMDI_DATA_RAW_I = 0, PMDI_DATA_SQDEV_I = 1, PMDI_DATA_ZBIN_I = 2, PMDI_DATA_LEVELS_I = 3 };      // PMDI_DATA_* of include/pmdi_hip.h
+hipError_t pmdi_launch_data_groupsum(int is_float, const void *x, int D, long long ld, int G, int mode, const int *perm, const int *chunk_at,
+                                     const int *chunk_info, int nchunks, const int *chunks_at, const double *shift, const double *scale,
+                                     int L, double *part, void *out, int *flag, hipStream_t stream);
 
 // One add of the streaming summary accumulator (pmdi_summary.hip): the source arrays in the GibbsArgs layouts, the
 // accumulator's state, and this add's trace row.

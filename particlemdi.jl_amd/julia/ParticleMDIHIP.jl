@@ -484,6 +484,22 @@ function psm_blocksum_device(counts::Ptr{Cvoid}, S::Integer, K::Integer, n::Inte
     return K > 1 ? vcat(fill(Int64(S), K), Int64(S) * K) : [Int64(S)]
 end
 
+# ---- plot_pmdi_data (feature_select_plots.jl:27-166): sums of a data matrix over a grouping of its rows (pmdi_data_groupsum_device;
+# not executed, as above) ----
+# x: device pointer to the ROW-MAJOR n x D matrix (element (i, d) at x[i * ld + d]: a Julia matrix transposed once), Float64 for
+# kind = GaussianCluster, Int64 otherwise; group as above; mode: DATA_RAW, DATA_SQDEV (shift), DATA_ZBIN (shift, scale) or DATA_LEVELS
+# (L); out: device pointer to Float64 or Int64 [G][D], or Int32 [G][D][L], filled.  Synchronises.
+const DATA_RAW, DATA_SQDEV, DATA_ZBIN, DATA_LEVELS = Int32(0), Int32(1), Int32(2), Int32(3)
+function data_groupsum_device(kind::Integer, x::Ptr{Cvoid}, n::Integer, D::Integer, group::Vector{Int32}, G::Integer, mode::Integer,
+                              out::Ptr{Cvoid}; ld::Integer = D, shift::Union{Vector{Float64}, Nothing} = nothing,
+                              scale::Union{Vector{Float64}, Nothing} = nothing, L::Integer = 0, device::Integer = 0,
+                              stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:pmdi_data_groupsum_device, LIB), Cint,
+                (Int32, Int32, Ptr{Cvoid}, Int64, Int32, Int64, Ptr{Int32}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
+                device, kind, x, n, D, ld, group, G, mode, shift === nothing ? C_NULL : shift, scale === nothing ? C_NULL : scale, L, out, stream))
+    return nothing
+end
+
 # ---- the cluster plugin protocol on the device (unit-level entry points) ----------------------
 # calc_logprob / cluster_add! / calc_logmarginal for a batch of stand-alone clusters of dataset k;
 # see pmdi_clusters_new, pmdi_cluster_add, pmdi_calc_logprob, pmdi_calc_logmarginal in the header.
