@@ -658,6 +658,66 @@ int pmdi_fusion_counts(pmdi_fusion *a, const int32_t **fused, const int32_t **co
 int pmdi_gibbs_run3(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ,
                     pmdi_fusion *fus, void *stream);
 
+/* ---- streaming mixing accumulator: the clustering autocorrelation and what an effective sample size needs, per chain ----
+ * The fourth accumulator beside pmdi_psm_acc, pmdi_summary and pmdi_fusion.  R-hat (pmdi_summary) compares chains with each
+ * other; this one looks inside a chain: the reference's clustrand (src/output_analysis/acf_plots.jl:41-59, default maxlag =
+ * 20), the mean adjusted Rand index between a chain's allocations `lag` retained rows apart, and the lagged products of M, Phi
+ * and the cluster counts from which the host forms autocorrelations, an integrated autocorrelation time and an ESS.
+ * C = n_chains, K datasets, N labels, n observations, L = maxlag >= 1, npairs = K (K - 1) / 2; T = adds so far.  Lags count
+ * RETAINED samples (thin is already applied).  For chain c, dataset k, add t (1-based) and lag l in 1..min(L, t - 1) let n_ab be
+ * the number of observations with label a in sample t and label b in sample t - l, and (all Int64)
+ *     A = sum_ab n_ab (n_ab - 1) / 2,  P_t = sum_a h_a (h_a - 1) / 2 (h = the label histogram of sample t),  Q = P_{t-l},
+ *     T2 = n (n - 1) / 2.
+ * Arrays (row-major, the order of pmdi_mixing_get):
+ *   rand_num [C][K][L] Int64    every add contributes T2 + 2 A - P_t - P_{t-l}, the pairs of observations on which the two
+ *                               partitions agree: exact in any order.  Mean Rand index = rand_num / ((T - l) T2).
+ *   ari_sum  [C][K][L] Float64  the sum over t, in retention order, of the add's adjusted Rand index; one lane per entry,
+ *                               separate IEEE double operations (never fused):
+ *                                   e = (double)P * (double)Q / (double)T2;  m = ((double)P + (double)Q) / 2.0;  den = m - e;
+ *                                   ari = (den == 0.0) ? 1.0 : ((double)A - e) / den;  ari_sum = ari_sum + ari;
+ *                               den == 0: both partitions are trivial.  n = 1: T2 = 0 and ari is 1.0 by definition, without
+ *                               dividing.  A plain loop over the same integers reproduces every bit.
+ *   Scalars: J = 2 K + npairs per chain, in this order: M_k (K), Phi_p (npairs), nclust_k (K; the number of non-zero bins of
+ *   the histogram behind P_t, as a double).  With x1 the chain's first retained value of a scalar and y_t = x_t - x1 (the shift
+ *   keeps the cancellation in the autocovariance small):
+ *   sum_y [C][J] Float64        ((0.0 + y_1) + y_2) + ...
+ *   prod  [C][J][L + 1] Float64 prod[l] = prod[l] + y_t * y_{t-l} for every t > l, l = 0..L: a multiply, then an add
+ *   head  [C][J][L] Float64     y_1 .. y_L, zero where T has not reached
+ *   tail  [C][J][L] Float64     y_{T-L+1} .. y_T, oldest first; zero in front of y_1 while T < L
+ *   first [C][J] Float64        x1
+ *   All bit-defined by the retention order.  With m = sum_y / T the lag-l autocovariance about the chain mean is
+ *       (prod[l] - m ((sum_y - sum(head[0..l-1])) + (sum_y - sum(tail[L-l..L-1]))) + (T - l) m m) / T        (l < T).
+ * Device state, one slab: the arrays; a ring of L + 1 slots of label bytes, sample t in slot t mod (L + 1), every (chain,
+ * dataset) row padded to a multiple of 32 bytes; a ring of P_t [L + 1][C][K] Int64; a ring of the scalars; an error flag.
+ * Footprint: (L + 1) C K ceil(n / 32) 32 bytes for the labels (2.6 GB for 3072 chains, K = 4, n = 10000, L = 20) plus
+ * 8 (C K (4 L + 2) + C J (4 L + 4)) bytes for everything else.
+ * create: 1 <= K <= PMDI_KMAX, 2 <= N <= 255, 1 <= n <= 65535, 1 <= maxlag <= 1024, n_chains >= 1 and n_chains * K <=
+ *   INT32_MAX, all checked before the device is touched (PMDI_E_ARG), as is the size (PMDI_E_MEMORY beyond 4e18 bytes); no
+ *   usable device is PMDI_E_DEVICE, a failed allocation PMDI_E_MEMORY.
+ * add_arrays: device arrays in the layouts of the resident state: s [C][K][n] 0-based int32, M [C][K], Phi [C][max(1, npairs)].
+ *   A label outside 0..N-1 is counted nowhere (it matches no label of any other sample) and sets a device flag that
+ *   pmdi_mixing_get reports as PMDI_E_DATA until pmdi_mixing_reset.
+ * add_gibbs: the current s, M, Phi of every chain of g.  PMDI_E_ARG unless g's device, n_chains, K, N, n are the accumulator's.
+ * T is bounded by INT32_MAX: an add that would pass it is PMDI_E_ARG and changes nothing.
+ * get: SYNCHRONISES `stream`, then copies to the host arrays that are not NULL.
+ * reset: everything zero, T = 0.  One device, not thread-safe, asynchronous on `stream` except create, destroy and get; all
+ * calls on one accumulator go on ONE stream. */
+typedef struct pmdi_mixing pmdi_mixing;
+int pmdi_mixing_create(int32_t device, int32_t n_chains, int32_t K, int32_t N, int64_t n, int32_t maxlag, pmdi_mixing **out);
+int pmdi_mixing_destroy(pmdi_mixing *a);
+int pmdi_mixing_reset(pmdi_mixing *a, void *stream);
+int pmdi_mixing_add_gibbs(pmdi_mixing *a, pmdi_gibbs *g, void *stream);
+int pmdi_mixing_add_arrays(pmdi_mixing *a, const int32_t *s, const double *M, const double *Phi, void *stream);
+int64_t pmdi_mixing_samples(const pmdi_mixing *a);      /* T, the number of adds */
+int pmdi_mixing_get(pmdi_mixing *a, int64_t *rand_num, double *ari_sum, double *sum_y, double *prod, double *head, double *tail,
+                    double *first, void *stream);
+
+/* pmdi_gibbs_run3 with the fourth accumulator: after every retained local iteration acc, then summ, then fus, then mix get
+ * their add; any may be NULL, and pmdi_gibbs_run3(g, ..., acc, summ, fus, stream) is pmdi_gibbs_run4(g, ..., acc, summ, fus,
+ * NULL, stream).  All are checked against g and against their limits before the first iteration runs. */
+int pmdi_gibbs_run4(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ,
+                    pmdi_fusion *fus, pmdi_mixing *mix, void *stream);
+
 /* Device pointers of the resident state (zero-copy consumers; layouts of pmdi_sweep_device). */
 typedef struct {
     double *M, *gamma, *gamma0, *Phi, *vZ, *Pi, *log1p_phi, *feature_prob, *logweight;

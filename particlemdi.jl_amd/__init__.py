@@ -21,3 +21,4 @@ from .fusion import FusionAccumulator, FusionCounts, fused_consensus_allocations
 from .summary import (  # noqa: F401,E402
     PosteriorSummary, SummaryAccumulator, get_feature_select_probs, get_nclust, get_phi,
 )
+from .mixing import MixingAccumulator, MixingSummary  # noqa: F401,E402

@@ -1,5 +1,5 @@
-// pmdi_acc.cpp -- the streaming accumulators of include/pmdi_hip.h (pmdi_psm_acc_*, pmdi_fusion_*, pmdi_summary_*) and their
-// driver pmdi_gibbs_run / run2 / run3, which needs nothing of a pmdi_gibbs but the public pmdi_gibbs_step.
+// pmdi_acc.cpp -- the streaming accumulators of include/pmdi_hip.h (pmdi_psm_acc_*, pmdi_fusion_*, pmdi_summary_*, pmdi_mixing_*) and
+// their driver pmdi_gibbs_run / run2 / run3 / run4, which needs nothing of a pmdi_gibbs but the public pmdi_gibbs_step.
 #include "pmdi_host.h"
 
 #include <cstring>
@@ -45,6 +45,20 @@ struct pmdi_summary {
     size_t count[SUM_ARRAYS] = {};       // elements of each array ...
     char *at[SUM_ARRAYS] = {};           // ... and where it starts in the slab (int64: hist, nsum, nsumsq, flag_count, tr_nclust; else double)
     int *err = nullptr, *nclust = nullptr;
+    int64_t T = 0;                       // adds so far
+};
+
+// Streaming mixing accumulator (pmdi_mixing_* entry points): one device slab -- the arrays of include/pmdi_hip.h one after the
+// other (8-byte elements) and the error flag (what reset zeroes), then the rings of P and of the scalars and the per-add
+// scratch, then the ring of label bytes
+enum { MIX_RAND, MIX_ARI, MIX_SUMY, MIX_PROD, MIX_HEAD, MIX_TAIL, MIX_FIRST, MIX_ARRAYS };      // the order of pmdi_mixing_get's arguments
+struct pmdi_mixing {
+    int device = 0;
+    MixingArgs ma{};                     // everything of an add but its sources
+    char *slab = nullptr;
+    size_t state_bytes = 0;              // what reset zeroes: every array and the error flag
+    size_t count[MIX_ARRAYS] = {};       // elements of each array ...
+    char *at[MIX_ARRAYS] = {};           // ... and where it starts in the slab (int64: rand_num; else double)
     int64_t T = 0;                       // adds so far
 };
 
@@ -110,6 +124,19 @@ int summary_accepts(const pmdi_summary *a, const pmdi_gibbs *g, int64_t n_adds)
                     a->n, c.n_chains, c.K, c.N, (long long)c.n);
     if (a->sumD != g->h->sumD && !(a->sumD == 0 && !g->feature_select))
         return fail(PMDI_E_ARG, "the accumulator holds sumD=%lld, the chains sumD=%d", a->sumD, g->h->sumD);
+    if (c.device != a->device) return fail(PMDI_E_ARG, "the chains live on device %d, the accumulator on device %d", c.device, a->device);
+    if (n_adds > 2147483647LL - a->T) return fail(PMDI_E_ARG, "%lld + %lld adds pass INT32_MAX", (long long)a->T, (long long)n_adds);
+    return PMDI_OK;
+}
+
+// what pmdi_mixing_add_gibbs checks before it touches anything (pmdi_gibbs_run4 asks once, before its first iteration)
+int mixing_accepts(const pmdi_mixing *a, const pmdi_gibbs *g, int64_t n_adds)
+{
+    const pmdi_config &c = g->h->cfg;
+    const MixingArgs &m = a->ma;
+    if (c.n_chains != m.C || c.K != m.K || c.N != m.N || c.n != m.n)
+        return fail(PMDI_E_ARG, "the accumulator holds n_chains=%d K=%d N=%d n=%lld, the chains n_chains=%d K=%d N=%d n=%lld", m.C, m.K, m.N,
+                    m.n, c.n_chains, c.K, c.N, (long long)c.n);
     if (c.device != a->device) return fail(PMDI_E_ARG, "the chains live on device %d, the accumulator on device %d", c.device, a->device);
     if (n_adds > 2147483647LL - a->T) return fail(PMDI_E_ARG, "%lld + %lld adds pass INT32_MAX", (long long)a->T, (long long)n_adds);
     return PMDI_OK;
@@ -445,8 +472,110 @@ int pmdi_summary_get(pmdi_summary *a, int64_t *nclust_hist, int64_t *nclust_sum,
     return PMDI_OK;
 }
 
-int pmdi_gibbs_run3(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
-                    void *stream)
+int pmdi_mixing_destroy(pmdi_mixing *a)
+{
+    if (!a) return PMDI_OK;
+    (void)hipSetDevice(a->device);
+    (void)hipDeviceSynchronize();
+    if (a->slab) (void)hipFree(a->slab);
+    delete a;
+    return PMDI_OK;
+}
+
+int pmdi_mixing_create(int32_t device, int32_t n_chains, int32_t K, int32_t N, int64_t n, int32_t maxlag, pmdi_mixing **out)
+{
+    if (!out) return fail(PMDI_E_ARG, "null argument");
+    *out = nullptr;
+    if (K < 1 || K > PMDI_KMAX_I) return fail(PMDI_E_ARG, "K=%d outside 1..%d", K, PMDI_KMAX_I);
+    if (N < 2 || N > 255) return fail(PMDI_E_ARG, "N=%d outside 2..255", N);
+    if (n < 1 || n > 65535) return fail(PMDI_E_ARG, "n=%lld outside 1..65535", (long long)n);
+    if (maxlag < 1 || maxlag > 1024) return fail(PMDI_E_ARG, "maxlag=%d outside 1..1024", maxlag);
+    if (n_chains < 1 || (long long)n_chains * K > 2147483647LL) return fail(PMDI_E_ARG, "n_chains=%d: need n_chains >= 1 and n_chains * K <= INT32_MAX", n_chains);
+    const int npairs = K * (K - 1) / 2, J = 2 * K + npairs, L = maxlag, np = (int)((n + 31) / 32 * 32);
+    const size_t CK = (size_t)n_chains * K, CJ = (size_t)n_chains * J;
+    const size_t counts[MIX_ARRAYS] = {CK * L, CK * L, CJ, CJ * (L + 1), CJ * L, CJ * L, CJ};
+    // 8-byte elements: the arrays, err; the ring of P, the ring of the scalars, A, nclust; then the label ring (256-byte aligned)
+    long double total = 1.0L + (long double)(L + 1) * (CK + CJ) + (long double)CK * L + (long double)CK;
+    for (size_t c : counts) total += (long double)c;
+    total = total * 8.0L + 256.0L + (long double)(L + 1) * (long double)CK * np;
+    if (total > 4.0e18L) return fail(PMDI_E_MEMORY, "the accumulator would need more than 4e18 bytes");
+    if (const int rc = open_device(device)) return rc;
+    pmdi_mixing *a = new (std::nothrow) pmdi_mixing();
+    if (!a) return fail(PMDI_E_MEMORY, "out of host memory");
+    a->device = device;
+    MixingArgs &m = a->ma;
+    m.C = n_chains; m.K = K; m.N = N; m.npairs = npairs; m.phi_stride = npairs > 0 ? npairs : 1; m.L = L; m.J = J; m.np = np; m.n = n;
+    a->state_bytes = 8;
+    for (int i = 0; i < MIX_ARRAYS; ++i) { a->count[i] = counts[i]; a->state_bytes += counts[i] * 8; }
+    const size_t words = a->state_bytes + ((size_t)(L + 1) * (CK + CJ) + CK * L + CK) * 8;
+    const size_t ring_at = (words + 255) & ~(size_t)255, bytes = ring_at + (size_t)(L + 1) * CK * np;
+    hipError_t e = hipMalloc((void **)&a->slab, bytes);
+    if (e != hipSuccess) { a->slab = nullptr; pmdi_mixing_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e)); }
+    if (hipMemset(a->slab, 0, ring_at) != hipSuccess) { pmdi_mixing_destroy(a); return fail(PMDI_E_DEVICE, "hipMemset failed"); }
+    char *p = a->slab;
+    for (int i = 0; i < MIX_ARRAYS; ++i) { a->at[i] = p; p += a->count[i] * 8; }
+    m.err = (int *)p; p += 8;
+    m.P_ring = (long long *)p; p += (size_t)(L + 1) * CK * 8;
+    m.y_ring = (double *)p; p += (size_t)(L + 1) * CJ * 8;
+    m.A = (long long *)p; p += CK * L * 8;
+    m.nclust = (double *)p;
+    m.ring = (unsigned char *)a->slab + ring_at;
+    m.rand_num = (long long *)a->at[MIX_RAND]; m.ari_sum = (double *)a->at[MIX_ARI]; m.sum_y = (double *)a->at[MIX_SUMY];
+    m.prod = (double *)a->at[MIX_PROD]; m.head = (double *)a->at[MIX_HEAD]; m.tail = (double *)a->at[MIX_TAIL];
+    m.first = (double *)a->at[MIX_FIRST];
+    *out = a;
+    return PMDI_OK;
+}
+
+int pmdi_mixing_reset(pmdi_mixing *a, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipMemsetAsync(a->slab, 0, a->state_bytes, (hipStream_t)stream));      // (the rings are read only as far back as T reaches)
+    a->T = 0;
+    return PMDI_OK;
+}
+
+int pmdi_mixing_add_arrays(pmdi_mixing *a, const int32_t *s, const double *M, const double *Phi, void *stream)
+{
+    if (!a || !s || !M || (!Phi && a->ma.npairs > 0)) return fail(PMDI_E_ARG, "null argument");
+    if (a->T >= 2147483647LL) return fail(PMDI_E_ARG, "%lld + 1 adds pass INT32_MAX", (long long)a->T);
+    HIP_TRY(hipSetDevice(a->device));
+    MixingArgs m = a->ma;
+    m.s = s; m.M = M; m.Phi = Phi;
+    hipError_t e = pmdi_launch_mixing_add(m, (long long)a->T + 1, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "mixing-add launch: %s", hipGetErrorString(e));
+    a->T += 1;
+    return PMDI_OK;
+}
+
+int pmdi_mixing_add_gibbs(pmdi_mixing *a, pmdi_gibbs *g, void *stream)
+{
+    if (!a || !g) return fail(PMDI_E_ARG, "null argument");
+    if (const int rc = mixing_accepts(a, g, 1)) return rc;
+    return pmdi_mixing_add_arrays(a, g->ga.s, g->ga.M, g->ga.Phi, stream);
+}
+
+int64_t pmdi_mixing_samples(const pmdi_mixing *a) { return a ? a->T : 0; }
+
+int pmdi_mixing_get(pmdi_mixing *a, int64_t *rand_num, double *ari_sum, double *sum_y, double *prod, double *head, double *tail,
+                    double *first, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    hipStream_t st = (hipStream_t)stream;
+    int err = 0;
+    void *const dst[MIX_ARRAYS] = {rand_num, ari_sum, sum_y, prod, head, tail, first};
+    for (int i = 0; i < MIX_ARRAYS; ++i)
+        if (dst[i]) HIP_TRY(hipMemcpyAsync(dst[i], a->at[i], a->count[i] * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&err, a->ma.err, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (err) return fail(PMDI_E_DATA, "a label outside 0..%d was added (pmdi_mixing_add_arrays); pmdi_mixing_reset clears the accumulator", a->ma.N - 1);
+    return PMDI_OK;
+}
+
+int pmdi_gibbs_run4(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
+                    pmdi_mixing *mix, void *stream)
 {
     if (!g || n_iter < 0) return fail(PMDI_E_ARG, "bad argument");
     if (burnin < 0 || thin < 1) return fail(PMDI_E_ARG, "burnin=%lld must be >= 0 and thin=%lld >= 1", (long long)burnin, (long long)thin);
@@ -455,6 +584,7 @@ int pmdi_gibbs_run3(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
     if (acc && (rc = accepts(acc, "accumulator", g, kept))) return rc;
     if (summ && (rc = summary_accepts(summ, g, kept))) return rc;
     if (fus && (rc = accepts(fus, "fusion accumulator", g, kept))) return rc;
+    if (mix && (rc = mixing_accepts(mix, g, kept))) return rc;
     for (int64_t t = 1; t <= n_iter; ++t) {
         if ((rc = pmdi_gibbs_step(g, PMDI_STEP_BEGIN, stream)) || (rc = pmdi_gibbs_step(g, PMDI_STEP_HYPERS, stream)) ||
             (rc = pmdi_gibbs_step(g, PMDI_STEP_SWEEP, stream)))
@@ -465,9 +595,16 @@ int pmdi_gibbs_run3(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
             if (acc && (rc = pmdi_psm_acc_add_gibbs(acc, g, stream))) return rc;
             if (summ && (rc = pmdi_summary_add_gibbs(summ, g, stream))) return rc;
             if (fus && (rc = pmdi_fusion_add_gibbs(fus, g, stream))) return rc;
+            if (mix && (rc = pmdi_mixing_add_gibbs(mix, g, stream))) return rc;
         }
     }
     return PMDI_OK;
+}
+
+int pmdi_gibbs_run3(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
+                    void *stream)
+{
+    return pmdi_gibbs_run4(g, n_iter, burnin, thin, acc, summ, fus, nullptr, stream);
 }
 
 int pmdi_gibbs_run2(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, void *stream)

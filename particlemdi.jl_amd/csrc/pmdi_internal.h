@@ -296,3 +296,27 @@ struct SummaryArgs {
 };
 // t = 1, 2, ...: the number of this add (the divisor of the Welford recurrences)
 hipError_t pmdi_launch_summary_add(const SummaryArgs &a, long long t, hipStream_t stream);
+
+// One add of the streaming mixing accumulator (pmdi_mixing.hip): the source arrays in the GibbsArgs layouts, the rings and
+// the accumulator's state.  J = 2 K + npairs scalars per chain: M_k, Phi_p, then the cluster counts.
+struct MixingArgs {
+    int C, K, N, npairs;        // chains, datasets, labels, K (K - 1) / 2 (0 when K = 1)
+    int phi_stride;             // max(1, npairs): chain stride of Phi
+    int L, J;                   // maxlag; scalars per chain
+    int np;                     // n rounded up to a multiple of 32: the row stride of the label ring
+    long long n;
+    const int *s;               // [C][K][n]  0-based labels
+    const double *M;            // [C][K]
+    const double *Phi;          // [C][phi_stride]
+    unsigned char *ring;        // [L + 1][C K][np]  label bytes, sample t in slot t mod (L + 1); 255 = no label
+    long long *P_ring;          // [L + 1][C K]      sum_a h_a (h_a - 1) / 2 of the slot's sample
+    double *y_ring;             // [L + 1][C][J]     the shifted scalars of the slot's sample
+    long long *A;               // [C K][L]   scratch: this add's sum_ab n_ab (n_ab - 1) / 2 per lag
+    double *nclust;             // [C K]      scratch: occupied labels per row of this add
+    int *err;                   // set to 1 by a label outside 0..N-1
+    long long *rand_num;        // [C K][L]
+    double *ari_sum;            // [C K][L]
+    double *sum_y, *prod, *head, *tail, *first;      // [C][J], [C][J][L + 1], [C][J][L], [C][J][L], [C][J]
+};
+// t = 1, 2, ...: the number of this add
+hipError_t pmdi_launch_mixing_add(const MixingArgs &a, long long t, hipStream_t stream);

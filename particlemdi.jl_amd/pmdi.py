@@ -128,17 +128,30 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     per group of datasets, how often each observation is clustered alike in all of them, and the posterior-similarity matrix
     of those fused observations -- is returned after the summary: (counts[, summary][, fusion][, draws]).  True = all pairs
     of datasets, with matrices; "probabilities" = all pairs, the per-observation counts only; an iterable of tuples of
-    0-based dataset indices = those groups, with matrices.  Needs K > 1."""
+    0-based dataset indices = those groups, with matrices.  Needs K > 1.
+    mixing (keyword only, default False): a fourth accumulator (mixing.MixingAccumulator) takes the same retained iterations and
+    its mixing.MixingSummary -- the clustering autocorrelation of every chain up to lag `mixing` (True = 20) in retained
+    iterations, and the autocorrelation time and effective sample size of M, Phi and the cluster counts -- is returned after
+    the summary and the fusion counts, before the draws: (counts[, summary][, fusion][, mixing][, draws]).  Needs
+    mixing <= retained iterations - 1."""
     from .fusion import FusionAccumulator, _group_masks
     fusion = more.pop("fusion", False)
+    mixing = more.pop("mixing", False)
     if more:
         raise TypeError(f"pmdi_pooled() got an unexpected keyword argument {next(iter(more))!r}")
     from .psm import PsmAccumulator, _DeviceInt32View, retained_iterations
     from .summary import SummaryAccumulator
+    from .mixing import MixingAccumulator
     K, n_obs, names = _check_arguments(dataFiles, dataTypes, N, particles, rho)
     _need(n_chains >= 1, "n_chains must be >= 1")
     _need(0 <= burnin < iter, "burnin must be >= 0 and smaller than iter (nothing would be retained)")
     _need(thin >= 1, "thin must be >= 1")
+    maxlag = 0
+    if mixing is not False and mixing is not None:
+        maxlag = 20 if mixing is True else int(mixing)
+        _need(1 <= maxlag <= 1024, "mixing must be True or a maximal lag in 1..1024")
+        _need(maxlag <= len(retained_iterations(iter, burnin, thin)) - 1,
+              "mixing: the maximal lag must be at most the number of retained iterations - 1")
     fusion_groups, fusion_matrix = None, True
     if fusion is not False and fusion is not None:
         _need(K > 1, "fusion needs two or more datasets")
@@ -160,13 +173,18 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
         summ = SummaryAccumulator(n_chains, K, N, n_obs, sumD=sweeper.sumD if featureSelect else 0,
                                   trace_cap=len(retained_iterations(iter, burnin, thin)), device=device)
     fus = FusionAccumulator(K, n_obs, n_labels=N, groups=fusion_groups, matrix=fusion_matrix, device=device) if fusion else None
+    mix = None
     try:
-        g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ, fusion=fus)
+        if maxlag:      # ((maxlag + 1) n_chains K n bytes: inside the try, so that a failed allocation still closes the handles)
+            mix = MixingAccumulator(n_chains, K, N, n_obs, maxlag=maxlag, device=device)
+        g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ, fusion=fus, mixing=mix)
         g.results()                      # synchronises; raises on a kernel-side error of any chain
         counts = acc.counts(names=names)   # (the view keeps the accumulator alive)
         out = (counts,) if summ is None else (counts, summ.summary(names=names, feature_D=sweeper.D))
         if fus is not None:
             out += (fus.counts(names=names),)      # (views again: they keep the accumulator alive)
+        if mix is not None:
+            out += (mix.result(names=names),)
         if final_allocations:
             import torch
             dev = torch.device("cuda", int(device))
@@ -176,5 +194,7 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     finally:
         if summ is not None:
             summ.close()
+        if mix is not None:
+            mix.close()
         g.close()
         sweeper.close()
