@@ -718,6 +718,72 @@ int pmdi_mixing_get(pmdi_mixing *a, int64_t *rand_num, double *ari_sum, double *
 int pmdi_gibbs_run4(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ,
                     pmdi_fusion *fus, pmdi_mixing *mix, void *stream);
 
+/* ---- streaming predictive accumulator: where do held-out rows fall, and do they fit at all? ----
+ * The fifth accumulator.  The other four describe the training observations; this one places m NEW rows (the same m for every
+ * dataset; new row j of dataset k has the D_k features of that dataset's kind) in every retained state while it is resident,
+ * and averages over the posterior without keeping a sample.  C = n_chains, K datasets, N labels, n training observations of
+ * the handle; one retained state of chain c is s[c][k][i] (0-based), Pi[c][k][.] and feature_flag[c][.], the arrays of
+ * pmdi_gibbs_device_view.  Per add:
+ *   1. For every (c, k, label l) the cluster of l is rebuilt: cluster_add! of its members in ascending observation index under
+ *      chain c's flags (features that are off are neither updated nor read) -- what feature selection does with all flags on
+ *      (src/pmdi.jl:360-364; with flags :201-206).  An empty label is the constructor's cluster: the prior predictive.  The
+ *      nlevels of a categorical feature stay the training column's.
+ *   2. lp[c][k][j][l] = calc_logprob(new row j, cluster l, flags), the feature sum in ascending feature order, expression by
+ *      expression pmdi_calc_logprob's.
+ *   3. The sweep's proposal (src/pmdi.jl:231-248) WITHOUT Phi, exactly as the sweep's own proposal ignores it:
+ *          mx = max_l lp_l;  f_l = exp(lp_l - mx) * Pi_l;  F = ((f_0 + f_1) + ...) in label order;  inc = log(F) + mx;
+ *          w_l = f_l / F;  q_l = (int32) floor(w_l * 2^20 + 0.5)                 (separate IEEE double operations, never fused)
+ *   4. sim         [K][m][n] Int64    += sum_c q[c][k][j][ s[c][k][i] ]: divided by T C 2^20, the posterior probability that
+ *                                      new row j co-clusters with training observation i.  Exact in any order.
+ *      new_cluster [K][m]    Int64    += sum_c sum over the labels l that are empty in sample c of q[c][k][j][l]: the weight on
+ *                                      opening a new cluster, a novelty score.  Exact in any order.
+ *      lpd_sum     [K][m]    Float64  = (((lpd_sum + inc_0) + inc_1) + ...) in chain order, one lane per (k, j): bit-defined given
+ *                                      the inc values; lpd_sum / (T C) is the mean log posterior-predictive density.
+ * Deliberately not computed: the JOINT allocation of a new observation across the datasets through Phi, an N^K object.  The
+ * per-dataset proposal above is what the sweep itself draws from.
+ * Stage buffers of the last add: q [C][K][m][N] Int32 (4 C K m N bytes: 250 MB for 3072 chains, K = 4, N = 20, m = 256), inc
+ * [C][K][m] Float64, the label sizes [C][K][N] Int32; lp [C][K][m][N] Float64 is kept whole only with keep_last -- otherwise the
+ * chains go through step 1-3 in batches whose lp fits 64 MB.  State: sim (8 K m n bytes), new_cluster, lpd_sum, an error flag.
+ * NegBinom: the accumulator owns a lgamma table built by the host call pmdi_create makes, long enough for the new rows' largest
+ * value; the entries it shares with the handle's are bit-equal.
+ * create: checked before the device is touched -- 1 <= m <= PMDI_PREDICT_MMAX; 4 C K m N and 8 K m n at most
+ *   PMDI_PREDICT_MAX_BYTES; new_rows[k] has the kind and D of the handle's dataset k and ld >= m (PMDI_E_ARG); categorical new
+ *   levels in 1..L (L = pmdi_categorical_L: the reference's counts[x, q] would be out of bounds otherwise), NegBinom values >= 0
+ *   (PMDI_E_DATA).  The rows are copied.  The accumulator is a child of h: pmdi_destroy(h) is refused (PMDI_E_STATE) while it lives.
+ * add_arrays: device arrays in the layouts of the resident state: s [C][K][n] 0-based int32, Pi [C][K][N], flags [C][sum D]
+ *   bytes or NULL = every feature on.  Pi is not checked: every row must be finite and >= 0 with a positive entry at a label whose
+ *   f_l does not underflow (the resident Pi is a normalised gamma draw: all positive); a row with F = 0 or not finite gives q = 0 for
+ *   every label (it adds nothing to sim and new_cluster) and inc = log(F) + mx as IEEE computes it.  A label outside 0..N-1 belongs to no cluster, adds nothing to sim and sets a device flag
+ *   that pmdi_predict_get reports as PMDI_E_DATA until pmdi_predict_reset.
+ * add_gibbs: the current s, Pi and (with feature selection) feature_flag of every chain of g, which must be a child of the same h.
+ * merge: sim, new_cluster, lpd_sum are DEVICE arrays of another accumulator of the same shape (integers added; lpd_sum = lpd_sum +
+ *   theirs), T += theirs.  The integers equal those of one accumulator that saw both halves; lpd_sum is bit-defined by that one
+ *   addition of the two partial sums, which is ANOTHER ORDER of the same terms than adding the second half's states one by one, so
+ *   it agrees with such an accumulator only to rounding.  T is bounded by INT32_MAX: an add or merge that would pass it is
+ *   PMDI_E_ARG and changes nothing.
+ * get: SYNCHRONISES `stream`, then copies to the host arrays that are not NULL.  counts: the device address of sim (zero-copy) and T.
+ * last: only with keep_last (else PMDI_E_STATE): synchronises the device and copies the last add's lp, inc, q to the host arrays
+ *   that are not NULL.  reset: everything zero, T = 0.  One device, not thread-safe, asynchronous on `stream` except create, destroy,
+ *   get and last; all calls on one accumulator go on ONE stream. */
+#define PMDI_PREDICT_MMAX 1048576
+#define PMDI_PREDICT_MAX_BYTES 34359738368LL /* 2^35 */
+typedef struct pmdi_predict pmdi_predict;
+int pmdi_predict_create(pmdi_handle *h, int64_t m, const pmdi_dataset *new_rows, int32_t keep_last, pmdi_predict **out);
+int pmdi_predict_destroy(pmdi_predict *a);
+int pmdi_predict_reset(pmdi_predict *a, void *stream);
+int64_t pmdi_predict_samples(const pmdi_predict *a);      /* T, the number of adds */
+int pmdi_predict_add_gibbs(pmdi_predict *a, pmdi_gibbs *g, void *stream);
+int pmdi_predict_add_arrays(pmdi_predict *a, const int32_t *s, const double *Pi, const uint8_t *flags, void *stream);
+int pmdi_predict_merge(pmdi_predict *a, const int64_t *sim, const int64_t *new_cluster, const double *lpd_sum, int64_t T, void *stream);
+int pmdi_predict_get(pmdi_predict *a, int64_t *sim, int64_t *new_cluster, double *lpd_sum, void *stream);
+int pmdi_predict_counts(pmdi_predict *a, const int64_t **sim_device, int64_t *T, void *stream);
+int pmdi_predict_last(pmdi_predict *a, double *lp, double *inc, int32_t *q);
+
+/* pmdi_gibbs_run4 with the fifth accumulator: after every retained local iteration acc, summ, fus, mix, then pred get their add;
+ * any may be NULL, and pmdi_gibbs_run4(g, ..., mix, stream) is pmdi_gibbs_run5(g, ..., mix, NULL, stream). */
+int pmdi_gibbs_run5(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ,
+                    pmdi_fusion *fus, pmdi_mixing *mix, pmdi_predict *pred, void *stream);
+
 /* Device pointers of the resident state (zero-copy consumers; layouts of pmdi_sweep_device). */
 typedef struct {
     double *M, *gamma, *gamma0, *Phi, *vZ, *Pi, *log1p_phi, *feature_prob, *logweight;

@@ -1,7 +1,9 @@
-// pmdi_acc.cpp -- the streaming accumulators of include/pmdi_hip.h (pmdi_psm_acc_*, pmdi_fusion_*, pmdi_summary_*, pmdi_mixing_*) and
-// their driver pmdi_gibbs_run / run2 / run3 / run4, which needs nothing of a pmdi_gibbs but the public pmdi_gibbs_step.
+// pmdi_acc.cpp -- the streaming accumulators of include/pmdi_hip.h (pmdi_psm_acc_*, pmdi_fusion_*, pmdi_summary_*, pmdi_mixing_*,
+// pmdi_predict_*) and their driver pmdi_gibbs_run / run2 / run3 / run4 / run5, which needs nothing of a pmdi_gibbs but the public
+// pmdi_gibbs_step.
 #include "pmdi_host.h"
 
+#include <cmath>
 #include <cstring>
 #include <new>
 
@@ -59,6 +61,20 @@ struct pmdi_mixing {
     size_t state_bytes = 0;              // what reset zeroes: every array and the error flag
     size_t count[MIX_ARRAYS] = {};       // elements of each array ...
     char *at[MIX_ARRAYS] = {};           // ... and where it starts in the slab (int64: rand_num; else double)
+    int64_t T = 0;                       // adds so far
+};
+
+// Streaming predictive accumulator (pmdi_predict_* entry points): a child of the handle whose datasets and tables it reads.  One
+// device slab holds what reset zeroes -- sim, new_cluster, lpd_sum (8-byte elements) and the error flag; the new rows, the longer
+// NegBinom tables and the per-add stage buffers are separate allocations
+struct pmdi_predict {
+    pmdi_handle *h = nullptr;
+    int device = 0;
+    PredictArgs pa{};                    // everything of an add but its sources
+    bool keep_last = false;
+    char *slab = nullptr;
+    size_t state_bytes = 0;
+    std::vector<void *> owned;           // device allocations freed in destroy
     int64_t T = 0;                       // adds so far
 };
 
@@ -139,6 +155,38 @@ int mixing_accepts(const pmdi_mixing *a, const pmdi_gibbs *g, int64_t n_adds)
                     m.n, c.n_chains, c.K, c.N, (long long)c.n);
     if (c.device != a->device) return fail(PMDI_E_ARG, "the chains live on device %d, the accumulator on device %d", c.device, a->device);
     if (n_adds > 2147483647LL - a->T) return fail(PMDI_E_ARG, "%lld + %lld adds pass INT32_MAX", (long long)a->T, (long long)n_adds);
+    return PMDI_OK;
+}
+
+// what pmdi_predict_add_gibbs checks before it touches anything (pmdi_gibbs_run5 asks once, before its first iteration)
+int predict_accepts(const pmdi_predict *a, const pmdi_gibbs *g, int64_t n_adds)
+{
+    if (g->h != a->h) return fail(PMDI_E_ARG, "the predictive accumulator was created from another handle than the chains");
+    if (n_adds > 2147483647LL - a->T) return fail(PMDI_E_ARG, "%lld + %lld adds pass INT32_MAX", (long long)a->T, (long long)n_adds);
+    return PMDI_OK;
+}
+
+// device memory of a predictive accumulator, freed with it
+template <class Tp>
+int predict_alloc(pmdi_predict *a, Tp **p, size_t count)
+{
+    size_t bytes = count * sizeof(Tp);
+    if (bytes == 0) bytes = 16;
+    void *q = nullptr;
+    hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
+    a->owned.push_back(q);
+    *p = (Tp *)q;
+    return PMDI_OK;
+}
+
+template <class Tp>
+int predict_upload(pmdi_predict *a, const std::vector<Tp> &v, const Tp **p)
+{
+    Tp *q = nullptr;
+    if (const int rc = predict_alloc(a, &q, v.size())) return rc;
+    if (!v.empty()) HIP_TRY(hipMemcpy(q, v.data(), v.size() * sizeof(Tp), hipMemcpyHostToDevice));
+    *p = q;
     return PMDI_OK;
 }
 
@@ -574,8 +622,193 @@ int pmdi_mixing_get(pmdi_mixing *a, int64_t *rand_num, double *ari_sum, double *
     return PMDI_OK;
 }
 
-int pmdi_gibbs_run4(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
-                    pmdi_mixing *mix, void *stream)
+int pmdi_predict_destroy(pmdi_predict *a)
+{
+    if (!a) return PMDI_OK;
+    (void)hipSetDevice(a->device);
+    (void)hipDeviceSynchronize();
+    if (a->slab) (void)hipFree(a->slab);
+    for (void *p : a->owned) (void)hipFree(p);
+    if (a->h && a->h->children > 0) a->h->children -= 1;      // (the handle outlives its children: pmdi_destroy refuses otherwise)
+    delete a;
+    return PMDI_OK;
+}
+
+int pmdi_predict_create(pmdi_handle *h, int64_t m, const pmdi_dataset *new_rows, int32_t keep_last, pmdi_predict **out)
+{
+    if (!h || !new_rows || !out) return fail(PMDI_E_ARG, "null argument");
+    *out = nullptr;
+    const int C = h->cfg.n_chains, K = h->cfg.K, N = h->cfg.N;
+    const long long n = h->cfg.n;
+    if (m < 1 || m > PMDI_PREDICT_MMAX) return fail(PMDI_E_ARG, "m=%lld outside 1..%d", (long long)m, PMDI_PREDICT_MMAX);
+    const long double q_bytes = 4.0L * C * K * (long double)m * N, sim_bytes = 8.0L * K * (long double)m * (long double)n;
+    if (q_bytes > (long double)PMDI_PREDICT_MAX_BYTES || sim_bytes > (long double)PMDI_PREDICT_MAX_BYTES)
+        return fail(PMDI_E_ARG, "m=%lld: the weights (4 C K m N = %.0Lf bytes) or sim (8 K m n = %.0Lf bytes) pass %lld bytes", (long long)m,
+                    q_bytes, sim_bytes, (long long)PMDI_PREDICT_MAX_BYTES);
+    // the new rows, row-major like the training data, checked before the device is touched
+    std::vector<double> xf[PMDI_KMAX_I];
+    std::vector<int> xi[PMDI_KMAX_I];
+    long long lg_len[PMDI_KMAX_I] = {};
+    for (int k = 0; k < K; ++k) {
+        const pmdi_dataset &src = new_rows[k];
+        const DsetDev &d = h->ds[k];
+        if (src.kind != d.kind || src.D != d.D)
+            return fail(PMDI_E_ARG, "new rows of dataset %d: kind=%d D=%d, the handle has kind=%d D=%d", k, src.kind, src.D, d.kind, d.D);
+        if (src.ld < m) return fail(PMDI_E_ARG, "new rows of dataset %d: ld=%lld < m=%lld", k, (long long)src.ld, (long long)m);
+        const int D = d.D;
+        if (d.kind == K_GAUSSIAN) {
+            if (!src.xf) return fail(PMDI_E_ARG, "new rows of dataset %d: xf is null", k);
+            xf[k].resize((size_t)m * D);
+            for (long long j = 0; j < m; ++j)
+                for (int q = 0; q < D; ++q) xf[k][(size_t)j * D + q] = src.xf[(size_t)q * src.ld + j];
+        } else {
+            if (!src.xi) return fail(PMDI_E_ARG, "new rows of dataset %d: xi is null", k);
+            xi[k].resize((size_t)m * D);
+            long long vmax = 0;
+            for (long long j = 0; j < m; ++j)
+                for (int q = 0; q < D; ++q) {
+                    const long long v = src.xi[(size_t)q * src.ld + j];
+                    if (d.kind == K_CATEGORICAL && (v < 1 || v > d.L))      // (the reference's counts[x, q] would be out of bounds)
+                        return fail(PMDI_E_DATA, "new rows of dataset %d: categorical level %lld outside 1..%d", k, v, d.L);
+                    if (d.kind == K_NEGBINOM && v < 0) return fail(PMDI_E_DATA, "new rows of dataset %d: negative count %lld", k, v);
+                    if (v > 0x3fffffff) return fail(PMDI_E_DATA, "new rows of dataset %d: value %lld too large", k, v);
+                    xi[k][(size_t)j * D + q] = (int)v;
+                    if (v > vmax) vmax = v;
+                }
+            if (d.kind == K_NEGBINOM) {      // the handle's table reaches n + (largest training value) + (largest column sum) + 8
+                lg_len[k] = d.lgtab_len + vmax;
+                if (lg_len[k] > (1LL << 28)) return fail(PMDI_E_DATA, "new rows of dataset %d: NegBinom lgamma table of %lld entries is too large", k, lg_len[k]);
+            }
+        }
+    }
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    pmdi_predict *a = new (std::nothrow) pmdi_predict();
+    if (!a) return fail(PMDI_E_MEMORY, "out of host memory");
+    a->h = h; a->device = h->cfg.device; a->keep_last = keep_last != 0;
+    h->children += 1;
+    PredictArgs &p = a->pa;
+    p.C = C; p.K = K; p.N = N; p.sumD = h->sumD; p.n = n; p.m = m;
+    // chains per batch of the weights kernels: their log predictives are 8 K m N bytes per chain, 64 MB per batch
+    const long long per_chain = 8LL * K * m * N;
+    long long Cb = (64LL << 20) / per_chain;
+    p.Cb = (int)(Cb < 1 ? 1 : Cb > C ? C : Cb);
+    p.lp_all = a->keep_last ? 1 : 0;
+    int rc = 0;
+    for (int k = 0; k < K && !rc; ++k) {
+        p.ds[k] = h->ds[k];
+        if (p.ds[k].kind == K_GAUSSIAN) rc = predict_upload(a, xf[k], &p.nxf[k]);
+        else rc = predict_upload(a, xi[k], &p.nxi[k]);
+        if (!rc && p.ds[k].kind == K_NEGBINOM) {
+            std::vector<double> lg((size_t)lg_len[k]);
+            for (long long i = 0; i < lg_len[k]; ++i) lg[i] = lgamma((double)i);      // the call pmdi_create makes: shared entries are bit-equal
+            rc = predict_upload(a, lg, &p.ds[k].lgtab);
+            p.ds[k].lgtab_len = lg_len[k];
+        }
+    }
+    const size_t CKm = (size_t)C * K * m, Km = (size_t)K * m;
+    if (!rc) rc = predict_alloc(a, &p.q, CKm * N);
+    if (!rc) rc = predict_alloc(a, &p.inc, CKm);
+    if (!rc) rc = predict_alloc(a, &p.qnew, CKm);
+    if (!rc) rc = predict_alloc(a, &p.cn, (size_t)C * K * N);
+    if (!rc) rc = predict_alloc(a, &p.lp, (size_t)(a->keep_last ? C : p.Cb) * K * m * N);
+    if (rc) { pmdi_predict_destroy(a); return rc; }
+    a->state_bytes = (Km * n + 2 * Km + 1) * 8;
+    hipError_t e = hipMalloc((void **)&a->slab, a->state_bytes);
+    if (e != hipSuccess) { a->slab = nullptr; pmdi_predict_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", a->state_bytes, hipGetErrorString(e)); }
+    if (hipMemset(a->slab, 0, a->state_bytes) != hipSuccess) { pmdi_predict_destroy(a); return fail(PMDI_E_DEVICE, "hipMemset failed"); }
+    p.sim = (long long *)a->slab;
+    p.new_cluster = p.sim + Km * n;
+    p.lpd_sum = (double *)(p.new_cluster + Km);
+    p.err = (int *)(p.lpd_sum + Km);
+    *out = a;
+    return PMDI_OK;
+}
+
+int pmdi_predict_reset(pmdi_predict *a, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipMemsetAsync(a->slab, 0, a->state_bytes, (hipStream_t)stream));
+    a->T = 0;
+    return PMDI_OK;
+}
+
+int pmdi_predict_add_arrays(pmdi_predict *a, const int32_t *s, const double *Pi, const uint8_t *flags, void *stream)
+{
+    if (!a || !s || !Pi) return fail(PMDI_E_ARG, "null argument");
+    if (a->T >= 2147483647LL) return fail(PMDI_E_ARG, "%lld + 1 adds pass INT32_MAX", (long long)a->T);
+    HIP_TRY(hipSetDevice(a->device));
+    PredictArgs p = a->pa;
+    p.s = s; p.Pi = Pi; p.flags = flags;
+    hipError_t e = pmdi_launch_predict_add(p, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "predict-add launch: %s", hipGetErrorString(e));
+    a->T += 1;
+    return PMDI_OK;
+}
+
+int pmdi_predict_add_gibbs(pmdi_predict *a, pmdi_gibbs *g, void *stream)
+{
+    if (!a || !g) return fail(PMDI_E_ARG, "null argument");
+    if (const int rc = predict_accepts(a, g, 1)) return rc;
+    return pmdi_predict_add_arrays(a, g->ga.s, g->ga.Pi, g->feature_select ? g->flags : nullptr, stream);
+}
+
+int pmdi_predict_merge(pmdi_predict *a, const int64_t *sim, const int64_t *new_cluster, const double *lpd_sum, int64_t T, void *stream)
+{
+    if (!a || !sim || !new_cluster || !lpd_sum) return fail(PMDI_E_ARG, "null argument");
+    if (T < 0 || T > 2147483647LL - a->T) return fail(PMDI_E_ARG, "%lld + %lld adds are negative or pass INT32_MAX", (long long)a->T, (long long)T);
+    HIP_TRY(hipSetDevice(a->device));
+    hipError_t e = pmdi_launch_predict_merge(a->pa, (const long long *)sim, (const long long *)new_cluster, lpd_sum, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "predict-merge launch: %s", hipGetErrorString(e));
+    a->T += T;
+    return PMDI_OK;
+}
+
+int64_t pmdi_predict_samples(const pmdi_predict *a) { return a ? a->T : 0; }
+
+int pmdi_predict_get(pmdi_predict *a, int64_t *sim, int64_t *new_cluster, double *lpd_sum, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    hipStream_t st = (hipStream_t)stream;
+    const PredictArgs &p = a->pa;
+    const size_t Km = (size_t)p.K * p.m;
+    int err = 0;
+    if (sim) HIP_TRY(hipMemcpyAsync(sim, p.sim, Km * p.n * 8, hipMemcpyDeviceToHost, st));
+    if (new_cluster) HIP_TRY(hipMemcpyAsync(new_cluster, p.new_cluster, Km * 8, hipMemcpyDeviceToHost, st));
+    if (lpd_sum) HIP_TRY(hipMemcpyAsync(lpd_sum, p.lpd_sum, Km * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&err, p.err, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (err) return fail(PMDI_E_DATA, "a label outside 0..%d was added (pmdi_predict_add_arrays); pmdi_predict_reset clears the accumulator", p.N - 1);
+    return PMDI_OK;
+}
+
+int pmdi_predict_counts(pmdi_predict *a, const int64_t **sim_device, int64_t *T, void *stream)
+{
+    (void)stream;      // (nothing to finish: sim is current after every add)
+    if (!a || !sim_device) return fail(PMDI_E_ARG, "null argument");
+    *sim_device = (const int64_t *)a->pa.sim;
+    if (T) *T = a->T;
+    return PMDI_OK;
+}
+
+int pmdi_predict_last(pmdi_predict *a, double *lp, double *inc, int32_t *q)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    if (!a->keep_last) return fail(PMDI_E_STATE, "pmdi_predict_last: the accumulator was created without keep_last");
+    if (a->T < 1) return fail(PMDI_E_STATE, "pmdi_predict_last: nothing was added yet");
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const PredictArgs &p = a->pa;
+    const size_t CKm = (size_t)p.C * p.K * p.m;
+    if (lp) HIP_TRY(hipMemcpy(lp, p.lp, CKm * p.N * 8, hipMemcpyDeviceToHost));
+    if (inc) HIP_TRY(hipMemcpy(inc, p.inc, CKm * 8, hipMemcpyDeviceToHost));
+    if (q) HIP_TRY(hipMemcpy(q, p.q, CKm * p.N * 4, hipMemcpyDeviceToHost));
+    return PMDI_OK;
+}
+
+int pmdi_gibbs_run5(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
+                    pmdi_mixing *mix, pmdi_predict *pred, void *stream)
 {
     if (!g || n_iter < 0) return fail(PMDI_E_ARG, "bad argument");
     if (burnin < 0 || thin < 1) return fail(PMDI_E_ARG, "burnin=%lld must be >= 0 and thin=%lld >= 1", (long long)burnin, (long long)thin);
@@ -585,6 +818,7 @@ int pmdi_gibbs_run4(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
     if (summ && (rc = summary_accepts(summ, g, kept))) return rc;
     if (fus && (rc = accepts(fus, "fusion accumulator", g, kept))) return rc;
     if (mix && (rc = mixing_accepts(mix, g, kept))) return rc;
+    if (pred && (rc = predict_accepts(pred, g, kept))) return rc;
     for (int64_t t = 1; t <= n_iter; ++t) {
         if ((rc = pmdi_gibbs_step(g, PMDI_STEP_BEGIN, stream)) || (rc = pmdi_gibbs_step(g, PMDI_STEP_HYPERS, stream)) ||
             (rc = pmdi_gibbs_step(g, PMDI_STEP_SWEEP, stream)))
@@ -596,9 +830,16 @@ int pmdi_gibbs_run4(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
             if (summ && (rc = pmdi_summary_add_gibbs(summ, g, stream))) return rc;
             if (fus && (rc = pmdi_fusion_add_gibbs(fus, g, stream))) return rc;
             if (mix && (rc = pmdi_mixing_add_gibbs(mix, g, stream))) return rc;
+            if (pred && (rc = pmdi_predict_add_gibbs(pred, g, stream))) return rc;
         }
     }
     return PMDI_OK;
+}
+
+int pmdi_gibbs_run4(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
+                    pmdi_mixing *mix, void *stream)
+{
+    return pmdi_gibbs_run5(g, n_iter, burnin, thin, acc, summ, fus, mix, nullptr, stream);
 }
 
 int pmdi_gibbs_run3(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,

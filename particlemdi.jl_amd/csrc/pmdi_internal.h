@@ -320,3 +320,31 @@ struct MixingArgs {
 };
 // t = 1, 2, ...: the number of this add
 hipError_t pmdi_launch_mixing_add(const MixingArgs &a, long long t, hipStream_t stream);
+
+// One add of the streaming predictive accumulator (pmdi_predict.hip): the source arrays in the GibbsArgs layouts, the handle's
+// datasets and tables, the new rows and the accumulator's state.
+struct PredictArgs {
+    int C, K, N, sumD;          // chains, datasets, labels, features of all datasets
+    int ltile;                  // features of a categorical dataset counted per pass: ltile * L level counts fit the LDS tile (set by the launcher)
+    long long n, m;             // training observations, new rows
+    DsetDev ds[PMDI_KMAX_I];    // the handle's datasets: training data and tables (lgtab: the accumulator's own, longer table)
+    const double *nxf[PMDI_KMAX_I];     // [m][D] new rows, Gaussian
+    const int *nxi[PMDI_KMAX_I];        // [m][D] new rows, Categorical / NegBinom
+    const int *s;               // [C][K][n]  0-based labels
+    const double *Pi;           // [C][K][N]
+    const unsigned char *flags; // [C][sumD], or null: every feature on
+    double *lp;                 // [Cb][K][m][N]  log predictives of one batch of chains (with keep_last: of all chains)
+    int lp_all;                 // 1: lp holds all C chains, a batch writes its own slice
+    int Cb;                     // chains per batch of the weights kernels
+    int *cn;                    // [C][K][N]  members of each label in this add's sample
+    int *q;                     // [C][K][m][N]  fixed-point proposal weights
+    double *inc;                // [C][K][m]  log(F) + mx
+    int *qnew;                  // [C][K][m]  the q of the sample's empty labels, summed
+    int *err;                   // set to 1 by a label outside 0..N-1
+    long long *sim;             // [K][m][n]
+    long long *new_cluster;     // [K][m]
+    double *lpd_sum;            // [K][m]
+};
+hipError_t pmdi_launch_predict_add(const PredictArgs &a, hipStream_t stream);
+// sim += sim_b, new_cluster += nc_b, lpd_sum = lpd_sum + lpd_b (device arrays)
+hipError_t pmdi_launch_predict_merge(const PredictArgs &a, const long long *sim_b, const long long *nc_b, const double *lpd_b, hipStream_t stream);

@@ -133,16 +133,25 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     its mixing.MixingSummary -- the clustering autocorrelation of every chain up to lag `mixing` (True = 20) in retained
     iterations, and the autocorrelation time and effective sample size of M, Phi and the cluster counts -- is returned after
     the summary and the fusion counts, before the draws: (counts[, summary][, fusion][, mixing][, draws]).  Needs
-    mixing <= retained iterations - 1."""
+    mixing <= retained iterations - 1.
+    predict (keyword only, default None): a list of K matrices of held-out rows, [Xnew_1, ..., Xnew_K] with the same number m of
+    rows and the columns of their datasets (checked before any device use: predict.check_new_rows).  A fifth accumulator
+    (predict.PredictiveAccumulator) takes the same retained iterations and its predict.PredictiveCounts -- how often each new row
+    co-clusters with each training observation, its weight on a new cluster and its mean log predictive density -- is returned
+    after the mixing summary and before the draws: (counts[, summary][, fusion][, mixing][, predict][, draws])."""
     from .fusion import FusionAccumulator, _group_masks
     fusion = more.pop("fusion", False)
     mixing = more.pop("mixing", False)
+    predict = more.pop("predict", None)
     if more:
         raise TypeError(f"pmdi_pooled() got an unexpected keyword argument {next(iter(more))!r}")
     from .psm import PsmAccumulator, _DeviceInt32View, retained_iterations
     from .summary import SummaryAccumulator
     from .mixing import MixingAccumulator
+    from .predict import PredictiveAccumulator, check_new_rows
     K, n_obs, names = _check_arguments(dataFiles, dataTypes, N, particles, rho)
+    if predict is not None:
+        check_new_rows(dataFiles, dataTypes, predict)
     _need(n_chains >= 1, "n_chains must be >= 1")
     _need(0 <= burnin < iter, "burnin must be >= 0 and smaller than iter (nothing would be retained)")
     _need(thin >= 1, "thin must be >= 1")
@@ -173,11 +182,13 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
         summ = SummaryAccumulator(n_chains, K, N, n_obs, sumD=sweeper.sumD if featureSelect else 0,
                                   trace_cap=len(retained_iterations(iter, burnin, thin)), device=device)
     fus = FusionAccumulator(K, n_obs, n_labels=N, groups=fusion_groups, matrix=fusion_matrix, device=device) if fusion else None
-    mix = None
+    mix = pred = None
     try:
         if maxlag:      # ((maxlag + 1) n_chains K n bytes: inside the try, so that a failed allocation still closes the handles)
             mix = MixingAccumulator(n_chains, K, N, n_obs, maxlag=maxlag, device=device)
-        g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ, fusion=fus, mixing=mix)
+        if predict is not None:
+            pred = PredictiveAccumulator(sweeper, predict)
+        g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ, fusion=fus, mixing=mix, predict=pred)
         g.results()                      # synchronises; raises on a kernel-side error of any chain
         counts = acc.counts(names=names)   # (the view keeps the accumulator alive)
         out = (counts,) if summ is None else (counts, summ.summary(names=names, feature_D=sweeper.D))
@@ -185,6 +196,8 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
             out += (fus.counts(names=names),)      # (views again: they keep the accumulator alive)
         if mix is not None:
             out += (mix.result(names=names),)
+        if pred is not None:
+            out += (pred.result(names=names),)
         if final_allocations:
             import torch
             dev = torch.device("cuda", int(device))
@@ -196,5 +209,7 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
             summ.close()
         if mix is not None:
             mix.close()
+        if pred is not None:
+            pred.close()      # (a child of the sweeper's handle: before it)
         g.close()
         sweeper.close()

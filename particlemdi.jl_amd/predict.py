@@ -1,0 +1,194 @@
+"""Held-out observations: where do new rows fall, and do they fit at all?
+
+The four other accumulators describe the observations a run was fitted to.  PredictiveAccumulator (include/pmdi_hip.h,
+pmdi_predict_*) places m NEW rows -- one row per dataset and new observation -- in every retained state of every chain
+while it is resident on the MI355X: each label's cluster is rebuilt from its members, every new row is scored against it
+(calc_logprob) and the sweep's own per-dataset proposal over the labels is accumulated as exact fixed-point integers.  It
+ends in a PredictiveCounts, a small host object: the probability that a new row co-clusters with each training
+observation, the weight on opening a new cluster (a novelty score), and the mean log posterior-predictive density.  The
+joint allocation of a new observation across the datasets through Phi (an N^K object) is deliberately not computed: the
+per-dataset proposal is what the sweep itself draws from.
+"""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import CATEGORICAL, GAUSSIAN, KIND_BY_NAME, NEGBINOM, _Accumulator, _check, _Dataset, _ptr, lib
+
+Q_ONE = 1 << 20      # the fixed point of the weights: q = floor(w * 2^20 + 0.5)
+
+
+def check_new_rows(dataFiles, dataTypes, new_rows):
+    """The argument checks of pmdi_predict_create, on the host and before any device use: one matrix of new rows per dataset,
+    the same number m >= 1 of rows in each, the D of its dataset; categorical levels in 1..L (L = the largest training level
+    of the dataset: the reference's counts[x, q] would be out of bounds otherwise), NegBinom counts >= 0.  Returns m."""
+    K = len(dataFiles)
+    if new_rows is None or len(new_rows) != K:
+        raise ValueError(f"predict: {0 if new_rows is None else len(new_rows)} matrices of new rows for {K} datasets")
+    rows = [np.asarray(x) for x in new_rows]
+    if any(x.ndim != 2 for x in rows):
+        raise ValueError("predict: every entry must be a matrix (m, D)")
+    m = int(rows[0].shape[0])
+    if m < 1 or any(x.shape[0] != m for x in rows):
+        raise ValueError("predict: the new rows need the same number m >= 1 of rows in every dataset")
+    for k, (x, train, kind) in enumerate(zip(rows, dataFiles, dataTypes)):
+        kind = KIND_BY_NAME.get(kind, kind)
+        if x.shape[1] != train.shape[1]:
+            raise ValueError(f"predict: new rows of dataset {k} have D={x.shape[1]}, the dataset D={train.shape[1]}")
+        if kind == CATEGORICAL:
+            L = int(np.max(train))
+            if int(x.min()) < 1 or int(x.max()) > L:
+                raise ValueError(f"predict: new rows of dataset {k} have a categorical level outside 1..{L}")
+        elif kind == NEGBINOM and int(x.min()) < 0:
+            raise ValueError(f"predict: new rows of dataset {k} have a negative count")
+    return m
+
+
+class PredictiveCounts:
+    """What T adds of C chains say about m new rows against n training observations in K datasets, as plain numpy in the layouts
+    of include/pmdi_hip.h:
+      sim         (K, m, n) int64    sum over adds and chains of the fixed-point weight of new row j on the label of observation i
+      new_cluster (K, m)    int64    the same weight on the labels that were empty in the sample
+      lpd_sum     (K, m)    float64  the sum over adds and chains of the log predictive increment
+    Built by PredictiveAccumulator.result(), or directly from arrays."""
+
+    def __init__(self, T, C, sim, new_cluster, lpd_sum, names=None):
+        self.T, self.C = int(T), int(C)
+        self.sim = np.asarray(sim, dtype=np.int64)
+        if self.sim.ndim != 3:
+            raise ValueError(f"sim must be (K, m, n), not {self.sim.shape}")
+        self.K, self.m, self.n = self.sim.shape
+        self.new_cluster_sum = np.asarray(new_cluster, dtype=np.int64).reshape(self.K, self.m)
+        self.lpd_sum = np.asarray(lpd_sum, dtype=np.float64).reshape(self.K, self.m)
+        self.names = list(names) if names is not None else [f"K{i}" for i in range(1, self.K + 1)]
+
+    def _samples(self):
+        if self.T < 1 or self.C < 1:
+            raise ValueError("PredictiveCounts: no samples behind the counts")
+        return self.T * self.C
+
+    def similarity(self, k=None):
+        """The posterior probability that new row j co-clusters with training observation i: float64 (K, m, n), or (m, n) for
+        dataset k.  The integers divided once by T C 2^20."""
+        s = self.sim if k is None else self.sim[k]
+        return s / float(self._samples() * Q_ONE)
+
+    def new_cluster(self):
+        """(K, m): the posterior weight on opening a new cluster for each new row -- the novelty score."""
+        return self.new_cluster_sum / float(self._samples() * Q_ONE)
+
+    def log_predictive(self):
+        """(K, m): the mean over the samples of the log predictive increment of each new row."""
+        return self.lpd_sum / float(self._samples())
+
+    def allocate(self, labels, k=None):
+        """New rows against a consensus clustering `labels` (n,) of the training observations: (assigned (m,), scores (m, G)).
+        The G groups are the distinct labels in ascending order; scores[j, g] is the mean similarity of new row j to the members
+        of group g (in dataset k, or averaged over the datasets when k is None); assigned[j] is the label of the group with the
+        largest score, the lowest group on a tie."""
+        labels = np.asarray(labels)
+        if labels.shape != (self.n,):
+            raise ValueError(f"allocate: labels must be ({self.n},), not {labels.shape}")
+        groups = np.unique(labels)
+        sim = self.similarity(k)
+        if k is None:
+            sim = sim.sum(axis=0) / self.K
+        scores = np.stack([sim[:, labels == g].sum(axis=1) / int((labels == g).sum()) for g in groups], axis=1)
+        return groups[np.argmax(scores, axis=1)], scores      # (argmax: the first of equal maxima)
+
+
+class PredictiveAccumulator(_Accumulator):
+    """The streaming predictive accumulator on one MI355X (include/pmdi_hip.h, pmdi_predict_*), a child of `sweeper`'s handle:
+    new_rows = one (m, D_k) matrix per dataset.  After every retained iteration it takes the device-resident allocations, Pi and
+    feature flags of every chain.  Device memory: 4 C K m N bytes of weights, 8 K m n of sim (and 8 C K m N of log predictives
+    with keep_last=True, which is what last() reads).  All calls go to the current torch stream of the device."""
+    _prefix = "pmdi_predict"
+    T = samples = property(_Accumulator._samples, doc="Adds so far = retained draws per chain.")
+
+    def __init__(self, sweeper, new_rows, keep_last=False):
+        if len(new_rows) != sweeper.K:
+            raise ValueError(f"PredictiveAccumulator: {len(new_rows)} matrices of new rows for {sweeper.K} datasets")
+        m = int(np.asarray(new_rows[0]).shape[0])
+        ds = (_Dataset * sweeper.K)()
+        keep = []
+        for k, (x, kind) in enumerate(zip(new_rows, sweeper.kinds)):
+            x = np.asarray(x)
+            if x.ndim != 2 or x.shape[0] != m:
+                raise ValueError("PredictiveAccumulator: every entry of new_rows must be a matrix with the same number of rows")
+            ds[k].kind, ds[k].D, ds[k].ld = kind, x.shape[1], m
+            if kind == GAUSSIAN:
+                xf = np.asfortranarray(x, dtype=np.float64)
+                keep.append(xf)
+                ds[k].xf = xf.ctypes.data_as(C.POINTER(C.c_double))
+            else:
+                xi = np.asfortranarray(x, dtype=np.int64)
+                keep.append(xi)
+                ds[k].xi = xi.ctypes.data_as(C.POINTER(C.c_int64))
+        h = C.c_void_p()
+        _check(lib().pmdi_predict_create(sweeper.h, m, ds, int(bool(keep_last)), C.byref(h)))      # (copies the rows)
+        self.h = h
+        self.sw = sweeper      # (the handle outlives its children)
+        self.C, self.K, self.N, self.n, self.m = sweeper.C, sweeper.K, sweeper.N, sweeper.n, m
+        self.sumD, self.device, self.keep_last = sweeper.sumD, sweeper.device, bool(keep_last)
+
+    def add_arrays(self, s, Pi, flags=None):
+        """CUDA tensors in the layouts of the resident state: s int32 (C, K, n) 0-based labels, Pi float64 (C, K, N), flags
+        uint8 (C, sumD) or None = every feature on."""
+        import torch
+        keep = [self._checked_tensor(s, torch.int32, (self.C, self.K, self.n), "add_arrays: s"),
+                self._checked_tensor(Pi, torch.float64, (self.C, self.K, self.N), "add_arrays: Pi")]
+        if flags is not None:
+            keep.append(self._checked_tensor(flags, torch.uint8, (self.C, self.sumD), "add_arrays: flags"))
+        ptrs = [C.c_void_p(t.data_ptr()) for t in keep] + ([None] if flags is None else [])
+        _check(lib().pmdi_predict_add_arrays(self.h, *ptrs, self._stream()))
+
+    def arrays(self):
+        """Host copies of sim, new_cluster, lpd_sum (synchronises the stream); raises PmdiError(PMDI_E_DATA) if a label outside
+        0..N-1 was added since the last reset."""
+        out = {"sim": np.zeros((self.K, self.m, self.n), dtype=np.int64), "new_cluster": np.zeros((self.K, self.m), dtype=np.int64),
+               "lpd_sum": np.zeros((self.K, self.m))}
+        _check(lib().pmdi_predict_get(self.h, *[_ptr(a) for a in out.values()], self._stream()))
+        return out
+
+    def sim_device(self):
+        """(zero-copy int64 CUDA tensor (K, m, n) of the accumulator's sim that keeps it alive, T)"""
+        import torch
+        ptr, T = C.c_void_p(), C.c_int64(0)
+        _check(lib().pmdi_predict_counts(self.h, C.byref(ptr), C.byref(T), self._stream()))
+        view = _DeviceInt64View(self, ptr.value, (self.K, self.m, self.n))
+        return torch.as_tensor(view, device=torch.device("cuda", self.device)), T.value
+
+    def last(self):
+        """The stage outputs of the last add (keep_last=True only; synchronises the device): {"lp": (C, K, m, N) float64 log
+        predictives, "inc": (C, K, m) float64, "q": (C, K, m, N) int32 fixed-point weights}."""
+        out = {"lp": np.zeros((self.C, self.K, self.m, self.N)), "inc": np.zeros((self.C, self.K, self.m)),
+               "q": np.zeros((self.C, self.K, self.m, self.N), dtype=np.int32)}
+        _check(lib().pmdi_predict_last(self.h, *[_ptr(a) for a in out.values()]))
+        return out
+
+    def merge(self, other):
+        """Adds what another accumulator of the same shape on the same device has seen (or a PredictiveCounts of it): the
+        integer sums are added, lpd_sum = lpd_sum + theirs, T += theirs."""
+        import torch
+        pc = other.result() if isinstance(other, PredictiveAccumulator) else other
+        if (pc.K, pc.m, pc.n, pc.C) != (self.K, self.m, self.n, self.C):
+            raise ValueError(f"merge needs the same K, m, n, C: {(self.K, self.m, self.n, self.C)} vs {(pc.K, pc.m, pc.n, pc.C)}")
+        dev = torch.device("cuda", self.device)
+        t = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (pc.sim, pc.new_cluster_sum, pc.lpd_sum)]
+        _check(lib().pmdi_predict_merge(self.h, *[C.c_void_p(x.data_ptr()) for x in t], int(pc.T), self._stream()))
+        torch.cuda.current_stream(dev).synchronize()      # the uploads may go once the kernel has read them
+
+    def result(self, names=None):
+        """The PredictiveCounts of everything added so far."""
+        a = self.arrays()
+        return PredictiveCounts(self.T, self.C, a["sim"], a["new_cluster"], a["lpd_sum"], names=names)
+
+
+class _DeviceInt64View:
+    """What torch.as_tensor needs to wrap device memory it does not own (no copy); the tensor keeps this object, and this
+    object the accumulator, alive."""
+
+    def __init__(self, owner, ptr, shape):
+        self._owner = owner
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<i8", "data": (int(ptr), False), "version": 2,
+                                         "strides": None}
