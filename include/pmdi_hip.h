@@ -739,8 +739,9 @@ int pmdi_gibbs_run4(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
  *                                      opening a new cluster, a novelty score.  Exact in any order.
  *      lpd_sum     [K][m]    Float64  = (((lpd_sum + inc_0) + inc_1) + ...) in chain order, one lane per (k, j): bit-defined given
  *                                      the inc values; lpd_sum / (T C) is the mean log posterior-predictive density.
- * Deliberately not computed: the JOINT allocation of a new observation across the datasets through Phi, an N^K object.  The
- * per-dataset proposal above is what the sweep itself draws from.
+ * The per-dataset proposal above is what the sweep itself draws from.  The JOINT allocation of a new observation across the
+ * datasets through Phi is computed too, without its N^K table, by an accumulator made with pmdi_predict_create_coupled and fed by
+ * pmdi_predict_add_arrays_coupled or pmdi_predict_add_gibbs: the block "coupled add" below.
  * Stage buffers of the last add: q [C][K][m][N] Int32 (4 C K m N bytes: 250 MB for 3072 chains, K = 4, N = 20, m = 256), inc
  * [C][K][m] Float64, the label sizes [C][K][N] Int32; lp [C][K][m][N] Float64 is kept whole only with keep_last -- otherwise the
  * chains go through step 1-3 in batches whose lp fits 64 MB.  State: sim (8 K m n bytes), new_cluster, lpd_sum, an error flag.
@@ -764,7 +765,45 @@ int pmdi_gibbs_run4(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
  * get: SYNCHRONISES `stream`, then copies to the host arrays that are not NULL.  counts: the device address of sim (zero-copy) and T.
  * last: only with keep_last (else PMDI_E_STATE): synchronises the device and copies the last add's lp, inc, q to the host arrays
  *   that are not NULL.  reset: everything zero, T = 0.  One device, not thread-safe, asynchronous on `stream` except create, destroy,
- *   get and last; all calls on one accumulator go on ONE stream. */
+ *   get and last; all calls on one accumulator go on ONE stream.
+ *
+ * Coupled add (pmdi_predict_create_coupled; K >= 2).  Everything above is computed as before, bit for bit, from the same q and
+ * inc.  In addition the posterior of the new observation's labels c = (c_1 .. c_K) in chain c's state,
+ *      p(c | state) ~ prod_k Pi_k[c_k] f_k(x_k | cluster c_k) * prod_{a<b} (1 + Phi_ab [c_a == c_b])
+ * (the weights of the sweep's Phi_upweight!), is summed exactly over its N^K combinations by the subset recursions that the
+ * hyper-parameter updates use (set partitions of the K datasets, O(K 2^K N + 3^K) per chain and new row).  W = the symmetric
+ * pair-weight matrix of chain c's Phi, pairs in Phi's own order (0,1), (0,2), ..., (K-2,K-1); full = all K datasets.  Per
+ * chain c and new row j, separate IEEE double operations in this order, never fused:
+ *   1. mx_k = max_l lp[c][k][j][l];  g[k][l] = exp(lp_l - mx_k) * Pi[c][k][l]             (step 3's f_l)
+ *   2. T[B] = sum_l prod_{k in B} g[k][l] for every non-empty set B of datasets: labels ascending, the product over k ascending
+ *   3. conn[B] = the sum over connected spanning edge sets of B of prod W_e, from positive terms only: with v the lowest member
+ *      of B, link[C] = prod_{u in C} (1 + W_vu) - 1 built member by member (r + w + r w), F[S] = sum over the subsets Cc of S
+ *      that hold S's lowest member of conn[Cc] * link[Cc] * F[S - Cc], conn[B] = F[B - v]; subsets in ascending mask order.
+ *      Zs[S] = sum over the subsets B of S that hold S's lowest member of conn[B] * T[B] * Zs[S - B], Zs[0] = 1;  Z = Zs[full].
+ *      conn depends on the chain only and is written once per add.
+ *   4. S[k][l] = sum over Cq inside full - k (ascending masks, from 0) of conn[Cq + k] * (prod_{u in Cq + k} g[u][l]) * Zs[full - k - Cq];
+ *      wj = S / Z;  qj[c][k][j][l] = (int32) floor(wj * 2^20 + 0.5): the joint marginal of label l in dataset k
+ *   5. for a < b: W2 = W with b contracted into a, W2[a][u] = W_au + W_bu + W_au * W_bu; conn2 = conn of W2 on full - b (per chain);
+ *      R_ab = (sum over Cq inside full - a - b of conn2[Cq + a] * T[Cq + a + b] * Zs[full - a - b - Cq]) * (1 + Phi_ab);
+ *      fq[c][pair][j] = (int32) floor(R_ab / Z * 2^20 + 0.5): the probability that datasets a and b give the row one label
+ *   6. Z0[c] = the same Z with g[k][l] = Pi[c][k][l], once per chain;
+ *      incj[c][j] = (log(Z) - log(Z0[c])) + ((mx_0 + mx_1) + ...): the log predictive density of the new observation's K rows jointly
+ *   7. Z = 0 or not finite: every qj and fq of that (c, j) is 0 (the rule F has above).  Phi is not checked, like Pi: finite and >= 0.
+ *      sim_joint         [K][m][n] Int64   += sum_c qj[c][k][j][ s[c][k][i] ]
+ *      new_cluster_joint [K][m]    Int64   += sum_c the qj of the sample's empty labels
+ *      fused_new         [G][m]    Int64   += sum_c fq,  G = K (K - 1) / 2
+ *      lpd_joint_sum     [m]       Float64  = ((lpd_joint_sum + incj_0) + incj_1) + ... in chain order, one lane per j
+ * With Phi = 0 the joint marginal is the per-dataset proposal and R_ab / Z = sum_l w_a[l] w_b[l].
+ * Added device memory: qj as large as q, sim_joint as large as sim, fq (4 C G m bytes), the subset tables (8 C (1 + G) 2^K bytes),
+ *   incj; with keep_last also g (as large as lp) and Z.  create_coupled: pmdi_predict_create's checks, K >= 2 (PMDI_E_ARG), and the
+ *   byte cap on 4 C G m and 8 C (1 + G) 2^K, all before the device is touched.
+ * add_arrays_coupled: add_arrays plus Phi, a device array [C][G].  On an accumulator made by pmdi_predict_create it is
+ *   PMDI_E_STATE, and so is pmdi_predict_add_arrays on a coupled one; pmdi_predict_add_gibbs serves both and takes a coupled
+ *   accumulator's Phi from g, so pmdi_gibbs_run5 drives either kind.
+ * get_coupled / merge_coupled / last_coupled: PMDI_E_STATE on an uncoupled accumulator.  get_coupled copies the four joint sums
+ *   (pmdi_predict_get the other three).  merge_coupled takes all seven DEVICE arrays of another coupled accumulator of the same
+ *   shape; lpd_joint_sum merges like lpd_sum.  last_coupled (keep_last only): g [C][K][m][N], Z [C][m], qj [C][K][m][N] Int32, fq
+ *   [C][G][m] Int32, incj [C][m], logZ0 [C], Z0 [C] of the last add.  reset zeroes the joint sums too. */
 #define PMDI_PREDICT_MMAX 1048576
 #define PMDI_PREDICT_MAX_BYTES 34359738368LL /* 2^35 */
 typedef struct pmdi_predict pmdi_predict;
@@ -778,6 +817,12 @@ int pmdi_predict_merge(pmdi_predict *a, const int64_t *sim, const int64_t *new_c
 int pmdi_predict_get(pmdi_predict *a, int64_t *sim, int64_t *new_cluster, double *lpd_sum, void *stream);
 int pmdi_predict_counts(pmdi_predict *a, const int64_t **sim_device, int64_t *T, void *stream);
 int pmdi_predict_last(pmdi_predict *a, double *lp, double *inc, int32_t *q);
+int pmdi_predict_create_coupled(pmdi_handle *h, int64_t m, const pmdi_dataset *new_rows, int32_t keep_last, pmdi_predict **out);
+int pmdi_predict_add_arrays_coupled(pmdi_predict *a, const int32_t *s, const double *Pi, const uint8_t *flags, const double *Phi, void *stream);
+int pmdi_predict_merge_coupled(pmdi_predict *a, const int64_t *sim, const int64_t *new_cluster, const double *lpd_sum, const int64_t *sim_joint,
+                               const int64_t *new_cluster_joint, const int64_t *fused_new, const double *lpd_joint_sum, int64_t T, void *stream);
+int pmdi_predict_get_coupled(pmdi_predict *a, int64_t *sim_joint, int64_t *new_cluster_joint, int64_t *fused_new, double *lpd_joint_sum, void *stream);
+int pmdi_predict_last_coupled(pmdi_predict *a, double *g, double *Z, int32_t *qj, int32_t *fq, double *incj, double *logZ0, double *Z0);
 
 /* pmdi_gibbs_run4 with the fifth accumulator: after every retained local iteration acc, summ, fus, mix, then pred get their add;
  * any may be NULL, and pmdi_gibbs_run4(g, ..., mix, stream) is pmdi_gibbs_run5(g, ..., mix, NULL, stream). */

@@ -76,6 +76,10 @@ struct pmdi_predict {
     size_t state_bytes = 0;
     std::vector<void *> owned;           // device allocations freed in destroy
     int64_t T = 0;                       // adds so far
+    bool coupled = false;                // created by pmdi_predict_create_coupled: every add also places the rows jointly through Phi
+    CoupledArgs ca{};                    // the coupled stage's tables, stage buffers and sums
+    char *slab2 = nullptr;               // what reset zeroes of a coupled accumulator: sim_joint, new_cluster_joint, fused_new, lpd_joint_sum
+    size_t state2_bytes = 0;
 };
 
 namespace {
@@ -628,19 +632,28 @@ int pmdi_predict_destroy(pmdi_predict *a)
     (void)hipSetDevice(a->device);
     (void)hipDeviceSynchronize();
     if (a->slab) (void)hipFree(a->slab);
+    if (a->slab2) (void)hipFree(a->slab2);
     for (void *p : a->owned) (void)hipFree(p);
     if (a->h && a->h->children > 0) a->h->children -= 1;      // (the handle outlives its children: pmdi_destroy refuses otherwise)
     delete a;
     return PMDI_OK;
 }
 
-int pmdi_predict_create(pmdi_handle *h, int64_t m, const pmdi_dataset *new_rows, int32_t keep_last, pmdi_predict **out)
+static int predict_create_any(pmdi_handle *h, int64_t m, const pmdi_dataset *new_rows, int32_t keep_last, bool coupled, pmdi_predict **out)
 {
     if (!h || !new_rows || !out) return fail(PMDI_E_ARG, "null argument");
     *out = nullptr;
     const int C = h->cfg.n_chains, K = h->cfg.K, N = h->cfg.N;
     const long long n = h->cfg.n;
+    if (coupled && K < 2) return fail(PMDI_E_ARG, "a coupled accumulator needs K >= 2 datasets, the handle has K=%d", K);
     if (m < 1 || m > PMDI_PREDICT_MMAX) return fail(PMDI_E_ARG, "m=%lld outside 1..%d", (long long)m, PMDI_PREDICT_MMAX);
+    const int G = K * (K - 1) / 2, nsub = 1 << K;
+    if (coupled) {      // the added arrays: qj and sim_joint are as large as q and sim (checked below)
+        const long double fq_bytes = 4.0L * C * G * (long double)m, tab_bytes = 8.0L * C * (1 + G) * nsub;
+        if (fq_bytes > (long double)PMDI_PREDICT_MAX_BYTES || tab_bytes > (long double)PMDI_PREDICT_MAX_BYTES)
+            return fail(PMDI_E_ARG, "m=%lld: the pair weights (4 C G m = %.0Lf bytes) or the subset tables (8 C (1 + G) 2^K = %.0Lf bytes) pass %lld bytes",
+                        (long long)m, fq_bytes, tab_bytes, (long long)PMDI_PREDICT_MAX_BYTES);
+    }
     const long double q_bytes = 4.0L * C * K * (long double)m * N, sim_bytes = 8.0L * K * (long double)m * (long double)n;
     if (q_bytes > (long double)PMDI_PREDICT_MAX_BYTES || sim_bytes > (long double)PMDI_PREDICT_MAX_BYTES)
         return fail(PMDI_E_ARG, "m=%lld: the weights (4 C K m N = %.0Lf bytes) or sim (8 K m n = %.0Lf bytes) pass %lld bytes", (long long)m,
@@ -720,8 +733,42 @@ int pmdi_predict_create(pmdi_handle *h, int64_t m, const pmdi_dataset *new_rows,
     p.new_cluster = p.sim + Km * n;
     p.lpd_sum = (double *)(p.new_cluster + Km);
     p.err = (int *)(p.lpd_sum + Km);
+    if (coupled) {
+        CoupledArgs &q = a->ca;
+        a->coupled = true;
+        q.npairs = G; q.nsub = nsub;
+        const size_t Cm = (size_t)C * m, Gm = (size_t)G * m;
+        rc = predict_alloc(a, &q.conn, (size_t)C * (1 + G) * nsub);
+        if (!rc) rc = predict_alloc(a, &q.Z0, (size_t)C);
+        if (!rc) rc = predict_alloc(a, &q.logZ0, (size_t)C);
+        if (!rc) rc = predict_alloc(a, &q.qj, CKm * N);
+        if (!rc) rc = predict_alloc(a, &q.qjnew, CKm);
+        if (!rc) rc = predict_alloc(a, &q.fq, (size_t)C * Gm);
+        if (!rc) rc = predict_alloc(a, &q.incj, Cm);
+        if (!rc && a->keep_last) rc = predict_alloc(a, &q.g, CKm * N);
+        if (!rc && a->keep_last) rc = predict_alloc(a, &q.Z, Cm);
+        if (rc) { pmdi_predict_destroy(a); return rc; }
+        a->state2_bytes = (Km * n + Km + Gm + (size_t)m) * 8;
+        e = hipMalloc((void **)&a->slab2, a->state2_bytes);
+        if (e != hipSuccess) { a->slab2 = nullptr; pmdi_predict_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", a->state2_bytes, hipGetErrorString(e)); }
+        if (hipMemset(a->slab2, 0, a->state2_bytes) != hipSuccess) { pmdi_predict_destroy(a); return fail(PMDI_E_DEVICE, "hipMemset failed"); }
+        q.sim_joint = (long long *)a->slab2;
+        q.new_cluster_joint = q.sim_joint + Km * n;
+        q.fused_new = q.new_cluster_joint + Km;
+        q.lpd_joint_sum = (double *)(q.fused_new + Gm);
+    }
     *out = a;
     return PMDI_OK;
+}
+
+int pmdi_predict_create(pmdi_handle *h, int64_t m, const pmdi_dataset *new_rows, int32_t keep_last, pmdi_predict **out)
+{
+    return predict_create_any(h, m, new_rows, keep_last, false, out);
+}
+
+int pmdi_predict_create_coupled(pmdi_handle *h, int64_t m, const pmdi_dataset *new_rows, int32_t keep_last, pmdi_predict **out)
+{
+    return predict_create_any(h, m, new_rows, keep_last, true, out);
 }
 
 int pmdi_predict_reset(pmdi_predict *a, void *stream)
@@ -729,28 +776,45 @@ int pmdi_predict_reset(pmdi_predict *a, void *stream)
     if (!a) return fail(PMDI_E_ARG, "null argument");
     HIP_TRY(hipSetDevice(a->device));
     HIP_TRY(hipMemsetAsync(a->slab, 0, a->state_bytes, (hipStream_t)stream));
+    if (a->slab2) HIP_TRY(hipMemsetAsync(a->slab2, 0, a->state2_bytes, (hipStream_t)stream));
     a->T = 0;
+    return PMDI_OK;
+}
+
+// one add of either kind; Phi: null for an uncoupled accumulator
+static int predict_add_any(pmdi_predict *a, const int32_t *s, const double *Pi, const uint8_t *flags, const double *Phi, void *stream)
+{
+    if (a->T >= 2147483647LL) return fail(PMDI_E_ARG, "%lld + 1 adds pass INT32_MAX", (long long)a->T);
+    HIP_TRY(hipSetDevice(a->device));
+    PredictArgs p = a->pa;
+    p.s = s; p.Pi = Pi; p.flags = flags;
+    CoupledArgs cp = a->ca;
+    cp.Phi = Phi;
+    hipError_t e = pmdi_launch_predict_add(p, (hipStream_t)stream, a->coupled ? &cp : nullptr);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "predict-add launch: %s", hipGetErrorString(e));
+    a->T += 1;
     return PMDI_OK;
 }
 
 int pmdi_predict_add_arrays(pmdi_predict *a, const int32_t *s, const double *Pi, const uint8_t *flags, void *stream)
 {
     if (!a || !s || !Pi) return fail(PMDI_E_ARG, "null argument");
-    if (a->T >= 2147483647LL) return fail(PMDI_E_ARG, "%lld + 1 adds pass INT32_MAX", (long long)a->T);
-    HIP_TRY(hipSetDevice(a->device));
-    PredictArgs p = a->pa;
-    p.s = s; p.Pi = Pi; p.flags = flags;
-    hipError_t e = pmdi_launch_predict_add(p, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "predict-add launch: %s", hipGetErrorString(e));
-    a->T += 1;
-    return PMDI_OK;
+    if (a->coupled) return fail(PMDI_E_STATE, "pmdi_predict_add_arrays: a coupled accumulator takes pmdi_predict_add_arrays_coupled (it needs Phi)");
+    return predict_add_any(a, s, Pi, flags, nullptr, stream);
+}
+
+int pmdi_predict_add_arrays_coupled(pmdi_predict *a, const int32_t *s, const double *Pi, const uint8_t *flags, const double *Phi, void *stream)
+{
+    if (!a || !s || !Pi || !Phi) return fail(PMDI_E_ARG, "null argument");
+    if (!a->coupled) return fail(PMDI_E_STATE, "pmdi_predict_add_arrays_coupled: the accumulator was created by pmdi_predict_create, not pmdi_predict_create_coupled");
+    return predict_add_any(a, s, Pi, flags, Phi, stream);
 }
 
 int pmdi_predict_add_gibbs(pmdi_predict *a, pmdi_gibbs *g, void *stream)
 {
     if (!a || !g) return fail(PMDI_E_ARG, "null argument");
     if (const int rc = predict_accepts(a, g, 1)) return rc;
-    return pmdi_predict_add_arrays(a, g->ga.s, g->ga.Pi, g->feature_select ? g->flags : nullptr, stream);
+    return predict_add_any(a, g->ga.s, g->ga.Pi, g->feature_select ? g->flags : nullptr, a->coupled ? g->ga.Phi : nullptr, stream);
 }
 
 int pmdi_predict_merge(pmdi_predict *a, const int64_t *sim, const int64_t *new_cluster, const double *lpd_sum, int64_t T, void *stream)
@@ -759,6 +823,23 @@ int pmdi_predict_merge(pmdi_predict *a, const int64_t *sim, const int64_t *new_c
     if (T < 0 || T > 2147483647LL - a->T) return fail(PMDI_E_ARG, "%lld + %lld adds are negative or pass INT32_MAX", (long long)a->T, (long long)T);
     HIP_TRY(hipSetDevice(a->device));
     hipError_t e = pmdi_launch_predict_merge(a->pa, (const long long *)sim, (const long long *)new_cluster, lpd_sum, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "predict-merge launch: %s", hipGetErrorString(e));
+    a->T += T;
+    return PMDI_OK;
+}
+
+int pmdi_predict_merge_coupled(pmdi_predict *a, const int64_t *sim, const int64_t *new_cluster, const double *lpd_sum, const int64_t *sim_joint,
+                               const int64_t *new_cluster_joint, const int64_t *fused_new, const double *lpd_joint_sum, int64_t T, void *stream)
+{
+    if (!a || !sim || !new_cluster || !lpd_sum || !sim_joint || !new_cluster_joint || !fused_new || !lpd_joint_sum) return fail(PMDI_E_ARG, "null argument");
+    if (!a->coupled) return fail(PMDI_E_STATE, "pmdi_predict_merge_coupled: the accumulator was created by pmdi_predict_create, not pmdi_predict_create_coupled");
+    if (T < 0 || T > 2147483647LL - a->T) return fail(PMDI_E_ARG, "%lld + %lld adds are negative or pass INT32_MAX", (long long)a->T, (long long)T);
+    HIP_TRY(hipSetDevice(a->device));
+    PredictArgs j = a->pa;
+    j.sim = a->ca.sim_joint; j.new_cluster = a->ca.new_cluster_joint; j.lpd_sum = nullptr;
+    hipError_t e = pmdi_launch_predict_merge(a->pa, (const long long *)sim, (const long long *)new_cluster, lpd_sum, (hipStream_t)stream);
+    if (e == hipSuccess) e = pmdi_launch_predict_merge(j, (const long long *)sim_joint, (const long long *)new_cluster_joint, nullptr, (hipStream_t)stream);
+    if (e == hipSuccess) e = pmdi_launch_predict_coupled_merge(a->pa, a->ca, (const long long *)fused_new, lpd_joint_sum, (hipStream_t)stream);
     if (e != hipSuccess) return fail(PMDI_E_DEVICE, "predict-merge launch: %s", hipGetErrorString(e));
     a->T += T;
     return PMDI_OK;
@@ -783,6 +864,26 @@ int pmdi_predict_get(pmdi_predict *a, int64_t *sim, int64_t *new_cluster, double
     return PMDI_OK;
 }
 
+int pmdi_predict_get_coupled(pmdi_predict *a, int64_t *sim_joint, int64_t *new_cluster_joint, int64_t *fused_new, double *lpd_joint_sum, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    if (!a->coupled) return fail(PMDI_E_STATE, "pmdi_predict_get_coupled: the accumulator was created by pmdi_predict_create, not pmdi_predict_create_coupled");
+    HIP_TRY(hipSetDevice(a->device));
+    hipStream_t st = (hipStream_t)stream;
+    const PredictArgs &p = a->pa;
+    const CoupledArgs &q = a->ca;
+    const size_t Km = (size_t)p.K * p.m, Gm = (size_t)q.npairs * p.m;
+    int err = 0;
+    if (sim_joint) HIP_TRY(hipMemcpyAsync(sim_joint, q.sim_joint, Km * p.n * 8, hipMemcpyDeviceToHost, st));
+    if (new_cluster_joint) HIP_TRY(hipMemcpyAsync(new_cluster_joint, q.new_cluster_joint, Km * 8, hipMemcpyDeviceToHost, st));
+    if (fused_new) HIP_TRY(hipMemcpyAsync(fused_new, q.fused_new, Gm * 8, hipMemcpyDeviceToHost, st));
+    if (lpd_joint_sum) HIP_TRY(hipMemcpyAsync(lpd_joint_sum, q.lpd_joint_sum, (size_t)p.m * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&err, p.err, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (err) return fail(PMDI_E_DATA, "a label outside 0..%d was added (pmdi_predict_add_arrays_coupled); pmdi_predict_reset clears the accumulator", p.N - 1);
+    return PMDI_OK;
+}
+
 int pmdi_predict_counts(pmdi_predict *a, const int64_t **sim_device, int64_t *T, void *stream)
 {
     (void)stream;      // (nothing to finish: sim is current after every add)
@@ -804,6 +905,27 @@ int pmdi_predict_last(pmdi_predict *a, double *lp, double *inc, int32_t *q)
     if (lp) HIP_TRY(hipMemcpy(lp, p.lp, CKm * p.N * 8, hipMemcpyDeviceToHost));
     if (inc) HIP_TRY(hipMemcpy(inc, p.inc, CKm * 8, hipMemcpyDeviceToHost));
     if (q) HIP_TRY(hipMemcpy(q, p.q, CKm * p.N * 4, hipMemcpyDeviceToHost));
+    return PMDI_OK;
+}
+
+int pmdi_predict_last_coupled(pmdi_predict *a, double *g, double *Z, int32_t *qj, int32_t *fq, double *incj, double *logZ0, double *Z0)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    if (!a->coupled) return fail(PMDI_E_STATE, "pmdi_predict_last_coupled: the accumulator was created by pmdi_predict_create, not pmdi_predict_create_coupled");
+    if (!a->keep_last) return fail(PMDI_E_STATE, "pmdi_predict_last_coupled: the accumulator was created without keep_last");
+    if (a->T < 1) return fail(PMDI_E_STATE, "pmdi_predict_last_coupled: nothing was added yet");
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const PredictArgs &p = a->pa;
+    const CoupledArgs &q = a->ca;
+    const size_t CKm = (size_t)p.C * p.K * p.m, Cm = (size_t)p.C * p.m;
+    if (g) HIP_TRY(hipMemcpy(g, q.g, CKm * p.N * 8, hipMemcpyDeviceToHost));
+    if (Z) HIP_TRY(hipMemcpy(Z, q.Z, Cm * 8, hipMemcpyDeviceToHost));
+    if (qj) HIP_TRY(hipMemcpy(qj, q.qj, CKm * p.N * 4, hipMemcpyDeviceToHost));
+    if (fq) HIP_TRY(hipMemcpy(fq, q.fq, (size_t)p.C * q.npairs * p.m * 4, hipMemcpyDeviceToHost));
+    if (incj) HIP_TRY(hipMemcpy(incj, q.incj, Cm * 8, hipMemcpyDeviceToHost));
+    if (logZ0) HIP_TRY(hipMemcpy(logZ0, q.logZ0, (size_t)p.C * 8, hipMemcpyDeviceToHost));
+    if (Z0) HIP_TRY(hipMemcpy(Z0, q.Z0, (size_t)p.C * 8, hipMemcpyDeviceToHost));
     return PMDI_OK;
 }
 

@@ -7,19 +7,8 @@
 // One workgroup per chain.  Compile with -ffp-contract=off.
 //
 // No N^K tables.  The reference materialises norm_temp[c] = prod_k g[c_k, k] * prod_{a<b} (1 + Phi_ab)^[c_a == c_b]
-// over all N^K label combinations c (src/pmdi.jl:69-92, update_hypers.jl:33,75,101) and sums slices of it.
-// Expanding the pair product over edge subsets E of the complete graph on the K datasets,
-//     prod_{a<b} (1 + Phi_ab [c_a == c_b]) = sum_E prod_{e in E} Phi_e * [c constant on every component of E],
-// and grouping the subsets by the partition of {1..K} their components induce, every such sum becomes a sum
-// over set partitions of products of
-//     T(B)    = sum_m prod_{j in B} g[m, j]                  (one label shared by the datasets of block B)
-//     conn(B) = sum over connected spanning edge sets of B of prod Phi_e,
-// i.e. Z = sum_{partitions pi} prod_{B in pi} conn(B) T(B), evaluated by a subset recursion (Zs below), and
-//     sum_{c : c_k = m} norm_temp[c]   = sum_{B containing k} conn(B) prod_{j in B} g[m, j] * Zs(complement of B)
-//     sum_{c : c_a = c_b} norm_temp[c] = (1 + Phi_ab) * the same sum with a and b contracted into one vertex.
-// conn(B) is built from positive terms only (no inclusion-exclusion differences): remove the lowest vertex v of
-// B; the rest falls into connected pieces C_i, each tied to v by a non-empty edge set:
-//     conn(B) = sum_{partitions {C_i} of B - v} prod_i conn(C_i) * (prod_{u in C_i} (1 + Phi_vu) - 1).
+// over all N^K label combinations c (src/pmdi.jl:69-92, update_hypers.jl:33,75,101) and sums slices of it; here every
+// such sum is a sum over set partitions of the K datasets, evaluated by the subset recursions of pmdi_subset.h.
 // Cost per chain and iteration: O(K 2^K N + 4^K) instead of O(K N^K).  The stale-Gamma_c behaviour of the
 // reference (norm_temp is always rebuilt from the INITIAL gamma) is kept: g starts from gamma0.
 //
@@ -32,6 +21,7 @@
 // oracle/pmdi_oracle_hypers.c, which restates the reference literally (N^K tables, recounts) and is what
 // tests/test_gpu_hypers.py compares these kernels with.
 #include "pmdi_device.h"
+#include "pmdi_subset.h"
 
 using namespace pmdi_dev;
 
@@ -74,63 +64,7 @@ __device__ __forceinline__ double gamma_logpdf(double k, double theta, double x)
     return -lgamma(k) - k * log(theta) + (k - 1.0) * log(x) - x / theta;
 }
 
-// ---- subset recursions (one lane; K <= 8: masks < 256) ------------------------------------------
-// conn[B] for every non-empty B inside `active`; W is the symmetric 8x8 pair-weight matrix.
-__device__ void conn_all(unsigned active, const double *W, double *conn, double *F, double *link)
-{
-    unsigned B = 0;
-    while ((B = (B - active) & active) != 0) {
-        const int v = __ffs((int)B) - 1;
-        const unsigned R = B & (B - 1);
-        if (R == 0) { conn[B] = 1.0; continue; }
-        link[0] = 0.0;
-        unsigned C = 0;
-        while ((C = (C - R) & R) != 0) {                       // prod_{u in C} (1 + W[v][u]) - 1, positive terms only
-            const int hb = 31 - __clz((int)C);
-            const double w = W[v * 8 + hb], r = link[C ^ (1u << hb)];
-            link[C] = r + w + r * w;
-        }
-        F[0] = 1.0;
-        unsigned S = 0;
-        while ((S = (S - R) & R) != 0) {
-            const unsigned l = S & (0u - S), Sp = S ^ l;
-            double acc = 0.0;
-            unsigned Cp = 0;
-            do {
-                const unsigned Cc = Cp | l;
-                acc += conn[Cc] * link[Cc] * F[Sp ^ Cp];
-                Cp = (Cp - Sp) & Sp;
-            } while (Cp != 0);
-            F[S] = acc;
-        }
-        conn[B] = F[R];
-    }
-}
-
-// Zs[S] = sum over set partitions of S of prod conn(B) T(B), for every S inside `active`
-__device__ void zs_all(unsigned active, const double *conn, const double *T, double *Zs)
-{
-    Zs[0] = 1.0;
-    unsigned S = 0;
-    while ((S = (S - active) & active) != 0) {
-        const unsigned l = S & (0u - S), Sp = S ^ l;
-        double acc = 0.0;
-        unsigned Cp = 0;
-        do {
-            const unsigned B = Cp | l;
-            acc += conn[B] * T[B] * Zs[Sp ^ Cp];
-            Cp = (Cp - Sp) & Sp;
-        } while (Cp != 0);
-        Zs[S] = acc;
-    }
-}
-
-__device__ __forceinline__ void fill_W(int K, const double *Phi, double *W)
-{
-    int i = 0;
-    for (int a = 0; a < K - 1; ++a)
-        for (int b = a + 1; b < K; ++b) { W[a * 8 + b] = Phi[i]; W[b * 8 + a] = Phi[i]; ++i; }
-}
+// (the subset recursions conn_all, zs_all, fill_W, compute_T, marginal_sum, contract_W, pair_sum: pmdi_subset.h)
 
 struct HCarve { size_t gam, g0, ge, T, conn, Zs, F, link, conn2, W, W2, alpha, Mv, Phi, red, cnt, nag, jbuf, misc, ord, total; };
 
@@ -148,20 +82,6 @@ __host__ __device__ inline void carve_hypers(const GibbsArgs &a, HCarve &c)
     c.cnt = take(KN * 4); c.nag = take(32 * 4); c.jbuf = take(256 * 4); c.misc = take(16 * 4);
     c.ord = take(a.order_lds ? (size_t)a.n * 4 : 0);
     c.total = o;
-}
-
-// T[B] = sum_m prod_{j in B} ge[j][m] for every non-empty B (lanes = subsets)
-__device__ __forceinline__ void compute_T(int K, int N, const double *ge, double *T, int tid, int nthreads)
-{
-    for (unsigned B = 1 + tid; B < (1u << K); B += nthreads) {
-        double acc = 0.0;
-        for (int m = 0; m < N; ++m) {
-            double p = 1.0;
-            for (int j = 0; j < K; ++j) if (B & (1u << j)) p = p * ge[j * N + m];
-            acc += p;
-        }
-        T[B] = acc;
-    }
 }
 
 // shuffle!(order_obs) (src/pmdi.jl:172): Fisher-Yates from the top, j = rand(1:i); the uniforms of 256
@@ -289,15 +209,7 @@ __global__ void __launch_bounds__(256) hypers_kernel(const GibbsArgs a, int do_s
         if (tid < N) {
             const int m = tid;
             // sum(view(norm_temp, pertinent_rows, :)) without the table: rows whose k-th digit is m
-            double S = 0.0;
-            unsigned Cq = 0;
-            do {
-                const unsigned B = Cq | (1u << k);
-                double p = 1.0;
-                for (int j = 0; j < K; ++j) if (B & (1u << j)) p = p * ge[j * N + m];
-                S += conn[B] * p * Zs[U ^ Cq];
-                Cq = (Cq - U) & U;
-            } while (Cq != 0);
+            const double S = marginal_sum(K, N, k, m, U, conn, ge, Zs);
             const double old_g = gam[k * N + m];
             const double beta_star = 1.0 + v * S / old_g;
             const double draw = gamma_draw(alpha[k * N + m], seed, iter, (unsigned)m, (unsigned)k, SITE_GAMMA);
@@ -335,20 +247,9 @@ __global__ void __launch_bounds__(256) hypers_kernel(const GibbsArgs a, int do_s
                     const unsigned rest = full ^ (1u << ka) ^ (1u << kb);
                     zs_all(rest, conn, T, Zs);
                     // contract a and b: the merged vertex keeps index a; weight to u = (1+W_au)(1+W_bu) - 1
-                    for (int e = 0; e < 64; ++e) W2[e] = W[e];
-                    for (int u = 0; u < K; ++u) {
-                        if (u == ka || u == kb) continue;
-                        const double wa = W[ka * 8 + u], wb = W[kb * 8 + u];
-                        const double w = wa + wb + wa * wb;
-                        W2[ka * 8 + u] = w; W2[u * 8 + ka] = w;
-                    }
+                    contract_W(K, ka, kb, W, W2);
                     conn_all(full ^ (1u << kb), W2, conn2, F, link);
-                    double S = 0.0;
-                    unsigned Cq = 0;
-                    do {
-                        S += conn2[Cq | (1u << ka)] * T[Cq | (1u << ka) | (1u << kb)] * Zs[rest ^ Cq];
-                        Cq = (Cq - rest) & rest;
-                    } while (Cq != 0);
+                    double S = pair_sum(ka, kb, rest, conn2, T, Zs);
                     S = S * (1.0 + cur);
                     red[256] = 5.0 + (v * S / (1.0 + cur));         // beta_star
                 }

@@ -345,6 +345,32 @@ struct PredictArgs {
     long long *new_cluster;     // [K][m]
     double *lpd_sum;            // [K][m]
 };
-hipError_t pmdi_launch_predict_add(const PredictArgs &a, hipStream_t stream);
-// sim += sim_b, new_cluster += nc_b, lpd_sum = lpd_sum + lpd_b (device arrays)
+// What a coupled add has beside PredictArgs (pmdi_predict_coupled.hip): the chains' Phi, the per-chain subset tables, the stage
+// buffers of the joint placement and the four joint sums.
+struct CoupledArgs {
+    int npairs, nsub;           // G = K (K - 1) / 2 pairs in Phi's order; 2^K subsets of the datasets
+    const double *Phi;          // [C][npairs]
+    double *conn;               // [C][1 + npairs][nsub]  conn of the chain's W, then conn2 of every pair (b contracted into a)
+    double *Z0, *logZ0;         // [C]  Z with g = Pi, and its log
+    double *g;                  // [C][K][m][N]  exp(lp - mx) * Pi, or null (kept with keep_last only)
+    double *Z;                  // [C][m], or null (kept with keep_last only)
+    int *qj;                    // [C][K][m][N]  fixed-point joint label marginals
+    int *qjnew;                 // [C][K][m]     the qj of the sample's empty labels, summed
+    int *fq;                    // [C][npairs][m]  fixed-point probability that a and b give the new row one label
+    double *incj;               // [C][m]  joint log predictive density
+    long long *sim_joint;       // [K][m][n]
+    long long *new_cluster_joint;       // [K][m]
+    long long *fused_new;       // [npairs][m]
+    double *lpd_joint_sum;      // [m]
+};
+// cp: null for an uncoupled add; else the per-chain tables are built first, every batch of chains goes through the coupling
+// kernel while its lp is live, and the joint sums follow the per-dataset ones
+hipError_t pmdi_launch_predict_add(const PredictArgs &a, hipStream_t stream, const CoupledArgs *cp = nullptr);
+// sim += sim_b, new_cluster += nc_b, lpd_sum = lpd_sum + lpd_b (device arrays; lpd_b null: lpd_sum is left alone)
 hipError_t pmdi_launch_predict_merge(const PredictArgs &a, const long long *sim_b, const long long *nc_b, const double *lpd_b, hipStream_t stream);
+// pmdi_predict_coupled.hip
+void pmdi_launch_predict_chain_tables(const PredictArgs &a, const CoupledArgs &cp, hipStream_t stream);
+void pmdi_launch_predict_couple(const PredictArgs &a, const CoupledArgs &cp, int c0, int chains, hipStream_t stream);
+void pmdi_launch_predict_coupled_reduce(const PredictArgs &a, const CoupledArgs &cp, hipStream_t stream);
+// fused_new += fused_b, lpd_joint_sum = lpd_joint_sum + lpdj_b (device arrays)
+hipError_t pmdi_launch_predict_coupled_merge(const PredictArgs &a, const CoupledArgs &cp, const long long *fused_b, const double *lpdj_b, hipStream_t stream);

@@ -7,6 +7,8 @@
 //                             Phi) as fixed-point weights q, its log increment, and the weight on the sample's empty labels
 //   predict_gather_kernel     sim[k][j][i] += sum over the chains of q[c][k][j][s[c][k][i]]: the hot path, exact integers
 //   predict_reduce_kernel     new_cluster and lpd_sum, one lane per (dataset, new row), chains in order
+// A coupled add (pmdi_predict_coupled.hip) runs its coupling kernel after every batch's normalise kernel and sends its joint weights
+// through the same gather and reduce kernels (launch_sums).
 // The arithmetic is pmdi_arith.h's and the tables are the host-built ones, so the integer kinds agree with a CPU evaluation bit for
 // bit.  Compile with -ffp-contract=off.
 #include "pmdi_device.h"
@@ -266,12 +268,18 @@ __global__ void __launch_bounds__(256) predict_gather_kernel(const PredictArgs a
 }
 
 // One lane per (dataset, new row), chains in order: the integer sum is exact, lpd_sum = ((lpd_sum + inc_0) + inc_1) + ...
+// (inc null: the joint sums of a coupled add, whose log density has one entry per new row and its own reduce)
 __global__ void __launch_bounds__(256) predict_reduce_kernel(const PredictArgs a)
 {
     const long long Km = (long long)a.K * a.m;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= Km) return;
     long long nc = a.new_cluster[idx];
+    if (!a.inc) {
+        for (int c = 0; c < a.C; ++c) nc += a.qnew[(size_t)c * Km + idx];
+        a.new_cluster[idx] = nc;
+        return;
+    }
     double lpd = a.lpd_sum[idx];
     for (int c = 0; c < a.C; ++c) {
         nc += a.qnew[(size_t)c * Km + idx];
@@ -289,13 +297,24 @@ __global__ void __launch_bounds__(256) predict_merge_kernel(const PredictArgs a,
     for (long long e = t0; e < total; e += step) a.sim[e] += sim_b[e];
     for (long long e = t0; e < Km; e += step) {
         a.new_cluster[e] += nc_b[e];
-        a.lpd_sum[e] = a.lpd_sum[e] + lpd_b[e];
+        if (lpd_b) a.lpd_sum[e] = a.lpd_sum[e] + lpd_b[e];
     }
+}
+
+// The sums of one add from its weights: sim += the gather of a.q over a.s, new_cluster += a.qnew and lpd_sum + a.inc in chain
+// order.  A coupled add calls it twice: with the per-dataset buffers, then with q, qnew, sim, new_cluster pointed at the joint ones.
+void launch_sums(const PredictArgs &b, hipStream_t stream)
+{
+    const size_t buf = (size_t)(b.N + 1) * PG_ROW * 4;
+    const int nbuf = 2 * buf <= 48 * 1024 ? 2 : 1;
+    dim3 grid((unsigned)((b.n + PG_OB - 1) / PG_OB), (unsigned)((b.m + PG_JS - 1) / PG_JS), (unsigned)b.K);
+    hipLaunchKernelGGL(predict_gather_kernel, grid, dim3(256), nbuf * buf, stream, b, nbuf);
+    hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)(((long long)b.K * b.m + 255) / 256)), dim3(256), 0, stream, b);
 }
 
 }  // namespace
 
-hipError_t pmdi_launch_predict_add(const PredictArgs &a, hipStream_t stream)
+hipError_t pmdi_launch_predict_add(const PredictArgs &a, hipStream_t stream, const CoupledArgs *cp)
 {
     PredictArgs b = a;
     int Lmax = 1;
@@ -311,17 +330,22 @@ hipError_t pmdi_launch_predict_add(const PredictArgs &a, hipStream_t stream)
             if (need > tile_bytes) tile_bytes = need;
         }
     const size_t lds_w = (size_t)PW_CHUNK * 4 + ((tile_bytes + 15) & ~(size_t)15);
+    if (cp) pmdi_launch_predict_chain_tables(b, *cp, stream);
     for (int c0 = 0; c0 < a.C; c0 += a.Cb) {
         const int chains = a.C - c0 < a.Cb ? a.C - c0 : a.Cb;
         hipLaunchKernelGGL(predict_weights_kernel, dim3((unsigned)chains * a.K * a.N), dim3(256), lds_w, stream, b, c0);
         const long long rows = (long long)chains * a.K * a.m;
         hipLaunchKernelGGL(predict_normalise_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, b, c0, chains);
+        if (cp) pmdi_launch_predict_couple(b, *cp, c0, chains, stream);      // (while the batch's lp is live)
     }
-    const size_t buf = (size_t)(a.N + 1) * PG_ROW * 4;
-    const int nbuf = 2 * buf <= 48 * 1024 ? 2 : 1;
-    dim3 grid((unsigned)((a.n + PG_OB - 1) / PG_OB), (unsigned)((a.m + PG_JS - 1) / PG_JS), (unsigned)a.K);
-    hipLaunchKernelGGL(predict_gather_kernel, grid, dim3(256), nbuf * buf, stream, b, nbuf);
-    hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)(((long long)a.K * a.m + 255) / 256)), dim3(256), 0, stream, b);
+    launch_sums(b, stream);
+    if (cp) {
+        PredictArgs j = b;
+        j.q = cp->qj; j.qnew = cp->qjnew; j.inc = nullptr;
+        j.sim = cp->sim_joint; j.new_cluster = cp->new_cluster_joint; j.lpd_sum = nullptr;
+        launch_sums(j, stream);
+        pmdi_launch_predict_coupled_reduce(b, *cp, stream);
+    }
     return hipGetLastError();
 }
 

@@ -138,11 +138,14 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     rows and the columns of their datasets (checked before any device use: predict.check_new_rows).  A fifth accumulator
     (predict.PredictiveAccumulator) takes the same retained iterations and its predict.PredictiveCounts -- how often each new row
     co-clusters with each training observation, its weight on a new cluster and its mean log predictive density -- is returned
-    after the mixing summary and before the draws: (counts[, summary][, fusion][, mixing][, predict][, draws])."""
+    after the mixing summary and before the draws: (counts[, summary][, fusion][, mixing][, predict][, draws]).
+    predict_coupled (keyword only, default False; needs predict and K > 1): the fifth accumulator also places every new observation
+    jointly across the datasets through Phi, and a predict.CoupledPredictiveCounts is returned in predict's place."""
     from .fusion import FusionAccumulator, _group_masks
     fusion = more.pop("fusion", False)
     mixing = more.pop("mixing", False)
     predict = more.pop("predict", None)
+    predict_coupled = bool(more.pop("predict_coupled", False))
     if more:
         raise TypeError(f"pmdi_pooled() got an unexpected keyword argument {next(iter(more))!r}")
     from .psm import PsmAccumulator, _DeviceInt32View, retained_iterations
@@ -150,6 +153,9 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     from .mixing import MixingAccumulator
     from .predict import PredictiveAccumulator, check_new_rows
     K, n_obs, names = _check_arguments(dataFiles, dataTypes, N, particles, rho)
+    if predict_coupled and predict is None:
+        raise ValueError("predict_coupled needs predict: the held-out rows to place")
+    _need(K > 1 or not predict_coupled, "predict_coupled needs two or more datasets")
     if predict is not None:
         check_new_rows(dataFiles, dataTypes, predict)
     _need(n_chains >= 1, "n_chains must be >= 1")
@@ -187,7 +193,7 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
         if maxlag:      # ((maxlag + 1) n_chains K n bytes: inside the try, so that a failed allocation still closes the handles)
             mix = MixingAccumulator(n_chains, K, N, n_obs, maxlag=maxlag, device=device)
         if predict is not None:
-            pred = PredictiveAccumulator(sweeper, predict)
+            pred = PredictiveAccumulator(sweeper, predict, coupled=predict_coupled)
         g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ, fusion=fus, mixing=mix, predict=pred)
         g.results()                      # synchronises; raises on a kernel-side error of any chain
         counts = acc.counts(names=names)   # (the view keeps the accumulator alive)

@@ -6,8 +6,10 @@ while it is resident on the MI355X: each label's cluster is rebuilt from its mem
 (calc_logprob) and the sweep's own per-dataset proposal over the labels is accumulated as exact fixed-point integers.  It
 ends in a PredictiveCounts, a small host object: the probability that a new row co-clusters with each training
 observation, the weight on opening a new cluster (a novelty score), and the mean log posterior-predictive density.  The
-joint allocation of a new observation across the datasets through Phi (an N^K object) is deliberately not computed: the
-per-dataset proposal is what the sweep itself draws from.
+per-dataset proposal is what the sweep itself draws from; with coupled=True the JOINT allocation of a new observation across
+the datasets through Phi is summed exactly as well (no N^K table: the subset recursions of the hyper-parameter updates), and
+the result is a CoupledPredictiveCounts: joint similarities and novelty scores, the probability that two datasets give a new
+row one label, and the joint log predictive density of its K rows.
 """
 import ctypes as C
 
@@ -81,31 +83,70 @@ class PredictiveCounts:
         """(K, m): the mean over the samples of the log predictive increment of each new row."""
         return self.lpd_sum / float(self._samples())
 
-    def allocate(self, labels, k=None):
+    def allocate(self, labels, k=None, joint=False):
         """New rows against a consensus clustering `labels` (n,) of the training observations: (assigned (m,), scores (m, G)).
         The G groups are the distinct labels in ascending order; scores[j, g] is the mean similarity of new row j to the members
         of group g (in dataset k, or averaged over the datasets when k is None); assigned[j] is the label of the group with the
-        largest score, the lowest group on a tie."""
+        largest score, the lowest group on a tie.  joint=True (CoupledPredictiveCounts only) scores with the Phi-coupled similarity."""
+        if joint and not hasattr(self, "joint_similarity"):
+            raise ValueError("allocate: joint=True needs the counts of a coupled accumulator")
         labels = np.asarray(labels)
         if labels.shape != (self.n,):
             raise ValueError(f"allocate: labels must be ({self.n},), not {labels.shape}")
         groups = np.unique(labels)
-        sim = self.similarity(k)
+        sim = self.joint_similarity(k) if joint else self.similarity(k)
         if k is None:
             sim = sim.sum(axis=0) / self.K
         scores = np.stack([sim[:, labels == g].sum(axis=1) / int((labels == g).sum()) for g in groups], axis=1)
         return groups[np.argmax(scores, axis=1)], scores      # (argmax: the first of equal maxima)
 
 
+class CoupledPredictiveCounts(PredictiveCounts):
+    """PredictiveCounts of a coupled accumulator: beside the per-dataset sums, those of the joint placement through Phi
+      sim_joint         (K, m, n) int64    the fixed-point joint marginal of new row j on the label of observation i
+      new_cluster_joint (K, m)    int64    the same on the labels that were empty in the sample
+      fused_new         (G, m)    int64    the fixed-point probability that datasets a < b give new row j one label; G = K (K - 1) / 2
+                                           pairs in Phi's order (0,1), (0,2), ..., (K-2,K-1)
+      lpd_joint_sum     (m,)      float64  the sum of the joint log predictive density of the new observation's K rows"""
+
+    def __init__(self, T, C, sim, new_cluster, lpd_sum, sim_joint, new_cluster_joint, fused_new, lpd_joint_sum, names=None):
+        super().__init__(T, C, sim, new_cluster, lpd_sum, names=names)
+        self.G = self.K * (self.K - 1) // 2
+        self.sim_joint = np.asarray(sim_joint, dtype=np.int64).reshape(self.K, self.m, self.n)
+        self.new_cluster_joint_sum = np.asarray(new_cluster_joint, dtype=np.int64).reshape(self.K, self.m)
+        self.fused_new = np.asarray(fused_new, dtype=np.int64).reshape(self.G, self.m)
+        self.lpd_joint_sum = np.asarray(lpd_joint_sum, dtype=np.float64).reshape(self.m)
+        self.pairs = [(a, b) for a in range(self.K - 1) for b in range(a + 1, self.K)]
+
+    def joint_similarity(self, k=None):
+        """similarity() under the joint posterior of the new observation's K labels: (K, m, n), or (m, n) for dataset k."""
+        s = self.sim_joint if k is None else self.sim_joint[k]
+        return s / float(self._samples() * Q_ONE)
+
+    def joint_new_cluster(self):
+        """(K, m): new_cluster() under the joint posterior."""
+        return self.new_cluster_joint_sum / float(self._samples() * Q_ONE)
+
+    def fused(self):
+        """(G, m): the posterior probability that datasets a and b give new row j one label (rows in the order of self.pairs)."""
+        return self.fused_new / float(self._samples() * Q_ONE)
+
+    def joint_log_predictive(self):
+        """(m,): the mean over the samples of the log predictive density of the new observation's K rows jointly."""
+        return self.lpd_joint_sum / float(self._samples())
+
+
 class PredictiveAccumulator(_Accumulator):
     """The streaming predictive accumulator on one MI355X (include/pmdi_hip.h, pmdi_predict_*), a child of `sweeper`'s handle:
     new_rows = one (m, D_k) matrix per dataset.  After every retained iteration it takes the device-resident allocations, Pi and
     feature flags of every chain.  Device memory: 4 C K m N bytes of weights, 8 K m n of sim (and 8 C K m N of log predictives
-    with keep_last=True, which is what last() reads).  All calls go to the current torch stream of the device."""
+    with keep_last=True, which is what last() reads).  coupled=True (K >= 2): every add also places the rows jointly through Phi
+    (pmdi_predict_create_coupled; add_arrays then needs Phi) at about twice the device memory; result() is a
+    CoupledPredictiveCounts.  All calls go to the current torch stream of the device."""
     _prefix = "pmdi_predict"
     T = samples = property(_Accumulator._samples, doc="Adds so far = retained draws per chain.")
 
-    def __init__(self, sweeper, new_rows, keep_last=False):
+    def __init__(self, sweeper, new_rows, keep_last=False, coupled=False):
         if len(new_rows) != sweeper.K:
             raise ValueError(f"PredictiveAccumulator: {len(new_rows)} matrices of new rows for {sweeper.K} datasets")
         m = int(np.asarray(new_rows[0]).shape[0])
@@ -125,22 +166,29 @@ class PredictiveAccumulator(_Accumulator):
                 keep.append(xi)
                 ds[k].xi = xi.ctypes.data_as(C.POINTER(C.c_int64))
         h = C.c_void_p()
-        _check(lib().pmdi_predict_create(sweeper.h, m, ds, int(bool(keep_last)), C.byref(h)))      # (copies the rows)
+        create = lib().pmdi_predict_create_coupled if coupled else lib().pmdi_predict_create
+        _check(create(sweeper.h, m, ds, int(bool(keep_last)), C.byref(h)))      # (copies the rows)
         self.h = h
         self.sw = sweeper      # (the handle outlives its children)
         self.C, self.K, self.N, self.n, self.m = sweeper.C, sweeper.K, sweeper.N, sweeper.n, m
         self.sumD, self.device, self.keep_last = sweeper.sumD, sweeper.device, bool(keep_last)
+        self.coupled, self.G = bool(coupled), sweeper.K * (sweeper.K - 1) // 2
 
-    def add_arrays(self, s, Pi, flags=None):
+    def add_arrays(self, s, Pi, flags=None, Phi=None):
         """CUDA tensors in the layouts of the resident state: s int32 (C, K, n) 0-based labels, Pi float64 (C, K, N), flags
-        uint8 (C, sumD) or None = every feature on."""
+        uint8 (C, sumD) or None = every feature on; Phi float64 (C, G) for a coupled accumulator (pmdi_predict_add_arrays_coupled),
+        None for an uncoupled one.  The wrong one of the two is PmdiError(PMDI_E_STATE)."""
         import torch
         keep = [self._checked_tensor(s, torch.int32, (self.C, self.K, self.n), "add_arrays: s"),
                 self._checked_tensor(Pi, torch.float64, (self.C, self.K, self.N), "add_arrays: Pi")]
         if flags is not None:
             keep.append(self._checked_tensor(flags, torch.uint8, (self.C, self.sumD), "add_arrays: flags"))
         ptrs = [C.c_void_p(t.data_ptr()) for t in keep] + ([None] if flags is None else [])
-        _check(lib().pmdi_predict_add_arrays(self.h, *ptrs, self._stream()))
+        if Phi is None:
+            _check(lib().pmdi_predict_add_arrays(self.h, *ptrs, self._stream()))
+            return
+        keep.append(self._checked_tensor(Phi, torch.float64, (self.C, self.G), "add_arrays: Phi"))
+        _check(lib().pmdi_predict_add_arrays_coupled(self.h, *ptrs, C.c_void_p(keep[-1].data_ptr()), self._stream()))
 
     def arrays(self):
         """Host copies of sim, new_cluster, lpd_sum (synchronises the stream); raises PmdiError(PMDI_E_DATA) if a label outside
@@ -148,6 +196,11 @@ class PredictiveAccumulator(_Accumulator):
         out = {"sim": np.zeros((self.K, self.m, self.n), dtype=np.int64), "new_cluster": np.zeros((self.K, self.m), dtype=np.int64),
                "lpd_sum": np.zeros((self.K, self.m))}
         _check(lib().pmdi_predict_get(self.h, *[_ptr(a) for a in out.values()], self._stream()))
+        if self.coupled:
+            more = {"sim_joint": np.zeros((self.K, self.m, self.n), dtype=np.int64), "new_cluster_joint": np.zeros((self.K, self.m), dtype=np.int64),
+                    "fused_new": np.zeros((self.G, self.m), dtype=np.int64), "lpd_joint_sum": np.zeros(self.m)}
+            _check(lib().pmdi_predict_get_coupled(self.h, *[_ptr(a) for a in more.values()], self._stream()))
+            out.update(more)
         return out
 
     def sim_device(self):
@@ -166,21 +219,39 @@ class PredictiveAccumulator(_Accumulator):
         _check(lib().pmdi_predict_last(self.h, *[_ptr(a) for a in out.values()]))
         return out
 
+    def last_coupled(self):
+        """The coupled stage's outputs of the last add (coupled=True and keep_last=True only; synchronises the device): {"g": (C, K, m, N)
+        float64 exp(lp - mx) * Pi, "Z": (C, m), "qj": (C, K, m, N) int32, "fq": (C, G, m) int32, "incj": (C, m), "logZ0": (C,), "Z0": (C,)}."""
+        out = {"g": np.zeros((self.C, self.K, self.m, self.N)), "Z": np.zeros((self.C, self.m)),
+               "qj": np.zeros((self.C, self.K, self.m, self.N), dtype=np.int32), "fq": np.zeros((self.C, self.G, self.m), dtype=np.int32),
+               "incj": np.zeros((self.C, self.m)), "logZ0": np.zeros(self.C), "Z0": np.zeros(self.C)}
+        _check(lib().pmdi_predict_last_coupled(self.h, *[_ptr(a) for a in out.values()]))
+        return out
+
     def merge(self, other):
         """Adds what another accumulator of the same shape on the same device has seen (or a PredictiveCounts of it): the
-        integer sums are added, lpd_sum = lpd_sum + theirs, T += theirs."""
+        integer sums are added, lpd_sum = lpd_sum + theirs, T += theirs.  A coupled accumulator takes coupled counts (all seven arrays)."""
         import torch
         pc = other.result() if isinstance(other, PredictiveAccumulator) else other
         if (pc.K, pc.m, pc.n, pc.C) != (self.K, self.m, self.n, self.C):
             raise ValueError(f"merge needs the same K, m, n, C: {(self.K, self.m, self.n, self.C)} vs {(pc.K, pc.m, pc.n, pc.C)}")
         dev = torch.device("cuda", self.device)
-        t = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (pc.sim, pc.new_cluster_sum, pc.lpd_sum)]
-        _check(lib().pmdi_predict_merge(self.h, *[C.c_void_p(x.data_ptr()) for x in t], int(pc.T), self._stream()))
+        parts = [pc.sim, pc.new_cluster_sum, pc.lpd_sum]
+        if self.coupled:
+            if not isinstance(pc, CoupledPredictiveCounts):
+                raise ValueError("merge: a coupled accumulator takes the counts of a coupled one")
+            parts += [pc.sim_joint, pc.new_cluster_joint_sum, pc.fused_new, pc.lpd_joint_sum]
+        t = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in parts]
+        merge = lib().pmdi_predict_merge_coupled if self.coupled else lib().pmdi_predict_merge
+        _check(merge(self.h, *[C.c_void_p(x.data_ptr()) for x in t], int(pc.T), self._stream()))
         torch.cuda.current_stream(dev).synchronize()      # the uploads may go once the kernel has read them
 
     def result(self, names=None):
         """The PredictiveCounts of everything added so far."""
         a = self.arrays()
+        if self.coupled:
+            return CoupledPredictiveCounts(self.T, self.C, a["sim"], a["new_cluster"], a["lpd_sum"], a["sim_joint"], a["new_cluster_joint"],
+                                           a["fused_new"], a["lpd_joint_sum"], names=names)
         return PredictiveCounts(self.T, self.C, a["sim"], a["new_cluster"], a["lpd_sum"], names=names)
 
 

@@ -4,7 +4,9 @@ PredictiveAccumulator.add_arrays by events, the median of `--reps` calls (defaul
 layouts of the resident state: add_gibbs forwards the resident pointers to the same launches.  The handle is created with the
 smallest cluster pool and four particles: the accumulator reads its data and tables, never its pools.  Where the weights (250 MB), sim and the
 sources do not fit the free memory the script falls back to 1 024 chains and says so.  Prints one JSON object; GPU only.
-`--add-only` runs three adds alone (for a rocprofv3 --kernel-trace --stats run, which gives the split between the kernels)."""
+`--add-only` runs three adds alone (for a rocprofv3 --kernel-trace --stats run, which gives the split between the kernels).
+`--coupled` times a coupled accumulator instead (PredictiveAccumulator(coupled=True), Phi drawn Gamma(1, 1)): the same adds with the
+Phi-coupled placement on top, and twice the weights and sums in memory.  Without it the output is what it was."""
 import json
 import os
 import sys
@@ -32,18 +34,21 @@ def timed(fn, reps):
     return {"ms_median": float(np.median(out)), "ms_min": float(min(out)), "ms_max": float(max(out)), "reps": reps}
 
 
-def case(C_, K, n, D, N, m, labels, reps, add_only):
+def case(C_, K, n, D, N, m, labels, reps, add_only, coupled=False):
     rng = np.random.default_rng(1)
     z = rng.integers(0, labels, n)
     train = [rng.normal(size=(n, D)) + 2.0 * z[:, None] for _ in range(K)]
     new = [rng.normal(size=(m, D)) + 2.0 * rng.integers(0, labels, m)[:, None] for _ in range(K)]
     sw = pkg.Sweeper(train, ["gaussian"] * K, N, 4, n_chains=C_, seed=1, pool_cap=N + 2)
-    acc = pkg.PredictiveAccumulator(sw, new)
+    acc = pkg.PredictiveAccumulator(sw, new, coupled=True) if coupled else pkg.PredictiveAccumulator(sw, new)
     gen = torch.Generator(device="cuda").manual_seed(1)
     s = torch.randint(0, labels, (C_, K, n), dtype=torch.int32, device="cuda", generator=gen)
     Pi = torch.rand((C_, K, N), dtype=torch.float64, device="cuda", generator=gen) + 0.05
     Pi /= Pi.sum(dim=2, keepdim=True)
     add = lambda: acc.add_arrays(s, Pi, None)
+    if coupled:
+        Phi = torch.empty((C_, K * (K - 1) // 2), dtype=torch.float64, device="cuda").exponential_(1.0, generator=gen)
+        add = lambda: acc.add_arrays(s, Pi, None, Phi=Phi)
     for _ in range(3):
         add()
     torch.cuda.synchronize()
@@ -54,6 +59,10 @@ def case(C_, K, n, D, N, m, labels, reps, add_only):
         res["add"]["gather_Gadds_per_s_if_all_gather"] = res["gather_adds"] / (res["add"]["ms_median"] * 1e-3) / 1e9
     pc = acc.result()
     assert pc.T == acc.T and np.isfinite(pc.log_predictive()).all() and pc.similarity(0)[0].sum() > 0
+    if coupled:
+        res["coupled"] = True
+        res["qj_bytes"], res["sim_joint_bytes"] = res["q_bytes"], res["sim_bytes"]
+        assert np.isfinite(pc.joint_log_predictive()).all() and pc.joint_similarity(0)[0].sum() > 0
     acc.close()
     sw.close()
     return res
@@ -61,10 +70,11 @@ def case(C_, K, n, D, N, m, labels, reps, add_only):
 
 free, _ = torch.cuda.mem_get_info()
 C_head, K, n, D, N, m = 3072, 4, 10000, 50, 20, 256
-need = 4 * C_head * K * m * N + 8 * K * m * n + C_head * K * n * 4 + (64 << 20) + (2 << 30)
+coupled = "--coupled" in sys.argv
+need = (2 if coupled else 1) * (4 * C_head * K * m * N + 8 * K * m * n) + C_head * K * n * 4 + (64 << 20) + (2 << 30)
 out = {"free_bytes": int(free), "fallback_to_1024_chains": bool(need > free)}
 if need > free:
     C_head = 1024
 reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 12
-out["headline"] = case(C_head, K, n, D, N, m, 4, reps, "--add-only" in sys.argv)
+out["headline"] = case(C_head, K, n, D, N, m, 4, reps, "--add-only" in sys.argv, coupled)
 print(json.dumps(out, indent=1))
