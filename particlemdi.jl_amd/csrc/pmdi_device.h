@@ -237,7 +237,7 @@ __device__ __forceinline__ void block_sum2(double &a, double &b, double *scr)
 }
 
 // Lanes of a wave holding equal `key` (among `valid` lanes) elect the lowest
-// lane as group leader; returns true on the leader with the group's size.
+// lane as group leader; returns true on the leader with the group's size (count is 0 on every other lane).
 __device__ __forceinline__ bool wave_group(int key, bool valid, int &count)
 {
     const int lane = threadIdx.x & 63;
@@ -295,7 +295,8 @@ __device__ __forceinline__ int wave_group_lead(int key, bool valid, int &count)
 }
 
 // number of set bits strictly below bit p of a bitmap (32-bit words, an even number of them
-// allocated, 8-byte aligned); read as 64-bit words, four loads in flight
+// allocated, 8-byte aligned); read as 64-bit words, four loads in flight.  The 64-bit word p >> 6 is always read, masked to
+// nothing when p is a multiple of 64: a caller that asks for p = nbits keeps (nbits >> 6) + 1 words (pmdi_sweep_carve.h does)
 __device__ __forceinline__ int popc_below(const unsigned *bm, int p)
 {
     const unsigned long long *b64 = (const unsigned long long *)bm;

@@ -17,7 +17,8 @@ __device__ __forceinline__ double readlane_f64(double v, int l)
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
 // All-reduce of a double: xor-1 and xor-2 inside quads, half-row and row mirrors give every lane its 16-lane row total; the four row
-// totals are read with v_readlane and combined as (r0 op r1) op (r2 op r3).
+// totals are read with v_readlane and combined as (r0 op r1) op (r2 op r3).  Every lane returns the same bits.  (max / min: when the
+// extremum is a zero and the wave holds zeros of both signs, which of the two comes back is not specified.)
 __device__ __forceinline__ double wave_sum_f64(double v)
 {
     v += dpp_f64<0xB1>(v);      // quad_perm [1,0,3,2]

@@ -2,6 +2,8 @@
 // wave primitives of namespace pmdi_s2) for the HOST: every primitive resolves through the lock-step workgroup emulator of
 // wavesim.h.  A translation unit includes this header and THEN the kernel body; the body sees PM2_LANE_API_PROVIDED and leaves
 // its own gfx950 definitions out.  Nothing under particlemdi.jl_amd/ includes or knows this file.
+// What every wave primitive here has to return is specified in tests/_np_lanes.py; tests/test_lanes_host.py holds this file to it,
+// tests/test_gpu_lanes.py the gfx950 definitions.
 #pragma once
 #include <math.h>
 
@@ -48,17 +50,19 @@ inline int shfl_i(int v, int src) { return (int)(unsigned)PM2_SHFL64((u64)(unsig
 // the value of lane `src` (wave-uniform)
 inline int readlane_i(int v, int src) { return shfl_i(v, src); }
 inline u64 readlane_u64(u64 v, int src) { return PM2_SHFL64(v, src); }
+// (after the butterfly every lane holds the extremum's value, but with zeros of both signs in the wave not the same zero: lane 0's is
+// taken, since the contract -- tests/_np_lanes.py -- is the same bits on every lane)
 inline double wave_max_d(double v)
 {
     const int lane = PM2_TID() & 63;
     for (int o = 1; o < 64; o <<= 1) { const double t = shfl_d(v, lane ^ o); v = (t > v) ? t : v; }
-    return v;
+    return shfl_d(v, 0);
 }
 inline double wave_min_d(double v)
 {
     const int lane = PM2_TID() & 63;
     for (int o = 1; o < 64; o <<= 1) { const double t = shfl_d(v, lane ^ o); v = (t < v) ? t : v; }
-    return v;
+    return shfl_d(v, 0);
 }
 inline double prev_lane_d(double v) { const int lane = PM2_TID() & 63; return shfl_d(v, lane ? lane - 1 : 0); }
 // (the device's order: quad, quad pair, half row, row, then (r0 + r1) + (r2 + r3) over the four rows of sixteen lanes)
