@@ -403,6 +403,47 @@ int pmdi_psm_refine_vi_device(int32_t device, const int32_t *counts, int64_t S, 
                               int32_t *sweeps_out /* host, B */, int64_t *objective_out /* host, B: F of labels_out */,
                               void *stream);
 
+/* ---- partition distances: candidates against sampled clusterings ---------------------------------------------------------
+ * The calls above compare a clustering with the PSM.  These compare it with the clusterings the chains drew, one by one: the
+ * contingency table n_gh = #{i : c_i = g, s_i = h} of every candidate c against every draw s, reduced to exact integers.  From
+ * them follow the distances of Wade & Ghahramani (2018, section 4) between two clusterings of n observations, with a_g the
+ * label counts of c, b_h those of s, C(x, 2) = x (x - 1) / 2 and L the fixed-point logarithm defined above (the same table):
+ *   pairs(c) = sum_g C(a_g, 2)        hl(c) = sum_g a_g L(a_g)        (0 L(0) = 0)
+ *   both(c, s) = sum_gh C(n_gh, 2)    jl(c, s) = sum_gh n_gh L(n_gh)
+ *   Binder: the pairs of observations the two disagree on = pairs(c) + pairs(s) - 2 both(c, s);
+ *   VI in bits = [hl(c) + hl(s) - 2 jl(c, s)] / (n 2^30), up to the error of L (at most 3 n bound(L) on the bracket / 2^30);
+ *   adjusted Rand index = (both - E) / ((pairs(c) + pairs(s)) / 2 - E), E = pairs(c) pairs(s) / C(n, 2).
+ * The Monte-Carlo posterior expected loss of c is the mean of a distance over the draws; the credible ball around c is the set
+ * of draws within the distance that holds a given share of them.
+ *
+ * pmdi_partition_rows_device packs R label rows into the bytes the distance kernel reads and forms their marginals.  labels:
+ * DEVICE memory, int32 (is_bytes = 0) or uint8 (is_bytes != 0), row r = the n labels at labels + r ld (elements; ld >= n, unit
+ * stride along n): the resident allocations s [C][K][n] are read in place (dataset k of every chain: labels = s + k n,
+ * ld = K n, R = C; all C K rows: ld = n, R = C K).  Every label must lie in 0..G-1, G <= PMDI_PARTDIST_GMAX (renumber by first
+ * appearance to get there).  bytes_out: DEVICE uint8 [R][np], np = n rounded up to a multiple of 32, 16-byte aligned; the bytes
+ * behind n are 255, which matches no label.  pairs_out, hl_out (int64) and nclust_out (int32, the occupied labels) are HOST
+ * arrays of R, so the call SYNCHRONISES `stream`.  A label outside 0..G-1 (a negative one included) indexes nothing, goes out as
+ * 255, raises a device flag and the call returns PMDI_E_ARG with the outputs undefined.
+ * PMDI_E_ARG, before any device use: a null pointer; R outside 1..2^31 - 1; n outside 1..65535; ld < n; G outside
+ * 1..PMDI_PARTDIST_GMAX.
+ *
+ * pmdi_partition_distance_device: cand_bytes [B][np] (labels < Gc) and draw_bytes [R][np] (labels < Gd) as written above, DEVICE.
+ * both_out and jl_out: DEVICE int64 [B][R], every element written by the call whatever it held before; the call is asynchronous
+ * on `stream` and allocates nothing.  The table n_gh is a product of one-hot int8 matrices on the matrix cores and is never
+ * stored; every output word is owned by one wavefront and every sum is an integer, so the results are bit-defined.
+ * The limits on n: 1 <= n <= 65535.  An entry of the table is at most n, so C(n_gh, 2) < 2^31 is formed in 32 bits; L(x) < 31 x
+ * 2^30 for x < 2^31, so jl, hl <= n L(n) < n 31 2^30 < 2^51 and every sum stays far inside int64; one draw row of np bytes, four
+ * staging buffers of 1 KiB and the 8 KiB table share one workgroup's LDS (at most 77 828 bytes).
+ * PMDI_E_ARG, before any device use: a null pointer; B < 1; R outside 1..2^31 - 1; n outside 1..65535; Gc or Gd outside
+ * 1..PMDI_PARTDIST_GMAX; B R >= 2^59.  n = 1: both = 0, jl = 0.  Stateless. */
+#define PMDI_PARTDIST_GMAX 255   /* labels of one side: a label is a byte and 255 is the padding */
+int pmdi_partition_rows_device(int32_t device, const void *labels /* device */, int32_t is_bytes, int64_t R, int64_t n, int64_t ld,
+                               int32_t G, uint8_t *bytes_out /* device, R np */, int64_t *pairs_out /* host, R */,
+                               int64_t *hl_out /* host, R */, int32_t *nclust_out /* host, R */, void *stream);
+int pmdi_partition_distance_device(int32_t device, const uint8_t *cand_bytes /* device, B np */, int64_t B, int32_t Gc,
+                                   const uint8_t *draw_bytes /* device, R np */, int64_t R, int32_t Gd, int64_t n,
+                                   int64_t *both_out /* device, B R */, int64_t *jl_out /* device, B R */, void *stream);
+
 /* ---- consensus_map (src/output_analysis/consensus_map.jl:125-196): block sums of the PSMs over a grouping ------------------
  * The reference gathers Symmetric(psm.psm[m], :L)[order, order] for every matrix and hands n x n cells to a plotting library.
  * pmdi_psm_blocksum_device sums the matrices over a grouping of the observations instead, without an n x n temporary.  With the

@@ -4,7 +4,7 @@ The directory name `particlemdi.jl_amd` is not a Python identifier; load it
 with `__graft_entry__.load_package()` which registers it as `particlemdi_jl_amd`.
 """
 from ._lib import (  # noqa: F401
-    ABI_VERSION, BLOCKSUM_GMAX, CATEGORICAL, EXPORTS, GAUSSIAN, KIND_BY_NAME, LIB_PATH, NEGBINOM,
+    ABI_VERSION, BLOCKSUM_GMAX, CATEGORICAL, EXPORTS, GAUSSIAN, KIND_BY_NAME, LIB_PATH, NEGBINOM, PARTDIST_GMAX,
     ClusterBatch, Comm, CsvWriter, Gibbs, format_float64, read_allocations, PmdiError, REFINE_GMAX, Sweeper, build, lib,
     STEP_ALIGN, STEP_BEGIN, STEP_FEATSEL, STEP_HYPERS, STEP_SWEEP,
 )
@@ -14,6 +14,7 @@ from .psm import (  # noqa: F401,E402
     block_similarity, block_sums, consensus_map, refine_allocations,
     retained_iterations, row_scores, score_allocations, search_consensus_allocation, select_consensus_allocations, vi_log2_table,
 )
+from .partition import CredibleBall, PartitionDistances, credible_ball, partition_distances  # noqa: F401,E402
 from .datamap import (  # noqa: F401,E402
     ClusterProfiles, DataMap, cluster_profiles, column_moments, data_map, group_sums,
 )

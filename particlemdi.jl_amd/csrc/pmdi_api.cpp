@@ -845,6 +845,49 @@ int pmdi_psm_refine_vi_device(int32_t device, const int32_t *counts, int64_t S, 
     return PMDI_OK;
 }
 
+int pmdi_partition_rows_device(int32_t device, const void *labels, int32_t is_bytes, int64_t R, int64_t n, int64_t ld, int32_t G,
+                               uint8_t *bytes_out, int64_t *pairs_out, int64_t *hl_out, int32_t *nclust_out, void *stream)
+{
+    if (!labels || !bytes_out || !pairs_out || !hl_out || !nclust_out) return fail(PMDI_E_ARG, "pmdi_partition_rows_device: null argument");
+    if (R < 1 || R > 2147483647LL || n < 1 || n > 65535 || ld < n || G < 1 || G > PMDI_PARTDIST_GMAX)
+        return fail(PMDI_E_ARG, "pmdi_partition_rows_device: R=%lld n=%lld ld=%lld G=%d out of range (R <= 2^31 - 1, 1 <= n <= 65535, ld >= n, 1 <= G <= %d)",
+                    (long long)R, (long long)n, (long long)ld, G, PMDI_PARTDIST_GMAX);
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    Scratch out;
+    const size_t bytes = (size_t)R * 20 + 8;         // R pairs, R hl, R nclust, the flag
+    HIP_TRY(hipMalloc(&out.p, bytes));
+    HIP_TRY(hipMemsetAsync(out.p, 0, bytes, st));
+    long long *d_pairs = (long long *)out.p, *d_hl = d_pairs + R;
+    int *d_nclust = (int *)(d_hl + R), *d_flag = d_nclust + R;
+    const hipError_t e = pmdi_launch_partition_rows(labels, is_bytes ? 1 : 0, R, n, ld, G, bytes_out, d_pairs, d_hl, d_nclust, d_flag, st);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "partition-rows launch: %s", hipGetErrorString(e));
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(pairs_out, d_pairs, (size_t)R * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hl_out, d_hl, (size_t)R * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(nclust_out, d_nclust, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&bad, d_flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad) return fail(PMDI_E_ARG, "pmdi_partition_rows_device: a label outside 0..%d", G - 1);
+    return PMDI_OK;
+}
+
+int pmdi_partition_distance_device(int32_t device, const uint8_t *cand_bytes, int64_t B, int32_t Gc, const uint8_t *draw_bytes, int64_t R,
+                                   int32_t Gd, int64_t n, int64_t *both_out, int64_t *jl_out, void *stream)
+{
+    if (!cand_bytes || !draw_bytes || !both_out || !jl_out) return fail(PMDI_E_ARG, "pmdi_partition_distance_device: null argument");
+    if (B < 1 || R < 1 || R > 2147483647LL || n < 1 || n > 65535 || Gc < 1 || Gc > PMDI_PARTDIST_GMAX || Gd < 1 || Gd > PMDI_PARTDIST_GMAX)
+        return fail(PMDI_E_ARG, "pmdi_partition_distance_device: B=%lld R=%lld n=%lld Gc=%d Gd=%d out of range (R <= 2^31 - 1, 1 <= n <= 65535, 1 <= G <= %d)",
+                    (long long)B, (long long)R, (long long)n, Gc, Gd, PMDI_PARTDIST_GMAX);
+    if ((unsigned __int128)B * (unsigned __int128)R >= ((unsigned __int128)1 << 59))      // 8 B R bytes of each output
+        return fail(PMDI_E_ARG, "pmdi_partition_distance_device: B=%lld R=%lld: B R >= 2^59", (long long)B, (long long)R);
+    HIP_TRY(hipSetDevice(device));
+    const hipError_t e = pmdi_launch_partition_distance(cand_bytes, B, Gc, draw_bytes, R, Gd, n, (long long *)both_out, (long long *)jl_out,
+                                                        (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "partition-distance launch: %s", hipGetErrorString(e));
+    return PMDI_OK;
+}
+
 static_assert(PMDI_BLOCKSUM_GMAX == PSM_BLOCKSUM_GMAX_I, "the header's group count is the kernel's");
 
 int pmdi_psm_blocksum_device(int32_t device, const int32_t *counts, int64_t S, int32_t K, int64_t n, const int32_t *group, int32_t G,

@@ -260,6 +260,13 @@ hipError_t pmdi_launch_psm_refine_vi(const int *counts, int K, long long n, int 
                                      const int *start, long long B, long long ld, int max_sweeps, int *labels, long long *moves,
                                      int *sweeps, long long *objective, int *flag, hipStream_t stream);
 void pmdi_vi_log2_table_host(int *out);
+// partition distances (pmdi_partdist.hip).  rows: R label rows (int32, or bytes when is_bytes; row r at labels + r ld) into bytes
+// [R][np], np = n rounded up to 32, with pairs, hl [R], nclust [R] and err [1] (zeroed by the caller) on the device.  distance:
+// cand [B][np] and draws [R][np] of such bytes into both, jl [B][R] on the device, every element written once
+hipError_t pmdi_launch_partition_rows(const void *labels, int is_bytes, long long R, long long n, long long ld, int G, unsigned char *bytes,
+                                      long long *pairs, long long *hl, int *nclust, int *err, hipStream_t stream);
+hipError_t pmdi_launch_partition_distance(const unsigned char *cand, long long B, int Gc, const unsigned char *draws, long long R, int Gd,
+                                          long long n, long long *both, long long *jl, hipStream_t stream);
 // block sums over a grouping (pmdi_psm_blocksum.hip): the tables of PsmBlocksumPlan (pmdi_psm_blocksum_plan.h) on the device;
 // out [K + (K > 1)][G][G] on the device, every element written
 hipError_t pmdi_launch_psm_blocksum(const int *counts, long long S, int K, long long n, int G, const unsigned short *g16, long long npad,
