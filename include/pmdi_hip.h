@@ -444,6 +444,49 @@ int pmdi_partition_distance_device(int32_t device, const uint8_t *cand_bytes /* 
                                    const uint8_t *draw_bytes /* device, R np */, int64_t R, int32_t Gd, int64_t n,
                                    int64_t *both_out /* device, B R */, int64_t *jl_out /* device, B R */, void *stream);
 
+/* ---- a descent of the expected loss against the sampled clusterings -------------------------------------------------------
+ * pmdi_psm_refine_vi_device descends the Jensen bound of the expected VI, formed from the pairwise matrix.
+ * pmdi_partition_refine_device descends the Monte-Carlo expected loss itself, against the draws (the greedy search of Dahl,
+ * Johnson & Mueller, 2022, with the visiting and tie rules of pmdi_psm_refine_device), in exact integers and without an n x n
+ * matrix.  Notation: s_1..s_R the draw rows (labels < Gd); c a clustering with slots 0..gcap-1; a_g = |g|;
+ * n^r_gh = #{i : c_i = g, s_r(i) = h}; M(x) = x L(x) for loss = 1 (vi; L the fixed-point logarithm above, M(0) = 0) and
+ * M(x) = x (x - 1) / 2 for loss = 0 (binder); d(x) = M(x + 1) - M(x), so d(0) = 0 in both.  The objective is the int64
+ *   F(c) = R sum_g M(a_g) - 2 sum_r sum_gh M(n^r_gh):
+ * for vi, sum_r [hl(c) + hl(s_r) - 2 jl(c, s_r)] = F(c) + sum_r hl(s_r), R n 2^30 times the expected VI in bits; for binder,
+ * sum_r [pairs(c) + pairs(s_r) - 2 both(c, s_r)] = F(c) + sum_r pairs(s_r), R times the expected Binder loss in pairs.
+ * One sweep visits i = 0..n-1 in index order.  For the current i:
+ *   1. i is taken out of its group cur: a_cur falls by 1, and n^r_{cur,h_r} falls by 1 for every r, h_r = s_r(i);
+ *   2. every live group g, cur included unless it is now empty, has score(g) = 2 sum_r d(n^r_{g,h_r}) - R d(a_g);
+ *   3. a new singleton scores 0 and takes the lowest free slot; it is offered only if i was not alone and fewer than gcap
+ *      groups are live; if i was alone, its own slot scores 0;
+ *   4. the options are ranked: the current group, the other live groups by ascending slot, the new singleton; the first
+ *      option with the largest score wins;
+ *   5. i is put there.
+ * F falls by score(new) - score(cur), which is > 0 exactly when i moves.  Sweeps repeat until one makes no move or max_sweeps
+ * (>= 1) are done.  With loss = 0, score(g) = 2 A_i(g) - R a_g with A_i(g) = sum_r n^r_{g,h_r}: the gain of
+ * pmdi_psm_refine_device on the counts of the same draws, D = R.
+ * draw_bytes: DEVICE [R][np] as pmdi_partition_rows_device writes them.  start: DEVICE int32, start b at start + b ld; a start
+ * label IS the slot of its group, in 0..gcap-1.  labels_out: DEVICE int32 [B][n], the final slots.  moves_out (int64),
+ * sweeps_out (int32, a last sweep without a move included), converged_out (int32: the last sweep made no move),
+ * marginal_out = sum_g M(a_g) and joint_out = sum_r sum_gh M(n^r_gh) (int64) are HOST arrays of B; the two sums are formed from
+ * the definition after the last sweep, by a pass over the final tables, and F = R marginal - 2 joint.
+ * Limits.  1 <= n <= 65535, so a table cell is a uint16.  1 <= R <= 2^24 and R n < 2^28.  For x <= 65535, L(x) < 2^34 and
+ * d(x) = L(x + 1) + x [L(x + 1) - L(x)] < 2^35, so a score, 2 R d, stays below 2^61 in magnitude; M(x) < 2^50, so
+ * R sum_g M(a_g) <= R n L(n) < 2^62 and sum_r sum_gh M(n^r_gh) <= R n L(n) < 2^62 (R n < 2^28, L(n) < 2^34): nothing beyond the
+ * argument checks guards against overflow.  1 <= Gd <= 255 and 1 <= gcap <= 255.
+ * The call allocates its work space -- the tables, B R Gd Gp uint16 with Gp = the power of two >= gcap, and the draws
+ * transposed to [n][R] bytes --, frees it before it returns and therefore SYNCHRONISES `stream`; a caller with many starts
+ * passes them in slabs.  An allocation that fails is PMDI_E_MEMORY.
+ * PMDI_E_ARG, before any device use: a null pointer; B < 1; R outside 1..2^24; n outside 1..65535; R n >= 2^28; ld < n; Gd or
+ * gcap outside 1..255; loss not 0 or 1; max_sweeps < 1.  A start label outside 0..gcap-1, or a draw byte >= Gd before column n,
+ * raises a device flag (nothing is indexed by it) and the call returns PMDI_E_DATA with the outputs undefined.  n = 1: no move,
+ * one sweep, converged, both sums 0.  Stateless. */
+int pmdi_partition_refine_device(int32_t device, const uint8_t *draw_bytes /* device, R np */, int64_t R, int32_t Gd, int64_t n,
+                                 const int32_t *start /* device */, int64_t B, int64_t ld, int32_t gcap, int32_t loss /* 0 binder, 1 vi */,
+                                 int32_t max_sweeps, int32_t *labels_out /* device, B n */, int64_t *moves_out /* host, B */,
+                                 int32_t *sweeps_out /* host, B */, int32_t *converged_out /* host, B */,
+                                 int64_t *marginal_out /* host, B */, int64_t *joint_out /* host, B */, void *stream);
+
 /* ---- consensus_map (src/output_analysis/consensus_map.jl:125-196): block sums of the PSMs over a grouping ------------------
  * The reference gathers Symmetric(psm.psm[m], :L)[order, order] for every matrix and hands n x n cells to a plotting library.
  * pmdi_psm_blocksum_device sums the matrices over a grouping of the observations instead, without an n x n temporary.  With the

@@ -14,7 +14,8 @@ from .psm import (  # noqa: F401,E402
     block_similarity, block_sums, consensus_map, refine_allocations,
     retained_iterations, row_scores, score_allocations, search_consensus_allocation, select_consensus_allocations, vi_log2_table,
 )
-from .partition import CredibleBall, PartitionDistances, credible_ball, partition_distances  # noqa: F401,E402
+from .partition import (  # noqa: F401,E402
+    CredibleBall, PartitionDistances, credible_ball, minimise_expected_loss, partition_distances, refine_expected_loss)
 from .datamap import (  # noqa: F401,E402
     ClusterProfiles, DataMap, cluster_profiles, column_moments, data_map, group_sums,
 )

@@ -13,7 +13,7 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("PMDI_LIB_PATH") or os.path.join(_PKG, "libpmdi_hip.so")   # override: A/B builds only
-_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_fusion.hip", "pmdi_summary.hip", "pmdi_mixing.hip", "pmdi_predict.hip", "pmdi_predict_coupled.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_psm_refine_vi.hip", "pmdi_partdist.hip", "pmdi_psm_blocksum.hip", "pmdi_data_groupsum.hip", "pmdi_api.cpp", "pmdi_plan.cpp", "pmdi_acc.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
+_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_fusion.hip", "pmdi_summary.hip", "pmdi_mixing.hip", "pmdi_predict.hip", "pmdi_predict_coupled.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_psm_refine_vi.hip", "pmdi_partdist.hip", "pmdi_partdist_refine.hip", "pmdi_psm_blocksum.hip", "pmdi_data_groupsum.hip", "pmdi_api.cpp", "pmdi_plan.cpp", "pmdi_acc.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
 # every header decides when to rebuild: a new one cannot be forgotten
 _HEADERS = sorted(glob.glob(os.path.join(_PKG, "csrc", "*.h"))) + [os.path.join(_ROOT, "include", "pmdi_hip.h")]
 
@@ -56,7 +56,7 @@ EXPORTS = [
     "pmdi_predict_add_arrays", "pmdi_predict_merge", "pmdi_predict_get", "pmdi_predict_counts", "pmdi_predict_last", "pmdi_gibbs_run5",
     "pmdi_predict_create_coupled", "pmdi_predict_add_arrays_coupled", "pmdi_predict_merge_coupled", "pmdi_predict_get_coupled",
     "pmdi_predict_last_coupled",
-    "pmdi_partition_rows_device", "pmdi_partition_distance_device",
+    "pmdi_partition_rows_device", "pmdi_partition_distance_device", "pmdi_partition_refine_device",
 ]
 
 
@@ -229,6 +229,8 @@ def lib():
     L.pmdi_partition_rows_device.argtypes = [i32, vp, i32, i64, i64, i64, i32, vp, vp, vp, vp, vp]
     L.pmdi_partition_distance_device.restype = C.c_int
     L.pmdi_partition_distance_device.argtypes = [i32, vp, i64, i32, vp, i64, i32, i64, vp, vp, vp]
+    L.pmdi_partition_refine_device.restype = C.c_int
+    L.pmdi_partition_refine_device.argtypes = [i32, vp, i64, i32, i64, vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.pmdi_psm_blocksum_device.restype = C.c_int
     L.pmdi_psm_blocksum_device.argtypes = [i32, vp, i64, i32, i64, vp, i32, vp, vp]
     L.pmdi_data_groupsum_device.restype = C.c_int

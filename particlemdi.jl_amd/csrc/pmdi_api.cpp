@@ -888,6 +888,51 @@ int pmdi_partition_distance_device(int32_t device, const uint8_t *cand_bytes, in
     return PMDI_OK;
 }
 
+int pmdi_partition_refine_device(int32_t device, const uint8_t *draw_bytes, int64_t R, int32_t Gd, int64_t n, const int32_t *start, int64_t B,
+                                 int64_t ld, int32_t gcap, int32_t loss, int32_t max_sweeps, int32_t *labels_out, int64_t *moves_out,
+                                 int32_t *sweeps_out, int32_t *converged_out, int64_t *marginal_out, int64_t *joint_out, void *stream)
+{
+    if (!draw_bytes || !start || !labels_out || !moves_out || !sweeps_out || !converged_out || !marginal_out || !joint_out)
+        return fail(PMDI_E_ARG, "pmdi_partition_refine_device: null argument");
+    if (B < 1 || R < 1 || R > (1LL << 24) || n < 1 || n > 65535 || R * n >= (1LL << 28) || ld < n || Gd < 1 || Gd > PMDI_PARTDIST_GMAX ||
+        gcap < 1 || gcap > PMDI_PARTDIST_GMAX)
+        return fail(PMDI_E_ARG, "pmdi_partition_refine_device: B=%lld R=%lld n=%lld ld=%lld Gd=%d gcap=%d out of range (R <= 2^24, 1 <= n <= 65535, R n < 2^28, ld >= n, 1 <= Gd, gcap <= %d)",
+                    (long long)B, (long long)R, (long long)n, (long long)ld, Gd, gcap, PMDI_PARTDIST_GMAX);
+    if (loss != 0 && loss != 1) return fail(PMDI_E_ARG, "pmdi_partition_refine_device: loss=%d is not 0 (binder) or 1 (vi)", loss);
+    if (max_sweeps < 1) return fail(PMDI_E_ARG, "pmdi_partition_refine_device: max_sweeps=%d < 1", max_sweeps);
+    int lgp = 0;
+    while ((1 << lgp) < gcap) ++lgp;                 // the slots of one (r, h), padded to a power of two
+    const unsigned __int128 table_bytes = (unsigned __int128)B * (unsigned __int128)(((R * Gd) << lgp) * 2);
+    if (table_bytes >= ((unsigned __int128)1 << 62))
+        return fail(PMDI_E_MEMORY, "pmdi_partition_refine_device: B=%lld starts need tables of 2^62 bytes or more", (long long)B);
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    Scratch transposed, tables, out;
+    const size_t out_bytes = (size_t)B * 32 + 8;     // B moves, B marginals, B joints, B sweeps, B converged, the flag
+    HIP_TRY(hipMalloc(&transposed.p, (size_t)n * (size_t)R));
+    HIP_TRY(hipMalloc(&tables.p, (size_t)table_bytes));
+    HIP_TRY(hipMalloc(&out.p, out_bytes));
+    HIP_TRY(hipMemsetAsync(tables.p, 0, (size_t)table_bytes, st));
+    HIP_TRY(hipMemsetAsync(out.p, 0, out_bytes, st));
+    long long *d_moves = (long long *)out.p, *d_marginal = d_moves + B, *d_joint = d_marginal + B;
+    int *d_sweeps = (int *)(d_joint + B), *d_converged = d_sweeps + B, *d_flag = d_converged + B;
+    const hipError_t e = pmdi_launch_partition_refine(draw_bytes, R, Gd, n, (unsigned char *)transposed.p, (unsigned short *)tables.p, lgp, start,
+                                                      B, ld, gcap, loss, max_sweeps, labels_out, d_moves, d_sweeps, d_converged, d_marginal,
+                                                      d_joint, d_flag, st);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "partition-refine launch: %s", hipGetErrorString(e));
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(moves_out, d_moves, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(marginal_out, d_marginal, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(joint_out, d_joint, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(sweeps_out, d_sweeps, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(converged_out, d_converged, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&bad, d_flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));               // the work spaces are freed on return
+    if (bad & 1) return fail(PMDI_E_DATA, "pmdi_partition_refine_device: a start label outside 0..%d", gcap - 1);
+    if (bad & 2) return fail(PMDI_E_DATA, "pmdi_partition_refine_device: a draw label outside 0..%d", Gd - 1);
+    return PMDI_OK;
+}
+
 static_assert(PMDI_BLOCKSUM_GMAX == PSM_BLOCKSUM_GMAX_I, "the header's group count is the kernel's");
 
 int pmdi_psm_blocksum_device(int32_t device, const int32_t *counts, int64_t S, int32_t K, int64_t n, const int32_t *group, int32_t G,

@@ -267,6 +267,14 @@ hipError_t pmdi_launch_partition_rows(const void *labels, int is_bytes, long lon
                                       long long *pairs, long long *hl, int *nclust, int *err, hipStream_t stream);
 hipError_t pmdi_launch_partition_distance(const unsigned char *cand, long long B, int Gc, const unsigned char *draws, long long R, int Gd,
                                           long long n, long long *both, long long *jl, hipStream_t stream);
+// descent of the expected loss against the draws (pmdi_partdist_refine.hip).  draw_bytes [R][np] of such bytes; dT = n R bytes and
+// tables = B (R Gd << lgp) uint16 of work space, the tables zeroed by the caller, lgp = log2 of the power of two >= gcap; labels
+// [B][n], moves, marginal, joint [B] int64, sweeps, converged [B] int32, flag [1] (zeroed by the caller; 1 = a start label
+// outside the slots, 2 = a draw byte >= Gd) on the device
+hipError_t pmdi_launch_partition_refine(const unsigned char *draw_bytes, long long R, int Gd, long long n, unsigned char *dT,
+                                        unsigned short *tables, int lgp, const int *start, long long B, long long ld, int gcap, int loss,
+                                        int max_sweeps, int *labels, long long *moves, int *sweeps, int *converged, long long *marginal,
+                                        long long *joint, int *flag, hipStream_t stream);
 // block sums over a grouping (pmdi_psm_blocksum.hip): the tables of PsmBlocksumPlan (pmdi_psm_blocksum_plan.h) on the device;
 // out [K + (K > 1)][G][G] on the device, every element written
 hipError_t pmdi_launch_psm_blocksum(const int *counts, long long S, int K, long long n, int G, const unsigned short *g16, long long npad,

@@ -8,39 +8,22 @@
 //                             the contingency table n_gh = #{i : c_i = g, s_i = h} is a product of one-hot int8 matrices with
 //                             the observations as the inner dimension (v_mfma_i32_32x32x32_i8) and lives in the accumulators
 //                             only: both = sum_gh C(n_gh, 2), jl = sum_gh n_gh L(n_gh)
-// L is the fixed-point logarithm of pmdi_psm_refine_vi.hip (the table of pmdi_vi_log2_table.h, here in LDS).  Every output word
+// L is the fixed-point logarithm of pmdi_fixlog.h (the table of pmdi_vi_log2_table.h, here in LDS).  Every output word
 // is owned by one wave and every sum is an integer: the results are bit-defined.
 #include <hip/hip_runtime.h>
 
+#include "pmdi_fixlog.h"            // L in 32-bit steps and v L(v)
 #include "pmdi_internal.h"
 #include "pmdi_onehot.h"            // the fragment types, MX_PAD, mx_wave_sync, mx_wave_sum, mx_onehot
 
 namespace {
 
-#define PD_TABLE 2049
+#define PD_TABLE PMDI_FIXLOG_TABLE
 #define PD_CHUNK 1024   // candidate label bytes a wave stages per round: 16 per lane
 
 __device__ const int pd_table[PD_TABLE] = {
 #include "pmdi_vi_log2_table.h"
 };
-
-// L(x) of include/pmdi_hip.h for 1 <= x < 2^32, in 32-bit steps: with m = x << (31 - e) (bit 31 set) the header's f is
-// (m - 2^31) << 31, so k = f >> 51 = (m - 2^31) >> 20 and r32 = (f & (2^51 - 1)) >> 19 = (m & (2^20 - 1)) << 12.
-__device__ __forceinline__ long long pd_L(unsigned x, const int *T)
-{
-    const int e = 31 - __clz((int)x);
-    const unsigned m = x << (31 - e);
-    const unsigned k = (m & 0x7fffffffu) >> 20;
-    const unsigned r32 = (m & 0xfffffu) << 12;
-    const int t0 = T[k], t1 = T[k + 1];
-    return ((long long)e << 30) + (long long)t0 + (long long)__umulhi((unsigned)(t1 - t0), r32);
-}
-
-// v L(v) with 0 L(0) = 0, branch-free: L(1) = 0
-__device__ __forceinline__ unsigned long long pd_vL(unsigned v, const int *T)
-{
-    return (unsigned long long)v * (unsigned long long)pd_L(v ? v : 1u, T);
-}
 
 // Row `row` of s (row r at s + r ld, n labels of unit stride) into bytes out [rows][np] (np = n rounded up to 32; the bytes
 // behind n are MX_PAD), one wavefront per row, 4 rows per workgroup; a lane packs four consecutive labels into one aligned
@@ -86,7 +69,7 @@ __global__ void __launch_bounds__(256) partdist_rows_kernel(const T *__restrict_
     for (int a = lane; a < G; a += 64) {
         const unsigned c = (unsigned)h[a];                   // <= 65535: c (c - 1) / 2 < 2^31
         pr += (unsigned long long)((c * (c - 1u)) >> 1);     // (c = 0: the product is 0 whatever c - 1 wrapped to)
-        lg += pd_vL(c, tab);
+        lg += pmdi_fixlog_vL32(c, tab);
         occupied += c ? 1ull : 0ull;
     }
     pr = mx_wave_sum(pr);
@@ -183,7 +166,7 @@ __global__ void __launch_bounds__(256) partdist_kernel(const unsigned char *__re
                         for (int e = 0; e < 16; ++e) {
                             const unsigned c = (unsigned)acc[i][j][e];       // <= 65535: c (c - 1) / 2 < 2^31, c L(c) < 2^50
                             t_both += (unsigned long long)((c * (c - 1u)) >> 1);
-                            t_jl += pd_vL(c, tab);
+                            t_jl += pmdi_fixlog_vL32(c, tab);
                         }
             }
         t_both = mx_wave_sum(t_both);

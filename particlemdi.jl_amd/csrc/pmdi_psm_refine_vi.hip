@@ -21,32 +21,18 @@
 // remarks, for the same reason as there.
 #include <hip/hip_runtime.h>
 
+#include "pmdi_fixlog.h"            // L and s L(s)
 #include "pmdi_internal.h"
 
 namespace {
 
 #define PSM_VI_G PMDI_REFINE_GMAX_I
 #define PSM_VI_THREADS 1024
-#define PSM_VI_TABLE 2049
+#define PSM_VI_TABLE PMDI_FIXLOG_TABLE
 
 __device__ const int psm_vi_table[PSM_VI_TABLE] = {
 #include "pmdi_vi_log2_table.h"
 };
-
-// L(x), 1 <= x < 2^62: the exponent, the table entry of the mantissa's first 11 bits and a linear step towards the next entry by
-// its following 32 bits.  t1 - t0 < 2^20 and r32 < 2^32: the high word of their 64-bit product is (t1 - t0) r32 >> 32.
-__device__ __forceinline__ long long psm_vi_L(unsigned long long x, const int *T)
-{
-    const int e = 63 - __clzll((long long)x);
-    const unsigned long long f = (x << (62 - e)) - (1ull << 62);
-    const unsigned k = (unsigned)(f >> 51);
-    const unsigned r32 = (unsigned)((f & ((1ull << 51) - 1ull)) >> 19);
-    const int t0 = T[k], t1 = T[k + 1];
-    return ((long long)e << 30) + (long long)t0 + (long long)__umulhi((unsigned)(t1 - t0), r32);
-}
-
-// s L(s), with 0 L(0) = 0
-__device__ __forceinline__ long long psm_vi_sL(int s, const int *T) { return s > 0 ? (long long)s * psm_vi_L((unsigned long long)s, T) : 0; }
 
 __global__ void __launch_bounds__(PSM_VI_THREADS) psm_refine_vi_kernel(const unsigned *__restrict__ W, long long n, long long D,
                                                                        const int *__restrict__ start, long long ld, int max_sweeps,
@@ -129,7 +115,7 @@ __global__ void __launch_bounds__(PSM_VI_THREADS) psm_refine_vi_kernel(const uns
                         const unsigned long long od = (unsigned long long)(o[u] + D);
                         const unsigned long long om = l[u] == cur ? od - w[u] : od + w[u];      // after i has moved
                         atomicAdd(&A[l[u]], (unsigned long long)w[u]);
-                        atomicAdd(&R[l[u]], (unsigned long long)(psm_vi_L(om, T) - psm_vi_L(od, T)));
+                        atomicAdd(&R[l[u]], (unsigned long long)(pmdi_fixlog_L(om, T) - pmdi_fixlog_L(od, T)));
                     }
             }
             __syncthreads();
@@ -138,8 +124,8 @@ __global__ void __launch_bounds__(PSM_VI_THREADS) psm_refine_vi_kernel(const uns
                 const int sz_cur = gsz[cur];
                 const bool alone = sz_cur == 1;
                 // what leaving the current group gains, the same for every destination
-                const long long leave = psm_vi_sL(sz_cur, T) - psm_vi_sL(sz_cur - 1, T) + 2 * (long long)R[cur]
-                                        - 2 * psm_vi_L((unsigned long long)(a_cur + D), T);
+                const long long leave = pmdi_fixlog_sL(sz_cur, T) - pmdi_fixlog_sL(sz_cur - 1, T) + 2 * (long long)R[cur]
+                                        - 2 * pmdi_fixlog_L((unsigned long long)(a_cur + D), T);
                 long long bg = 0, ba = 0;
                 int bs = -1;
                 for (int g = lane; g < hi; g += 64) {                          // ascending slots: a lane keeps its lowest best
@@ -147,8 +133,8 @@ __global__ void __launch_bounds__(PSM_VI_THREADS) psm_refine_vi_kernel(const uns
                     const int sz = gsz[g];
                     A[g] = 0; R[g] = 0;
                     if (g != cur && sz > 0) {
-                        const long long gain = leave - (psm_vi_sL(sz + 1, T) - psm_vi_sL(sz, T)) + 2 * r
-                                               + 2 * psm_vi_L((unsigned long long)(a + D), T);
+                        const long long gain = leave - (pmdi_fixlog_sL(sz + 1, T) - pmdi_fixlog_sL(sz, T)) + 2 * r
+                                               + 2 * pmdi_fixlog_L((unsigned long long)(a + D), T);
                         if (bs < 0 || gain > bg) { bg = gain; bs = g; ba = a; }
                     }
                 }
@@ -160,7 +146,7 @@ __global__ void __launch_bounds__(PSM_VI_THREADS) psm_refine_vi_kernel(const uns
                 long long tg = 0, a_new = a_cur;                               // the current group: gain 0
                 int target = cur;
                 if (bs >= 0 && bg > tg) { target = bs; tg = bg; a_new = ba; }
-                if (!alone && live < PSM_VI_G && leave + 2 * psm_vi_L((unsigned long long)D, T) > tg) {     // the new singleton: the lowest free slot
+                if (!alone && live < PSM_VI_G && leave + 2 * pmdi_fixlog_L((unsigned long long)D, T) > tg) {     // the new singleton: the lowest free slot
                     int f = PSM_VI_G;
                     for (int g = lane; g < PSM_VI_G; g += 64)
                         if (gsz[g] == 0) { f = g; break; }
@@ -207,8 +193,8 @@ __global__ void __launch_bounds__(PSM_VI_THREADS) psm_refine_vi_kernel(const uns
     }
 
     long long part = 0;                                                        // F of the result, literally
-    for (long long j = tid; j < n; j += PSM_VI_THREADS) part -= 2 * psm_vi_L((unsigned long long)(own[j] + D), T);
-    for (int g = tid; g < PSM_VI_G; g += PSM_VI_THREADS) part += psm_vi_sL(gsz[g], T);
+    for (long long j = tid; j < n; j += PSM_VI_THREADS) part -= 2 * pmdi_fixlog_L((unsigned long long)(own[j] + D), T);
+    for (int g = tid; g < PSM_VI_G; g += PSM_VI_THREADS) part += pmdi_fixlog_sL(gsz[g], T);
     for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
     if (lane == 0) atomicAdd(&s_obj, (unsigned long long)part);
     __syncthreads();

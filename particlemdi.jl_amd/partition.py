@@ -174,19 +174,12 @@ def _pack_rows(dev, st, t, is_bytes, offset, R, n, ld, G):
     return out, pairs, hl, nclust.astype(np.int64)
 
 
-def partition_distances(candidates, draws, orderby=0, max_bytes=1 << 30):
-    """Every candidate clustering against every sampled clustering, on the MI355X.  candidates: (B, n) integers of any value,
-    renumbered by first appearance; at most 255 distinct labels each (ValueError otherwise).  draws: a CUDA int32 (or uint8)
-    tensor (C, K, n), the resident layout of pmdi_pooled(..., final_allocations=True), or a uint8 / integer array (S, K, n) as
-    read_allocations gives; labels 0..254.  orderby = k (1-based) takes draws[:, k - 1, :], read in place; orderby = 0 takes all
-    C K rows in (chain, dataset) order.  The candidates are processed in slabs so that the two B x R int64 device buffers stay
-    under max_bytes.  Returns PartitionDistances.  There is no CPU path: without a device this raises."""
-    import ctypes as C
+def _packed_draws(draws, Cn, K, n, orderby, who):
+    """The draws that _checked_draws passed, as the bytes the kernels read: (device, stream, bytes (R, np) on the device,
+    pairs, hl, nclust of every row, R, Gd).  The label range is checked before any device use; a resident tensor is read in
+    place."""
     import torch
-    from ._lib import PARTDIST_GMAX, _check, lib
-    who = "partition_distances"
-    draws, Cn, K, n, rows = _checked_draws(draws, orderby, who)
-    cand, Gc = _checked_candidates(candidates, n, who)
+    from ._lib import PARTDIST_GMAX
     if not isinstance(draws, torch.Tensor):             # a host array: bytes as they are, anything else through int32
         if draws.size and (draws.min() < 0 or draws.max() >= PARTDIST_GMAX):
             raise ValueError(f"{who}: draw labels must lie in 0..{PARTDIST_GMAX - 1}")
@@ -208,6 +201,23 @@ def partition_distances(candidates, draws, orderby=0, max_bytes=1 << 30):
     R = Cn if orderby else Cn * K
     d_bytes, pairs_r, hl_r, nc_r = _pack_rows(dev, st, draws, is_bytes, item * (orderby - 1) * n if orderby else 0, R, n,
                                               K * n if orderby else n, Gd)
+    return dev, st, d_bytes, pairs_r, hl_r, nc_r, R, Gd
+
+
+def partition_distances(candidates, draws, orderby=0, max_bytes=1 << 30):
+    """Every candidate clustering against every sampled clustering, on the MI355X.  candidates: (B, n) integers of any value,
+    renumbered by first appearance; at most 255 distinct labels each (ValueError otherwise).  draws: a CUDA int32 (or uint8)
+    tensor (C, K, n), the resident layout of pmdi_pooled(..., final_allocations=True), or a uint8 / integer array (S, K, n) as
+    read_allocations gives; labels 0..254.  orderby = k (1-based) takes draws[:, k - 1, :], read in place; orderby = 0 takes all
+    C K rows in (chain, dataset) order.  The candidates are processed in slabs so that the two B x R int64 device buffers stay
+    under max_bytes.  Returns PartitionDistances.  There is no CPU path: without a device this raises."""
+    import ctypes as C
+    import torch
+    from ._lib import _check, lib
+    who = "partition_distances"
+    draws, Cn, K, n, rows = _checked_draws(draws, orderby, who)
+    cand, Gc = _checked_candidates(candidates, n, who)
+    dev, st, d_bytes, pairs_r, hl_r, nc_r, R, Gd = _packed_draws(draws, Cn, K, n, orderby, who)
     B = cand.shape[0]
     d_cand = torch.from_numpy(cand).to(dev)
     c_bytes, pairs_c, hl_c, nc_c = _pack_rows(dev, st, d_cand, True, 0, B, n, n, Gc)
@@ -254,3 +264,129 @@ def credible_ball(labels, draws, level=0.95, distance="vi", orderby=0):
     return CredibleBall(d, pd.n_clusters_draws, radius, inside, horizontal, upper, lower,
                         (clusterings(horizontal), clusterings(upper), clusterings(lower)), pd.expected(distance)[0], pd.rows,
                         distance, level, pd.n)
+
+
+_LOSSES = {"binder": 0, "vi": 1}
+
+
+def _checked_refine(starts, n, loss, max_sweeps, max_clusters, who):
+    """(slots (B, n) int32, 0.. by first appearance): the rules of refine_expected_loss that need no device."""
+    from ._lib import PARTDIST_GMAX
+    if loss not in _LOSSES:
+        raise ValueError(f"{who}: loss {loss!r} is not 'vi' or 'binder'")
+    if int(max_sweeps) < 1:
+        raise ValueError(f"{who}: max_sweeps must be at least 1")
+    if not 1 <= int(max_clusters) <= PARTDIST_GMAX:
+        raise ValueError(f"{who}: max_clusters={max_clusters} is outside 1..{PARTDIST_GMAX}")
+    arr = _host_integers(starts, who, "starts")
+    if arr.ndim != 2 or arr.shape[0] < 1 or arr.shape[1] != n:
+        raise ValueError(f"{who}: starts must be (B, {n}), not {tuple(arr.shape)}")
+    slots, distinct = _first_appearance(arr, 0)
+    if distinct.max() > int(max_clusters):
+        raise ValueError(f"{who}: a start has {int(distinct.max())} distinct labels, max_clusters={int(max_clusters)}")
+    return slots.astype(np.int32)
+
+
+def _refine(starts, draws, loss, orderby, max_sweeps, max_clusters, max_bytes, who):
+    """refine_expected_loss, and with it the constant that turns F into the sum of the distances over the draws."""
+    import ctypes as C
+    import torch
+    from ._lib import _check, _ptr, lib
+    draws, Cn, K, n, rows = _checked_draws(draws, orderby, who)
+    slots = _checked_refine(starts, n, loss, max_sweeps, max_clusters, who)
+    R = Cn if int(orderby) else Cn * K
+    if R > 1 << 24 or R * n >= 1 << 28:
+        raise ValueError(f"{who}: {R} draw rows of n={n}: at most 2^24 rows and R n < 2^28 fit")
+    dev, st, d_bytes, pairs_r, hl_r, _, R, Gd = _packed_draws(draws, Cn, K, n, orderby, who)
+    B, gcap = slots.shape[0], int(max_clusters)
+    Gp = 1 << (gcap - 1).bit_length()
+    slab = int(max(1, int(max_bytes) // (2 * R * Gd * Gp)))
+    d_start = torch.from_numpy(slots).to(dev)
+    d_out = torch.empty((B, n), dtype=torch.int32, device=dev)
+    moves, marginal, joint = (np.zeros(B, dtype=np.int64) for _ in range(3))
+    sweeps, converged = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    for at in range(0, B, slab):
+        m = min(slab, B - at)
+        _check(lib().pmdi_partition_refine_device(
+            dev.index or 0, C.c_void_p(d_bytes.data_ptr()), R, Gd, n, C.c_void_p(d_start.data_ptr() + 4 * at * n), m, n, gcap,
+            _LOSSES[loss], int(max_sweeps), C.c_void_p(d_out.data_ptr() + 4 * at * n), _ptr(moves[at:at + m]), _ptr(sweeps[at:at + m]),
+            _ptr(converged[at:at + m]), _ptr(marginal[at:at + m]), _ptr(joint[at:at + m]), C.c_void_p(st.cuda_stream)))
+    const = sum((hl_r if loss == "vi" else pairs_r).tolist())
+    F = [R * a - 2 * j for a, j in zip(marginal.tolist(), joint.tolist())]
+    den = R * (n << _FR) if loss == "vi" else R
+    labels, _ = _first_appearance(d_out.cpu().numpy(), 1)
+    info = {"moves": moves, "sweeps": sweeps.astype(np.int64), "converged": converged != 0,
+            "objective": np.array(F, dtype=np.int64), "expected": np.array([(f + const) / den for f in F], dtype=np.float64)}
+    return labels, info, const, den
+
+
+def refine_expected_loss(starts, draws, loss="vi", orderby=0, max_sweeps=64, max_clusters=64, max_bytes=1 << 30):
+    """A coordinate descent of the Monte-Carlo posterior expected loss itself -- the mean over the draws of the variation of
+    information (loss="vi") or of Binder's loss (loss="binder") -- from each start clustering, on the MI355X
+    (pmdi_partition_refine_device; the objective, the visiting order and the tie rule are in include/pmdi_hip.h).
+    refine_allocations(loss="vi") descends the Jensen bound of this quantity; this descends the quantity partition_distances
+    reports.  Integer gains: the same result on every run.  draws and orderby as in partition_distances (the resident tensor is
+    read in place); at most 2^24 rows, R n < 2^28.  starts: (B, n) integers of any value, renumbered by first appearance; more
+    distinct labels than max_clusters (1..255, the slots a clustering may grow to), ValueError.  The starts go to the device in
+    slabs that keep their contingency tables (2 R Gd Gp bytes per start, Gp = the power of two >= max_clusters) under max_bytes,
+    one start per slab at the least.  Returns (labels, info): labels int64 (B, n) renumbered 1.. by first appearance as cutree
+    does; info = {"moves", "sweeps": int64 (B,), "converged": bool (B,), the last sweep made no move, "objective": int64 (B,), the
+    integer F of the labels returned, "expected": float64 (B,), the expected loss in bits ("vi") or pairs ("binder"), equal to
+    PartitionDistances.expected(loss) of the same labels bit for bit}.  There is no CPU path."""
+    labels, info, _, _ = _refine(starts, draws, loss, orderby, max_sweeps, max_clusters, max_bytes, "refine_expected_loss")
+    return labels, info
+
+
+def minimise_expected_loss(psm, draws, k=range(2, 21), linkage=("ward",), orderby=0, loss="vi", draw_starts=0, max_sweeps=64,
+                           max_clusters=64):
+    """A search for the clustering of least expected loss against the draws.  The starts are the cuts k of every linkage of the
+    PSM's dendrogram, formed exactly as in search_consensus_allocation, then the first draw_starts draw rows in row order; a
+    start with more than max_clusters clusters is skipped.  Every start is refined by refine_expected_loss, and all candidates
+    -- the starts, then their refined forms in the same order -- are compared on the integer sum of their distances to the
+    draws: the lowest wins, the earliest among equals.  Returns (labels, table): the winner (int64 labels 1..) and the rows
+    (source, linkage, k, n_clusters, expected, moves, converged) in candidate order; source is "cut", "draw", "cut_refined" or
+    "draw_refined"; a draw has linkage None and its row index as k; an unrefined candidate has moves 0 and converged None.
+    There is no CPU path."""
+    import torch
+    from .psm import PsmCounts, _which_matrix, cutree, hclust, psm_distance_device
+    who = "minimise_expected_loss"
+    if loss not in _LOSSES:
+        raise ValueError(f"{who}: loss {loss!r} is not 'vi' or 'binder'")
+    if not isinstance(psm, PsmCounts):
+        raise ValueError(f"{who} needs a PsmCounts (the device-resident counts)")
+    which = _which_matrix(psm, orderby, who)
+    n = psm.counts.shape[1]
+    draws, _, _, n_draws, draw_rows = _checked_draws(draws, orderby, who)
+    if n_draws != n:
+        raise ValueError(f"{who}: the draws hold n={n_draws}, the counts n={n}")
+    _checked_refine(np.zeros((1, n), dtype=np.int64), n, loss, max_sweeps, max_clusters, who)
+    linkages = [linkage] if isinstance(linkage, str) else list(linkage)
+    ks = sorted({int(x) for x in ([k] if np.isscalar(k) else k) if 1 <= int(x) <= n})
+    draw_starts = min(max(int(draw_starts), 0), len(draw_rows))
+    if (not linkages or not ks) and not draw_starts:
+        raise ValueError(f"{who}: no start (no linkage, or no k in 1..n, and no draw)")
+    cand, rows = [], []
+    for lk in linkages:
+        hc = hclust(psm_distance_device(psm.counts, psm.S, which), lk, overwrite=True)
+        for kk in ks:
+            cand.append(cutree(hc, k=kk))
+            rows.append(("cut", lk, kk))
+    for at, (chain, dataset) in enumerate(draw_rows[:draw_starts].tolist()):
+        row = draws[chain, dataset]
+        cand.append(np.asarray(row.cpu() if isinstance(row, torch.Tensor) else row).astype(np.int64))
+        rows.append(("draw", None, at))
+    cand, distinct = _first_appearance(np.stack(cand), 1)
+    keep = np.flatnonzero(distinct <= int(max_clusters))
+    if not len(keep):
+        raise ValueError(f"{who}: every start has more than max_clusters={int(max_clusters)} clusters")
+    cand, rows = cand[keep], [rows[b] for b in keep]
+    pd = partition_distances(cand, draws, orderby=orderby)
+    refined, info, const, den = _refine(cand, draws, loss, orderby, max_sweeps, max_clusters, 1 << 30, who)
+    totals = [sum(row) for row in (pd.vi_fixed if loss == "vi" else pd.binder_pairs).tolist()] + [f + const for f in info["objective"].tolist()]
+    everyone = np.concatenate([cand, refined])
+    best = min(range(len(totals)), key=lambda b: (totals[b], b))
+    B = len(cand)
+    table = [(src if b < B else src + "_refined", lk, kk, int(len(np.unique(everyone[b]))), totals[b] / den,
+              0 if b < B else int(info["moves"][b - B]), None if b < B else bool(info["converged"][b - B]))
+             for b, (src, lk, kk) in enumerate(rows + rows)]
+    return everyone[best].astype(np.int64), table
