@@ -887,7 +887,44 @@ int pmdi_gibbs_run4(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
  * get_coupled / merge_coupled / last_coupled: PMDI_E_STATE on an uncoupled accumulator.  get_coupled copies the four joint sums
  *   (pmdi_predict_get the other three).  merge_coupled takes all seven DEVICE arrays of another coupled accumulator of the same
  *   shape; lpd_joint_sum merges like lpd_sum.  last_coupled (keep_last only): g [C][K][m][N], Z [C][m], qj [C][K][m][N] Int32, fq
- *   [C][G][m] Int32, incj [C][m], logZ0 [C], Z0 [C] of the last add.  reset zeroes the joint sums too. */
+ *   [C][G][m] Int32, incj [C][m], logZ0 [C], Z0 [C] of the last add.  reset zeroes the joint sums too.
+ *
+ * Masked add (pmdi_predict_create_masked).  A new observation measured in some features only: observed[k] is a host matrix laid
+ * out like the new rows of dataset k (column-major, ld = m, one byte per entry, non-zero = observed); a NULL entry, or observed
+ * = NULL, means dataset k is fully observed.  The clusters are rebuilt exactly as above -- the mask never touches the training
+ * data -- and step 2 becomes calc_logprob(new row j, cluster l, flags .& observed[k][j][.]): every term of calc_logprob belongs
+ * to one feature in all three kinds (gaussian_cluster.jl:37-50, categorical_cluster.jl:29-41, negbinom_cluster.jl:22-41), so
+ * leaving an unobserved feature's terms out marginalises it exactly.  With on(f) = flag[c][f] && observed[k][j][f]:
+ *     leading term   Gaussian (double)nobs * gtab[cn], nobs = the number of f with on(f);  Categorical -acc, acc the sum over the
+ *                    f with on(f) in ascending order of the per-feature constant;  NegBinom 0
+ *     feature terms  in ascending feature order, those of the f without on(f) skipped; the same expressions as step 2
+ *   A row with nothing observed in dataset k has lp = 0 for every label: its proposal is Pi, the g of a coupled add is Pi bit
+ *   for bit, and its joint weights in that dataset come from Phi and the other datasets alone.  The value of an unobserved entry
+ *   is never read, by a kernel or by create's range checks: it may be NaN, level 0 or negative.  An accumulator made by
+ *   pmdi_predict_create / _create_coupled runs the code it always ran; one made here with all masks NULL and impute = 0 too.
+ *   create_masked: create's checks (coupled != 0: create_coupled's), on the observed entries only.  It returns the same
+ *   pmdi_predict: add_gibbs, add_arrays(_coupled), merge(_coupled), get(_coupled), last(_coupled), reset, destroy and
+ *   pmdi_gibbs_run5 work on it unchanged.
+ * Imputation sums (impute != 0; Gaussian datasets).  Step 1 also keeps the location of every label's cluster, mu[c][k][l][f] =
+ *   Sigma / (cn + 0.001) (gaussian_cluster.jl:60; an empty label: 0; a feature the chain has off: not used), row length Dmax =
+ *   the largest D of a Gaussian dataset.  After step 3, for every Gaussian dataset k, new row j and feature f, OBSERVED OR NOT
+ *   (the observed entries give fitted values for residual checks), off_k = the features of the datasets before k:
+ *       e = 0.0;  for l = 0 .. N-1:  e = e + (double)q[c][k][j][l] * mu[c][k][l][f]       (a product and a sum per label, never fused)
+ *       loc_sum[j][off_k + f] = loc_sum[j][off_k + f] + e         for the chains c in ascending order that have flag[c][off_k + f]
+ *                                                                 on (flags NULL: every chain)
+ *       flag_on[off_k + f] += the number of those chains
+ *   A coupled accumulator sums loc_joint_sum the same way from qj.  loc_sum, loc_joint_sum [m][sum D] Float64, flag_on [sum D]
+ *   Int64; the columns of the other kinds stay 0.  One owner per entry, bit-defined given q and mu.  On the host, with the
+ *   reference's null cluster for a feature a chain has off (every observation in one cluster, src/pmdi.jl:353-365), whose
+ *   location null_f = (sum_i x[i][f], rows ascending) / (n + 0.001) does not depend on the chain:
+ *       fitted[j][f] = (loc_sum[j][f] / 2^20 + (T C - flag_on[f]) * null_f) / (T C)
+ *   Device memory: mu 8 Cb K N Dmax bytes (8 C K N Dmax with keep_last), the sums 8 m sum D each; both are capped by
+ *   PMDI_PREDICT_MAX_BYTES (PMDI_E_ARG).
+ * get_imputed: PMDI_E_STATE without impute, or for loc_joint_sum on an uncoupled accumulator; SYNCHRONISES `stream` and copies to
+ *   the host arrays that are not NULL.  merge_imputed: DEVICE arrays of another accumulator of the same shape, ours + theirs
+ *   (loc_joint_sum: NULL exactly when uncoupled); it is called beside pmdi_predict_merge(_coupled), which alone advances T.
+ *   last_imputed (keep_last and impute, else PMDI_E_STATE): synchronises the device and copies the last add's mu
+ *   [C][K][N][Dmax] to the host; the rows of the other kinds are 0.  reset zeroes the imputation sums too. */
 #define PMDI_PREDICT_MMAX 1048576
 #define PMDI_PREDICT_MAX_BYTES 34359738368LL /* 2^35 */
 typedef struct pmdi_predict pmdi_predict;
@@ -907,6 +944,12 @@ int pmdi_predict_merge_coupled(pmdi_predict *a, const int64_t *sim, const int64_
                                const int64_t *new_cluster_joint, const int64_t *fused_new, const double *lpd_joint_sum, int64_t T, void *stream);
 int pmdi_predict_get_coupled(pmdi_predict *a, int64_t *sim_joint, int64_t *new_cluster_joint, int64_t *fused_new, double *lpd_joint_sum, void *stream);
 int pmdi_predict_last_coupled(pmdi_predict *a, double *g, double *Z, int32_t *qj, int32_t *fq, double *incj, double *logZ0, double *Z0);
+int pmdi_predict_create_masked(pmdi_handle *h, int64_t m, const pmdi_dataset *new_rows, const uint8_t *const *observed, int32_t keep_last,
+                               int32_t coupled, int32_t impute, pmdi_predict **out);
+int pmdi_predict_get_imputed(pmdi_predict *a, double *loc_sum, double *loc_joint_sum /* NULL if uncoupled */, int64_t *flag_on, void *stream);
+int pmdi_predict_merge_imputed(pmdi_predict *a, const double *loc_sum, const double *loc_joint_sum /* NULL if uncoupled */,
+                               const int64_t *flag_on, void *stream);
+int pmdi_predict_last_imputed(pmdi_predict *a, double *mu /* host [C][K][N][Dmax] */);
 
 /* pmdi_gibbs_run4 with the fifth accumulator: after every retained local iteration acc, summ, fus, mix, then pred get their add;
  * any may be NULL, and pmdi_gibbs_run4(g, ..., mix, stream) is pmdi_gibbs_run5(g, ..., mix, NULL, stream). */

@@ -24,4 +24,5 @@ from .summary import (  # noqa: F401,E402
     PosteriorSummary, SummaryAccumulator, get_feature_select_probs, get_nclust, get_phi,
 )
 from .mixing import MixingAccumulator, MixingSummary  # noqa: F401,E402
-from .predict import CoupledPredictiveCounts, PredictiveAccumulator, PredictiveCounts  # noqa: F401,E402
+from .predict import (  # noqa: F401,E402
+    CoupledPredictiveCounts, PredictiveAccumulator, PredictiveCounts, check_new_rows, observed_masks)

@@ -56,6 +56,7 @@ EXPORTS = [
     "pmdi_predict_add_arrays", "pmdi_predict_merge", "pmdi_predict_get", "pmdi_predict_counts", "pmdi_predict_last", "pmdi_gibbs_run5",
     "pmdi_predict_create_coupled", "pmdi_predict_add_arrays_coupled", "pmdi_predict_merge_coupled", "pmdi_predict_get_coupled",
     "pmdi_predict_last_coupled",
+    "pmdi_predict_create_masked", "pmdi_predict_get_imputed", "pmdi_predict_merge_imputed", "pmdi_predict_last_imputed",
     "pmdi_partition_rows_device", "pmdi_partition_distance_device", "pmdi_partition_refine_device",
 ]
 
@@ -291,6 +292,14 @@ def lib():
     L.pmdi_predict_get_coupled.argtypes = [vp, vp, vp, vp, vp, vp]
     L.pmdi_predict_last_coupled.restype = C.c_int
     L.pmdi_predict_last_coupled.argtypes = [vp] + [vp] * 7
+    L.pmdi_predict_create_masked.restype = C.c_int
+    L.pmdi_predict_create_masked.argtypes = [vp, i64, C.POINTER(_Dataset), C.POINTER(vp), i32, i32, i32, C.POINTER(vp)]
+    L.pmdi_predict_get_imputed.restype = C.c_int
+    L.pmdi_predict_get_imputed.argtypes = [vp, vp, vp, vp, vp]
+    L.pmdi_predict_merge_imputed.restype = C.c_int
+    L.pmdi_predict_merge_imputed.argtypes = [vp, vp, vp, vp, vp]
+    L.pmdi_predict_last_imputed.restype = C.c_int
+    L.pmdi_predict_last_imputed.argtypes = [vp, vp]
     L.pmdi_mixing_create.restype = C.c_int
     L.pmdi_mixing_create.argtypes = [i32, i32, i32, i32, i64, i32, C.POINTER(vp)]
     L.pmdi_mixing_destroy.argtypes = [vp]
@@ -513,6 +522,10 @@ class Sweeper(_Handle):
         self.split = bool(L.pmdi_is_split(h))
         self.settled = bool(L.pmdi_settled_kernel(h, None))
         self.npairs = max(1, self.K * (self.K - 1) // 2)
+        # the Gaussian column sums, rows added in ascending order (cumsum is sequential): what predict.PredictiveAccumulator(impute=True)
+        # needs of the training data, the location of the reference's null cluster; zeros for the other kinds
+        self.column_sums = [np.array([np.cumsum(x[:, q])[-1] for q in range(x.shape[1])]) if kind == GAUSSIAN else np.zeros(x.shape[1])
+                            for x, kind in zip(self._keep, self.kinds)]
         self._keep = None  # the library copied the data
 
     def sweep(self, it, s, order_obs, n1, Pi, Phi, flags=None, lw_init=None, trace=False):

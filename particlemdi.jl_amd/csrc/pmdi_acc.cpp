@@ -80,6 +80,9 @@ struct pmdi_predict {
     CoupledArgs ca{};                    // the coupled stage's tables, stage buffers and sums
     char *slab2 = nullptr;               // what reset zeroes of a coupled accumulator: sim_joint, new_cluster_joint, fused_new, lpd_joint_sum
     size_t state2_bytes = 0;
+    bool impute = false;                 // created by pmdi_predict_create_masked with impute: every add also sums the imputed locations
+    char *slab3 = nullptr;               // what reset zeroes of an imputing accumulator: loc_sum, loc_joint_sum (coupled), flag_on
+    size_t state3_bytes = 0;
 };
 
 namespace {
@@ -633,13 +636,16 @@ int pmdi_predict_destroy(pmdi_predict *a)
     (void)hipDeviceSynchronize();
     if (a->slab) (void)hipFree(a->slab);
     if (a->slab2) (void)hipFree(a->slab2);
+    if (a->slab3) (void)hipFree(a->slab3);
     for (void *p : a->owned) (void)hipFree(p);
     if (a->h && a->h->children > 0) a->h->children -= 1;      // (the handle outlives its children: pmdi_destroy refuses otherwise)
     delete a;
     return PMDI_OK;
 }
 
-static int predict_create_any(pmdi_handle *h, int64_t m, const pmdi_dataset *new_rows, int32_t keep_last, bool coupled, pmdi_predict **out)
+// observed: null, or K host masks (column-major, ld = m, one byte per entry; a null entry: the dataset is fully observed)
+static int predict_create_any(pmdi_handle *h, int64_t m, const pmdi_dataset *new_rows, const uint8_t *const *observed, int32_t keep_last,
+                              bool coupled, bool impute, pmdi_predict **out)
 {
     if (!h || !new_rows || !out) return fail(PMDI_E_ARG, "null argument");
     *out = nullptr;
@@ -658,13 +664,29 @@ static int predict_create_any(pmdi_handle *h, int64_t m, const pmdi_dataset *new
     if (q_bytes > (long double)PMDI_PREDICT_MAX_BYTES || sim_bytes > (long double)PMDI_PREDICT_MAX_BYTES)
         return fail(PMDI_E_ARG, "m=%lld: the weights (4 C K m N = %.0Lf bytes) or sim (8 K m n = %.0Lf bytes) pass %lld bytes", (long long)m,
                     q_bytes, sim_bytes, (long long)PMDI_PREDICT_MAX_BYTES);
-    // the new rows, row-major like the training data, checked before the device is touched
+    int Dmax = 1;                        // row length of mu: the largest D of a Gaussian dataset
+    for (int k = 0; k < K; ++k)
+        if (h->ds[k].kind == K_GAUSSIAN && h->ds[k].D > Dmax) Dmax = h->ds[k].D;
+    if (impute) {
+        const long double mu_bytes = 8.0L * C * K * N * (long double)Dmax, loc_bytes = 8.0L * (long double)m * h->sumD;
+        if (mu_bytes > (long double)PMDI_PREDICT_MAX_BYTES || loc_bytes > (long double)PMDI_PREDICT_MAX_BYTES)
+            return fail(PMDI_E_ARG, "m=%lld: the locations (8 C K N Dmax = %.0Lf bytes) or the imputation sums (8 m sumD = %.0Lf bytes) pass %lld bytes",
+                        (long long)m, mu_bytes, loc_bytes, (long long)PMDI_PREDICT_MAX_BYTES);
+    }
+    // the new rows, row-major like the training data, checked before the device is touched; an unobserved entry is not read
     std::vector<double> xf[PMDI_KMAX_I];
     std::vector<int> xi[PMDI_KMAX_I];
+    std::vector<unsigned char> ob[PMDI_KMAX_I];
     long long lg_len[PMDI_KMAX_I] = {};
     for (int k = 0; k < K; ++k) {
         const pmdi_dataset &src = new_rows[k];
         const DsetDev &d = h->ds[k];
+        const uint8_t *mask = observed ? observed[k] : nullptr;
+        if (mask) {
+            ob[k].resize((size_t)m * d.D);
+            for (long long j = 0; j < m; ++j)
+                for (int q = 0; q < d.D; ++q) ob[k][(size_t)j * d.D + q] = mask[(size_t)q * m + j] != 0;
+        }
         if (src.kind != d.kind || src.D != d.D)
             return fail(PMDI_E_ARG, "new rows of dataset %d: kind=%d D=%d, the handle has kind=%d D=%d", k, src.kind, src.D, d.kind, d.D);
         if (src.ld < m) return fail(PMDI_E_ARG, "new rows of dataset %d: ld=%lld < m=%lld", k, (long long)src.ld, (long long)m);
@@ -673,13 +695,14 @@ static int predict_create_any(pmdi_handle *h, int64_t m, const pmdi_dataset *new
             if (!src.xf) return fail(PMDI_E_ARG, "new rows of dataset %d: xf is null", k);
             xf[k].resize((size_t)m * D);
             for (long long j = 0; j < m; ++j)
-                for (int q = 0; q < D; ++q) xf[k][(size_t)j * D + q] = src.xf[(size_t)q * src.ld + j];
+                for (int q = 0; q < D; ++q) xf[k][(size_t)j * D + q] = (mask && !ob[k][(size_t)j * D + q]) ? 0.0 : src.xf[(size_t)q * src.ld + j];
         } else {
             if (!src.xi) return fail(PMDI_E_ARG, "new rows of dataset %d: xi is null", k);
             xi[k].resize((size_t)m * D);
             long long vmax = 0;
             for (long long j = 0; j < m; ++j)
                 for (int q = 0; q < D; ++q) {
+                    if (mask && !ob[k][(size_t)j * D + q]) { xi[k][(size_t)j * D + q] = 0; continue; }
                     const long long v = src.xi[(size_t)q * src.ld + j];
                     if (d.kind == K_CATEGORICAL && (v < 1 || v > d.L))      // (the reference's counts[x, q] would be out of bounds)
                         return fail(PMDI_E_DATA, "new rows of dataset %d: categorical level %lld outside 1..%d", k, v, d.L);
@@ -711,6 +734,7 @@ static int predict_create_any(pmdi_handle *h, int64_t m, const pmdi_dataset *new
         p.ds[k] = h->ds[k];
         if (p.ds[k].kind == K_GAUSSIAN) rc = predict_upload(a, xf[k], &p.nxf[k]);
         else rc = predict_upload(a, xi[k], &p.nxi[k]);
+        if (!rc && !ob[k].empty()) { rc = predict_upload(a, ob[k], &p.obs[k]); p.masked = 1; }
         if (!rc && p.ds[k].kind == K_NEGBINOM) {
             std::vector<double> lg((size_t)lg_len[k]);
             for (long long i = 0; i < lg_len[k]; ++i) lg[i] = lgamma((double)i);      // the call pmdi_create makes: shared entries are bit-equal
@@ -724,6 +748,13 @@ static int predict_create_any(pmdi_handle *h, int64_t m, const pmdi_dataset *new
     if (!rc) rc = predict_alloc(a, &p.qnew, CKm);
     if (!rc) rc = predict_alloc(a, &p.cn, (size_t)C * K * N);
     if (!rc) rc = predict_alloc(a, &p.lp, (size_t)(a->keep_last ? C : p.Cb) * K * m * N);
+    p.Dmax = Dmax;
+    if (!rc && impute) {
+        const size_t mu_count = (size_t)(a->keep_last ? C : p.Cb) * K * N * Dmax;
+        p.masked = 1;
+        rc = predict_alloc(a, &p.mu, mu_count);
+        if (!rc && hipMemset(p.mu, 0, mu_count * 8) != hipSuccess) rc = fail(PMDI_E_DEVICE, "hipMemset failed");      // (the rows of the other kinds stay 0)
+    }
     if (rc) { pmdi_predict_destroy(a); return rc; }
     a->state_bytes = (Km * n + 2 * Km + 1) * 8;
     hipError_t e = hipMalloc((void **)&a->slab, a->state_bytes);
@@ -757,18 +788,35 @@ static int predict_create_any(pmdi_handle *h, int64_t m, const pmdi_dataset *new
         q.fused_new = q.new_cluster_joint + Km;
         q.lpd_joint_sum = (double *)(q.fused_new + Gm);
     }
+    if (impute) {
+        const size_t mD = (size_t)m * h->sumD;
+        a->impute = true;
+        a->state3_bytes = ((coupled ? 2 : 1) * mD + (size_t)h->sumD) * 8;
+        e = hipMalloc((void **)&a->slab3, a->state3_bytes);
+        if (e != hipSuccess) { a->slab3 = nullptr; pmdi_predict_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", a->state3_bytes, hipGetErrorString(e)); }
+        if (hipMemset(a->slab3, 0, a->state3_bytes) != hipSuccess) { pmdi_predict_destroy(a); return fail(PMDI_E_DEVICE, "hipMemset failed"); }
+        p.loc_sum = (double *)a->slab3;
+        p.loc_joint_sum = coupled ? p.loc_sum + mD : nullptr;
+        p.flag_on = (long long *)(p.loc_sum + (coupled ? 2 : 1) * mD);
+    }
     *out = a;
     return PMDI_OK;
 }
 
 int pmdi_predict_create(pmdi_handle *h, int64_t m, const pmdi_dataset *new_rows, int32_t keep_last, pmdi_predict **out)
 {
-    return predict_create_any(h, m, new_rows, keep_last, false, out);
+    return predict_create_any(h, m, new_rows, nullptr, keep_last, false, false, out);
 }
 
 int pmdi_predict_create_coupled(pmdi_handle *h, int64_t m, const pmdi_dataset *new_rows, int32_t keep_last, pmdi_predict **out)
 {
-    return predict_create_any(h, m, new_rows, keep_last, true, out);
+    return predict_create_any(h, m, new_rows, nullptr, keep_last, true, false, out);
+}
+
+int pmdi_predict_create_masked(pmdi_handle *h, int64_t m, const pmdi_dataset *new_rows, const uint8_t *const *observed, int32_t keep_last,
+                               int32_t coupled, int32_t impute, pmdi_predict **out)
+{
+    return predict_create_any(h, m, new_rows, observed, keep_last, coupled != 0, impute != 0, out);
 }
 
 int pmdi_predict_reset(pmdi_predict *a, void *stream)
@@ -777,6 +825,7 @@ int pmdi_predict_reset(pmdi_predict *a, void *stream)
     HIP_TRY(hipSetDevice(a->device));
     HIP_TRY(hipMemsetAsync(a->slab, 0, a->state_bytes, (hipStream_t)stream));
     if (a->slab2) HIP_TRY(hipMemsetAsync(a->slab2, 0, a->state2_bytes, (hipStream_t)stream));
+    if (a->slab3) HIP_TRY(hipMemsetAsync(a->slab3, 0, a->state3_bytes, (hipStream_t)stream));
     a->T = 0;
     return PMDI_OK;
 }
@@ -926,6 +975,47 @@ int pmdi_predict_last_coupled(pmdi_predict *a, double *g, double *Z, int32_t *qj
     if (incj) HIP_TRY(hipMemcpy(incj, q.incj, Cm * 8, hipMemcpyDeviceToHost));
     if (logZ0) HIP_TRY(hipMemcpy(logZ0, q.logZ0, (size_t)p.C * 8, hipMemcpyDeviceToHost));
     if (Z0) HIP_TRY(hipMemcpy(Z0, q.Z0, (size_t)p.C * 8, hipMemcpyDeviceToHost));
+    return PMDI_OK;
+}
+
+int pmdi_predict_get_imputed(pmdi_predict *a, double *loc_sum, double *loc_joint_sum, int64_t *flag_on, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    if (!a->impute) return fail(PMDI_E_STATE, "pmdi_predict_get_imputed: the accumulator was created without impute");
+    if (loc_joint_sum && !a->coupled) return fail(PMDI_E_STATE, "pmdi_predict_get_imputed: loc_joint_sum needs a coupled accumulator");
+    HIP_TRY(hipSetDevice(a->device));
+    hipStream_t st = (hipStream_t)stream;
+    const PredictArgs &p = a->pa;
+    const size_t mD = (size_t)p.m * p.sumD;
+    if (loc_sum) HIP_TRY(hipMemcpyAsync(loc_sum, p.loc_sum, mD * 8, hipMemcpyDeviceToHost, st));
+    if (loc_joint_sum) HIP_TRY(hipMemcpyAsync(loc_joint_sum, p.loc_joint_sum, mD * 8, hipMemcpyDeviceToHost, st));
+    if (flag_on) HIP_TRY(hipMemcpyAsync(flag_on, p.flag_on, (size_t)p.sumD * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PMDI_OK;
+}
+
+int pmdi_predict_merge_imputed(pmdi_predict *a, const double *loc_sum, const double *loc_joint_sum, const int64_t *flag_on, void *stream)
+{
+    if (!a || !loc_sum || !flag_on) return fail(PMDI_E_ARG, "null argument");
+    if (!a->impute) return fail(PMDI_E_STATE, "pmdi_predict_merge_imputed: the accumulator was created without impute");
+    if (a->coupled != (loc_joint_sum != nullptr))
+        return fail(a->coupled ? PMDI_E_ARG : PMDI_E_STATE, "pmdi_predict_merge_imputed: loc_joint_sum goes with a coupled accumulator, and only with one");
+    HIP_TRY(hipSetDevice(a->device));
+    hipError_t e = pmdi_launch_predict_merge_imputed(a->pa, loc_sum, loc_joint_sum, (const long long *)flag_on, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "predict-merge launch: %s", hipGetErrorString(e));
+    return PMDI_OK;
+}
+
+int pmdi_predict_last_imputed(pmdi_predict *a, double *mu)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    if (!a->impute) return fail(PMDI_E_STATE, "pmdi_predict_last_imputed: the accumulator was created without impute");
+    if (!a->keep_last) return fail(PMDI_E_STATE, "pmdi_predict_last_imputed: the accumulator was created without keep_last");
+    if (a->T < 1) return fail(PMDI_E_STATE, "pmdi_predict_last_imputed: nothing was added yet");
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const PredictArgs &p = a->pa;
+    if (mu) HIP_TRY(hipMemcpy(mu, p.mu, (size_t)p.C * p.K * p.N * p.Dmax * 8, hipMemcpyDeviceToHost));
     return PMDI_OK;
 }
 

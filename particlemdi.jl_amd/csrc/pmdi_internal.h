@@ -359,6 +359,14 @@ struct PredictArgs {
     long long *sim;             // [K][m][n]
     long long *new_cluster;     // [K][m]
     double *lpd_sum;            // [K][m]
+    // masked placement and imputation (pmdi_predict_create_masked); zero / null in every other accumulator
+    int masked;                 // 1: the weights kernel's masked variant runs (a mask was given, or mu is wanted)
+    int Dmax;                   // row length of mu: the largest D of a Gaussian dataset (at least 1)
+    const unsigned char *obs[PMDI_KMAX_I];      // [m][D] 1 = observed, or null: the dataset is fully observed
+    double *mu;                 // [Cb][K][N][Dmax]  location of every Gaussian label's cluster (with keep_last: of all chains), or null
+    double *loc_sum;            // [m][sumD]  imputation sums of the per-dataset weights, or null
+    double *loc_joint_sum;      // [m][sumD]  ... of the joint weights (coupled and impute), or null
+    long long *flag_on;         // [sumD]     (add, chain) pairs with the feature on
 };
 // What a coupled add has beside PredictArgs (pmdi_predict_coupled.hip): the chains' Phi, the per-chain subset tables, the stage
 // buffers of the joint placement and the four joint sums.
@@ -383,6 +391,8 @@ struct CoupledArgs {
 hipError_t pmdi_launch_predict_add(const PredictArgs &a, hipStream_t stream, const CoupledArgs *cp = nullptr);
 // sim += sim_b, new_cluster += nc_b, lpd_sum = lpd_sum + lpd_b (device arrays; lpd_b null: lpd_sum is left alone)
 hipError_t pmdi_launch_predict_merge(const PredictArgs &a, const long long *sim_b, const long long *nc_b, const double *lpd_b, hipStream_t stream);
+// loc_sum = loc_sum + loc_b, loc_joint_sum = loc_joint_sum + locj_b (null: left alone), flag_on += flag_b (device arrays)
+hipError_t pmdi_launch_predict_merge_imputed(const PredictArgs &a, const double *loc_b, const double *locj_b, const long long *flag_b, hipStream_t stream);
 // pmdi_predict_coupled.hip
 void pmdi_launch_predict_chain_tables(const PredictArgs &a, const CoupledArgs &cp, hipStream_t stream);
 void pmdi_launch_predict_couple(const PredictArgs &a, const CoupledArgs &cp, int c0, int chains, hipStream_t stream);

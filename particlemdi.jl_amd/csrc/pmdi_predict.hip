@@ -1,5 +1,5 @@
 // pmdi_predict.hip -- one add of the streaming predictive accumulator (include/pmdi_hip.h, pmdi_predict_*): where do m held-out
-// rows fall in the current state of every chain?  Four kernels per add:
+// rows fall in the current state of every chain?  Four kernels per add, five with imputation:
 //   predict_weights_kernel    per (chain, dataset, label): the label's cluster rebuilt from its members in ascending observation
 //                             order under the chain's feature flags (what featsel_label_kernel does with every flag on), then
 //                             calc_logprob of every new row against it, features in ascending order (cluster_logprob_kernel's sums)
@@ -7,6 +7,8 @@
 //                             Phi) as fixed-point weights q, its log increment, and the weight on the sample's empty labels
 //   predict_gather_kernel     sim[k][j][i] += sum over the chains of q[c][k][j][s[c][k][i]]: the hot path, exact integers
 //   predict_reduce_kernel     new_cluster and lpd_sum, one lane per (dataset, new row), chains in order
+//   predict_impute_kernel     (accumulators with imputation) loc_sum[j][f] += sum over the chains of sum_l q[c][k][j][l] * mu[c][k][l][f],
+//                             per batch of chains after its normalise kernel, and once more with the joint weights of a coupled add
 // A coupled add (pmdi_predict_coupled.hip) runs its coupling kernel after every batch's normalise kernel and sends its joint weights
 // through the same gather and reduce kernels (launch_sums).
 // The arithmetic is pmdi_arith.h's and the tables are the host-built ones, so the integer kinds agree with a CPU evaluation bit for
@@ -24,7 +26,16 @@ constexpr int PG_OB = 512;                  // gather tile: observations (two pe
 constexpr int PG_JS = 32;                   // ... times new rows (accumulators per observation)
 constexpr int PG_ROW = PG_JS + 4;           // LDS row stride in dwords: one 16-byte access of padding, rows start 16-byte aligned
 constexpr int PG_WINDOW = 2047;             // chains whose q (<= 2^20 each) one int32 accumulator takes
+constexpr int PI_F = 64;                    // impute tile: features (one per lane of a wave) ...
+constexpr int PI_R = 2;                     // ... times new rows per lane, ...
+constexpr int PI_J = 4 * PI_R;              // ... four waves of them
+constexpr int PI_LC = 32;                   // labels per stage of the impute kernel
+constexpr int PI_MU = PI_LC / 4;            // mu values a lane stages (its feature, every fourth label from its wave's index)
+static_assert(PI_J * PI_LC == 256, "one staged q entry per lane");
 
+// MASKED (pmdi_predict_create_masked): a feature of new row j counts only where obs[k][j][f] is set, the leading term becomes
+// per row, and the Gaussian locations go to a.mu for the imputation sums.  The other instantiation is the code it always was.
+template <bool MASKED>
 __global__ void __launch_bounds__(256) predict_weights_kernel(const PredictArgs a, int c0)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -44,6 +55,8 @@ __global__ void __launch_bounds__(256) predict_weights_kernel(const PredictArgs 
     double *lp = a.lp + (((size_t)(a.lp_all ? c : cb) * K + k) * m) * N + l;      // this label's column: stride N over the new rows
     const double *nxf = a.nxf[k];
     const int *nxi = a.nxi[k];
+    const unsigned char *ob = nullptr;                              // [m][D], null: every entry of the dataset is observed
+    if constexpr (MASKED) ob = a.obs[k];
 
     // the label's size; any label outside 0..N-1 raises the flag (it is a member of no cluster)
     if (tid == 0) s_count = 0;
@@ -63,24 +76,43 @@ __global__ void __launch_bounds__(256) predict_weights_kernel(const PredictArgs 
 
     // what calc_logprob starts from, before its loop over the features: the same for every new row, so one lane forms it (the
     // categorical sum in feature order) and the workgroup reads it back
-    if (tid == 0) {
-        double start = 0.0;
-        if (d.kind == K_GAUSSIAN) {
-            int nflag = 0;
-            for (int q = 0; q < D; ++q) nflag += (fl ? fl[q] != 0 : 1);
-            start = (double)nflag * glob(d.gtab)[cn];
-        } else if (d.kind == K_CATEGORICAL) {
-            double acc = 0.0;
-            for (int q = 0; q < D; ++q) {
-                if (fl && !fl[q]) continue;
-                acc += glob(d.lhtab)[glob(d.maxcol)[q] + 2 * cn];
+    if (MASKED && ob) {                                             // per row: the features that are on and observed
+        const double gt = d.kind == K_GAUSSIAN ? glob(d.gtab)[cn] : 0.0;
+        for (long long j = tid; j < m; j += 256) {
+            const unsigned char *oj = ob + (size_t)j * D;
+            double start = 0.0;
+            if (d.kind == K_GAUSSIAN) {
+                int nobs = 0;
+                for (int q = 0; q < D; ++q) nobs += ((fl ? fl[q] != 0 : true) && oj[q] != 0);
+                start = (double)nobs * gt;
+            } else if (d.kind == K_CATEGORICAL) {
+                double acc = 0.0;
+                for (int q = 0; q < D; ++q) {
+                    if ((fl && !fl[q]) || !oj[q]) continue;
+                    acc += glob(d.lhtab)[glob(d.maxcol)[q] + 2 * cn];
+                }
+                start = -acc;
             }
-            start = -acc;
+            lp[(size_t)j * N] = start;
         }
-        s_start = start;
-    }
-    __syncthreads();
-    {
+    } else {
+        if (tid == 0) {
+            double start = 0.0;
+            if (d.kind == K_GAUSSIAN) {
+                int nflag = 0;
+                for (int q = 0; q < D; ++q) nflag += (fl ? fl[q] != 0 : 1);
+                start = (double)nflag * glob(d.gtab)[cn];
+            } else if (d.kind == K_CATEGORICAL) {
+                double acc = 0.0;
+                for (int q = 0; q < D; ++q) {
+                    if (fl && !fl[q]) continue;
+                    acc += glob(d.lhtab)[glob(d.maxcol)[q] + 2 * cn];
+                }
+                start = -acc;
+            }
+            s_start = start;
+        }
+        __syncthreads();
         const double start = s_start;
         for (long long j = tid; j < m; j += 256) lp[(size_t)j * N] = start;
     }
@@ -149,6 +181,8 @@ __global__ void __launch_bounds__(256) predict_weights_kernel(const PredictArgs 
                 double mu, lam;
                 pmdi_arith::gauss_ml(cn, sg, bt, mu, lam);
                 ((double2 *)tile)[tid] = make_double2(mu, lam);
+                if constexpr (MASKED)
+                    if (a.mu) a.mu[((((size_t)(a.lp_all ? c : cb) * K + k) * N + l) * a.Dmax) + q] = mu;
             }
         } else if (d.kind == K_NEGBINOM) {
             if (tid < dq) ((long long *)tile)[tid] = S;
@@ -159,6 +193,8 @@ __global__ void __launch_bounds__(256) predict_weights_kernel(const PredictArgs 
             for (int qq = 0; qq < dq; ++qq) {
                 const int f = q0 + qq;
                 if (fl && !fl[f]) continue;
+                if constexpr (MASKED)
+                    if (ob && !ob[(size_t)j * D + f]) continue;     // (before the entry is read: it may be anything)
                 if (d.kind == K_GAUSSIAN) {
                     double ta, tb;
                     gauss_terms(glob(nxf)[(size_t)j * D + f], (double)cn, ((const double2 *)tile)[qq], ta, tb);
@@ -301,6 +337,105 @@ __global__ void __launch_bounds__(256) predict_merge_kernel(const PredictArgs a,
     }
 }
 
+// loc[j][off_k + f] += sum over the batch's chains (ascending, where the chain has the feature on) of
+//     e = ((0 + q[c][k][j][0] * mu[c][k][0][f]) + q[c][k][j][1] * mu[c][k][1][f]) + ...       labels ascending, separate multiply and add
+// for the Gaussian datasets.  A workgroup owns PI_J new rows x PI_F features of one dataset: a lane one feature (its wave's lane
+// index) and PI_R rows (its wave's).  A stage is PI_LC labels of one chain: mu [label][feature] and q transposed to [label][row] go
+// through registers into one of two LDS buffers -- the next stage's global reads are in flight while this one is summed, one
+// barrier per stage.  The mu row is read with one conflict-free 8-byte access per lane, the q of the wave's rows with one
+// broadcast.  e and the running sums live in registers across the stages, so no value depends on PI_LC or the tile; every entry
+// of loc has one owner: no atomics.  count: the owners of row tile 0 also add the chains with the feature on to flag_on.
+__global__ void __launch_bounds__(256) predict_impute_kernel(const PredictArgs a, const int *__restrict__ qsrc, double *__restrict__ loc,
+                                                             int c0, int chains, int count)
+{
+    __shared__ __attribute__((aligned(16))) double mus[2][PI_LC][PI_F];
+    __shared__ __attribute__((aligned(16))) int qs[2][PI_LC][PI_J];
+    const int k = blockIdx.z;
+    const DsetDev &d = a.ds[k];
+    const int D = d.D, N = a.N, K = a.K, Dmax = a.Dmax;
+    const int f0 = blockIdx.y * PI_F;
+    if (d.kind != K_GAUSSIAN || f0 >= D) return;                    // (the grid spans the largest Gaussian D; uniform per workgroup)
+    const long long m = a.m, j0 = (long long)blockIdx.x * PI_J;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f = f0 + lane;
+    const long long jr = j0 + wave * PI_R;
+    const bool mine = f < D;
+    double acc[PI_R];
+#pragma unroll
+    for (int r = 0; r < PI_R; ++r) acc[r] = (mine && jr + r < m) ? loc[(size_t)(jr + r) * a.sumD + d.flag_off + f] : 0.0;
+    const int nchunk = (N + PI_LC - 1) / PI_LC;
+    const long long stages = (long long)chains * nchunk;
+    const int ql = tid & (PI_LC - 1), qj = tid / PI_LC;             // the q entry this lane stages: label of the chunk, row of the tile
+    double pm[PI_MU];
+    int pq = 0;
+    auto fetch = [&](long long t) {
+        const int cb = (int)(t / nchunk), l0 = (int)(t - (long long)cb * nchunk) * PI_LC, c = c0 + cb;
+        const double *mu = a.mu + ((((size_t)(a.lp_all ? c : cb) * K + k) * N + l0) * Dmax) + f;
+#pragma unroll
+        for (int i = 0; i < PI_MU; ++i) {
+            const int ll = wave + 4 * i;
+            pm[i] = (mine && l0 + ll < N) ? mu[(size_t)ll * Dmax] : 0.0;
+        }
+        pq = (l0 + ql < N && j0 + qj < m) ? qsrc[((((size_t)c * K + k) * m + j0 + qj) * N) + l0 + ql] : 0;
+    };
+    if (stages > 0) fetch(0);
+    long long fon = 0;
+    double e[PI_R];
+    for (long long t = 0; t < stages; ++t) {
+        const int cb = (int)(t / nchunk), chunk = (int)(t - (long long)cb * nchunk), l0 = chunk * PI_LC;
+        const int lc = min(PI_LC, N - l0), buf = (int)(t & 1);
+#pragma unroll
+        for (int i = 0; i < PI_MU; ++i) mus[buf][wave + 4 * i][lane] = pm[i];
+        qs[buf][ql][qj] = pq;
+        __syncthreads();                                            // (the buffer's last readers, two stages back, passed the barrier between)
+        if (t + 1 < stages) fetch(t + 1);
+        if (chunk == 0) {
+#pragma unroll
+            for (int r = 0; r < PI_R; ++r) e[r] = 0.0;
+        }
+        for (int ll = 0; ll < lc; ++ll) {
+            const double u = mus[buf][ll][lane];
+#pragma unroll
+            for (int r = 0; r < PI_R; ++r) e[r] = e[r] + (double)qs[buf][ll][wave * PI_R + r] * u;
+        }
+        if (chunk == nchunk - 1) {
+            const bool on = mine && (a.flags ? a.flags[(size_t)(c0 + cb) * a.sumD + d.flag_off + f] != 0 : true);
+            fon += on;
+            if (on) {
+#pragma unroll
+                for (int r = 0; r < PI_R; ++r) acc[r] = acc[r] + e[r];
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < PI_R; ++r)
+        if (mine && jr + r < m) loc[(size_t)(jr + r) * a.sumD + d.flag_off + f] = acc[r];
+    if (count && blockIdx.x == 0 && wave == 0 && mine) a.flag_on[d.flag_off + f] += fon;
+}
+
+__global__ void __launch_bounds__(256) predict_merge_imputed_kernel(const PredictArgs a, const double *__restrict__ loc_b,
+                                                                    const double *__restrict__ locj_b, const long long *__restrict__ flag_b)
+{
+    const long long total = a.m * a.sumD;
+    const long long t0 = (long long)blockIdx.x * 256 + threadIdx.x, step = (long long)gridDim.x * 256;
+    for (long long e = t0; e < total; e += step) {
+        a.loc_sum[e] = a.loc_sum[e] + loc_b[e];
+        if (locj_b) a.loc_joint_sum[e] = a.loc_joint_sum[e] + locj_b[e];
+    }
+    for (long long e = t0; e < a.sumD; e += step) a.flag_on[e] += flag_b[e];
+}
+
+// The imputation sums of one batch of chains from the weights qsrc (q, or the joint qj) into loc
+void launch_impute(const PredictArgs &b, const int *qsrc, double *loc, int c0, int chains, int count, hipStream_t stream)
+{
+    int Dg = 0;
+    for (int k = 0; k < b.K; ++k)
+        if (b.ds[k].kind == K_GAUSSIAN && b.ds[k].D > Dg) Dg = b.ds[k].D;
+    if (Dg == 0) return;
+    dim3 grid((unsigned)((b.m + PI_J - 1) / PI_J), (unsigned)((Dg + PI_F - 1) / PI_F), (unsigned)b.K);
+    hipLaunchKernelGGL(predict_impute_kernel, grid, dim3(256), 0, stream, b, qsrc, loc, c0, chains, count);
+}
+
 // The sums of one add from its weights: sim += the gather of a.q over a.s, new_cluster += a.qnew and lpd_sum + a.inc in chain
 // order.  A coupled add calls it twice: with the per-dataset buffers, then with q, qnew, sim, new_cluster pointed at the joint ones.
 void launch_sums(const PredictArgs &b, hipStream_t stream)
@@ -333,10 +468,13 @@ hipError_t pmdi_launch_predict_add(const PredictArgs &a, hipStream_t stream, con
     if (cp) pmdi_launch_predict_chain_tables(b, *cp, stream);
     for (int c0 = 0; c0 < a.C; c0 += a.Cb) {
         const int chains = a.C - c0 < a.Cb ? a.C - c0 : a.Cb;
-        hipLaunchKernelGGL(predict_weights_kernel, dim3((unsigned)chains * a.K * a.N), dim3(256), lds_w, stream, b, c0);
+        if (a.masked) hipLaunchKernelGGL(predict_weights_kernel<true>, dim3((unsigned)chains * a.K * a.N), dim3(256), lds_w, stream, b, c0);
+        else hipLaunchKernelGGL(predict_weights_kernel<false>, dim3((unsigned)chains * a.K * a.N), dim3(256), lds_w, stream, b, c0);
         const long long rows = (long long)chains * a.K * a.m;
         hipLaunchKernelGGL(predict_normalise_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, b, c0, chains);
+        if (a.loc_sum) launch_impute(b, b.q, b.loc_sum, c0, chains, 1, stream);      // (while the batch's mu is live)
         if (cp) pmdi_launch_predict_couple(b, *cp, c0, chains, stream);      // (while the batch's lp is live)
+        if (cp && a.loc_joint_sum) launch_impute(b, cp->qj, b.loc_joint_sum, c0, chains, 0, stream);
     }
     launch_sums(b, stream);
     if (cp) {
@@ -346,6 +484,14 @@ hipError_t pmdi_launch_predict_add(const PredictArgs &a, hipStream_t stream, con
         launch_sums(j, stream);
         pmdi_launch_predict_coupled_reduce(b, *cp, stream);
     }
+    return hipGetLastError();
+}
+
+hipError_t pmdi_launch_predict_merge_imputed(const PredictArgs &a, const double *loc_b, const double *locj_b, const long long *flag_b, hipStream_t stream)
+{
+    long long grid = (a.m * a.sumD + 255) / 256;
+    if (grid > 65536) grid = 65536;
+    hipLaunchKernelGGL(predict_merge_imputed_kernel, dim3((unsigned)grid), dim3(256), 0, stream, a, loc_b, locj_b, flag_b);
     return hipGetLastError();
 }
 

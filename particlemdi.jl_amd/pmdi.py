@@ -140,12 +140,20 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     co-clusters with each training observation, its weight on a new cluster and its mean log predictive density -- is returned
     after the mixing summary and before the draws: (counts[, summary][, fusion][, mixing][, predict][, draws]).
     predict_coupled (keyword only, default False; needs predict and K > 1): the fifth accumulator also places every new observation
-    jointly across the datasets through Phi, and a predict.CoupledPredictiveCounts is returned in predict's place."""
+    jointly across the datasets through Phi, and a predict.CoupledPredictiveCounts is returned in predict's place.
+    predict_observed (keyword only, default None; needs predict): a list of K boolean (m, D_k) masks or None entries, True = the entry
+    of the held-out row was measured (a NaN in a Gaussian matrix counts as unobserved too).  The unobserved features are marginalised
+    exactly and their values never read; a row absent from a whole dataset is placed there by Pi, or with predict_coupled through Phi
+    by the datasets where it was seen.  A held-out observation with nothing observed anywhere is a ValueError.
+    predict_impute (keyword only, default False; needs predict): the fifth accumulator also sums the posterior-predictive location of
+    every Gaussian entry, and the returned counts give fitted(k) and imputed(k): the held-out rows with their missing values filled in."""
     from .fusion import FusionAccumulator, _group_masks
     fusion = more.pop("fusion", False)
     mixing = more.pop("mixing", False)
     predict = more.pop("predict", None)
     predict_coupled = bool(more.pop("predict_coupled", False))
+    predict_observed = more.pop("predict_observed", None)
+    predict_impute = bool(more.pop("predict_impute", False))
     if more:
         raise TypeError(f"pmdi_pooled() got an unexpected keyword argument {next(iter(more))!r}")
     from .psm import PsmAccumulator, _DeviceInt32View, retained_iterations
@@ -156,8 +164,10 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     if predict_coupled and predict is None:
         raise ValueError("predict_coupled needs predict: the held-out rows to place")
     _need(K > 1 or not predict_coupled, "predict_coupled needs two or more datasets")
+    if predict is None and (predict_observed is not None or predict_impute):
+        raise ValueError("predict_observed and predict_impute need predict: the held-out rows to place")
     if predict is not None:
-        check_new_rows(dataFiles, dataTypes, predict)
+        check_new_rows(dataFiles, dataTypes, predict, predict_observed)
     _need(n_chains >= 1, "n_chains must be >= 1")
     _need(0 <= burnin < iter, "burnin must be >= 0 and smaller than iter (nothing would be retained)")
     _need(thin >= 1, "thin must be >= 1")
@@ -193,7 +203,7 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
         if maxlag:      # ((maxlag + 1) n_chains K n bytes: inside the try, so that a failed allocation still closes the handles)
             mix = MixingAccumulator(n_chains, K, N, n_obs, maxlag=maxlag, device=device)
         if predict is not None:
-            pred = PredictiveAccumulator(sweeper, predict, coupled=predict_coupled)
+            pred = PredictiveAccumulator(sweeper, predict, coupled=predict_coupled, observed=predict_observed, impute=predict_impute)
         g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ, fusion=fus, mixing=mix, predict=pred)
         g.results()                      # synchronises; raises on a kernel-side error of any chain
         counts = acc.counts(names=names)   # (the view keeps the accumulator alive)

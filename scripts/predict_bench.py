@@ -6,7 +6,9 @@ smallest cluster pool and four particles: the accumulator reads its data and tab
 sources do not fit the free memory the script falls back to 1 024 chains and says so.  Prints one JSON object; GPU only.
 `--add-only` runs three adds alone (for a rocprofv3 --kernel-trace --stats run, which gives the split between the kernels).
 `--coupled` times a coupled accumulator instead (PredictiveAccumulator(coupled=True), Phi drawn Gamma(1, 1)): the same adds with the
-Phi-coupled placement on top, and twice the weights and sums in memory.  Without it the output is what it was."""
+Phi-coupled placement on top, and twice the weights and sums in memory.  Without it the output is what it was.
+`--masked` times a masked accumulator (observed=: every entry of the new rows unobserved with probability 1/2, drawn once) and
+`--impute` one that also sums the imputed locations (impute=True); both combine with `--coupled`."""
 import json
 import os
 import sys
@@ -34,13 +36,17 @@ def timed(fn, reps):
     return {"ms_median": float(np.median(out)), "ms_min": float(min(out)), "ms_max": float(max(out)), "reps": reps}
 
 
-def case(C_, K, n, D, N, m, labels, reps, add_only, coupled=False):
+def case(C_, K, n, D, N, m, labels, reps, add_only, coupled=False, masked=False, impute=False):
     rng = np.random.default_rng(1)
     z = rng.integers(0, labels, n)
     train = [rng.normal(size=(n, D)) + 2.0 * z[:, None] for _ in range(K)]
     new = [rng.normal(size=(m, D)) + 2.0 * rng.integers(0, labels, m)[:, None] for _ in range(K)]
     sw = pkg.Sweeper(train, ["gaussian"] * K, N, 4, n_chains=C_, seed=1, pool_cap=N + 2)
-    acc = pkg.PredictiveAccumulator(sw, new, coupled=True) if coupled else pkg.PredictiveAccumulator(sw, new)
+    if masked or impute:
+        observed = [rng.random((m, D)) < 0.5 for _ in range(K)] if masked else None
+        acc = pkg.PredictiveAccumulator(sw, new, coupled=coupled, observed=observed, impute=impute)
+    else:
+        acc = pkg.PredictiveAccumulator(sw, new, coupled=True) if coupled else pkg.PredictiveAccumulator(sw, new)
     gen = torch.Generator(device="cuda").manual_seed(1)
     s = torch.randint(0, labels, (C_, K, n), dtype=torch.int32, device="cuda", generator=gen)
     Pi = torch.rand((C_, K, N), dtype=torch.float64, device="cuda", generator=gen) + 0.05
@@ -63,6 +69,12 @@ def case(C_, K, n, D, N, m, labels, reps, add_only, coupled=False):
         res["coupled"] = True
         res["qj_bytes"], res["sim_joint_bytes"] = res["q_bytes"], res["sim_bytes"]
         assert np.isfinite(pc.joint_log_predictive()).all() and pc.joint_similarity(0)[0].sum() > 0
+    if masked or impute:
+        res["masked"], res["impute"] = masked, impute
+    if impute:
+        res["mu_bytes_per_batch"], res["loc_bytes"] = 8 * min(C_, (64 << 20) // (8 * K * m * N)) * K * N * D, 8 * m * K * D
+        res["impute_multiply_adds"] = C_ * K * m * N * D * (2 if coupled else 1)
+        assert np.isfinite(pc.fitted(0)).all() and (not coupled or np.isfinite(pc.fitted(0, joint=True)).all())
     acc.close()
     sw.close()
     return res
@@ -76,5 +88,5 @@ out = {"free_bytes": int(free), "fallback_to_1024_chains": bool(need > free)}
 if need > free:
     C_head = 1024
 reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 12
-out["headline"] = case(C_head, K, n, D, N, m, 4, reps, "--add-only" in sys.argv, coupled)
+out["headline"] = case(C_head, K, n, D, N, m, 4, reps, "--add-only" in sys.argv, coupled, "--masked" in sys.argv, "--impute" in sys.argv)
 print(json.dumps(out, indent=1))
