@@ -956,6 +956,96 @@ int pmdi_predict_last_imputed(pmdi_predict *a, double *mu /* host [C][K][N][Dmax
 int pmdi_gibbs_run5(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ,
                     pmdi_fusion *fus, pmdi_mixing *mix, pmdi_predict *pred, void *stream);
 
+/* ---- streaming leave-one-out accumulator: how well does the fitted mixture explain each TRAINING row? ----
+ * The sixth accumulator.  For every retained state it evaluates, for every training row i of every dataset k, the Gibbs full
+ * conditional of the row's allocation with the row itself taken out of its cluster, and sums what the conditional predictive
+ * ordinate needs:  CPO_i = p(x_i | all the other data) = 1 / E_post[ 1 / p(x_i | x_-i, state without i) ];  the sum of log CPO
+ * over the rows is the log pseudo-marginal likelihood (LPML).  Like the predictive accumulator it is a child of the handle and
+ * reads its datasets and tables.  C = n_chains, K datasets, N labels, n observations; one retained state of chain c is
+ * s[c][k][i] (0-based), Pi[c][k][.], feature_flag[c][.] and, coupled, Phi[c][.] in Phi's pair order (0,1), (0,2), ..., (K-2,K-1).
+ * Per add, separate IEEE double operations in this order, never fused:
+ *   1. Clusters.  For every (c, k, label l) the cluster of l is rebuilt as step 1 of the predictive accumulator does: its members
+ *      added in ascending observation index under chain c's flags.  This gives cn[l], and per feature the Gaussian (Sigma, beta)
+ *      through gauss_add_sb, the categorical level counts, the NegBinom sum S.
+ *   2. Evaluation.  Row i has the own label o = s[c][k][i] of size cn[o].
+ *      l != o, cn[l] > 0:  lp[l] = calc_logprob(x_i, cluster l, flags) exactly as step 2 of the predictive accumulator forms it:
+ *          the leading term, then the features in ascending order, out += ta; out -= tb (Gaussian), out += LH[2 count + 1]
+ *          (Categorical), out += the six-look-up term (NegBinom).
+ *      cn[l] == 0:  every empty label shares one value, calc_logprob against the constructor's cluster, formed once per row.
+ *      l == o:  the cluster WITHOUT i, of size cn[o] - 1, leading term and terms at that size.  Categorical: the count of x_i's
+ *          level less one; NegBinom: S - x; both exact integers, so lp[o] has the bits of a rebuild from the other members.
+ *          Gaussian: (Sigma', beta') = gauss_remove_sb(x, cn, Sigma, beta) of pmdi_arith.h, the algebraic inverse of gauss_add_sb
+ *          with i as the last member added:
+ *              cn == 1:  (0, 0.5), the constructor's, exactly;  else
+ *              Sigma' = Sigma - x;  mu' = Sigma' / ((cn - 1) + 0.001);  d = x - mu';
+ *              beta'  = beta - ((cn - 1) + 0.001) * (d * d) / (2 * (cn + 0.001));  beta' = max(beta', 0.5)
+ *          then mu, lambda = gauss_ml(cn - 1, Sigma', beta').  It agrees with a rebuild from the other members to rounding,
+ *          conditioned like beta / beta' (DESIGN.md 4.24).  A singleton's own label has the empty labels' lp bit for bit.
+ *      A label outside 0..N-1 is a member of no cluster and no row's own label; it sets the error flag.
+ *   3. Weights.  u[l] = 1.0, then for b != k in ascending b:  u[l] = u[l] * (1.0 + Phi_kb * [l == s[c][b][i]]);  an uncoupled
+ *      accumulator and K = 1 take u = 1.  mx = max_l lp[l];  w[l] = (exp(lp[l] - mx) * Pi[l]) * u[l];  F = ((w[0] + w[1]) + ...).
+ *   4. The log conditional predictive density  ell = log(F) + mx;  coupled:  ell = ell - log(Z0),  Z0 = ((Pi[0] u[0] + Pi[1] u[1])
+ *      + ...).
+ *   5. Fixed point, rounded as the predictive accumulator's q:  p_own = floor(w[o] / F * 2^20 + 0.5) (0 without an own label);
+ *      p_new = the sum of floor(w[l] / F * 2^20 + 0.5) over the labels that are empty once i is gone: cn[l] == 0, and o itself
+ *      when cn[o] == 1.
+ *   6. F = 0 or not finite: a degenerate row.  It adds 1 to zero[k][i] and to nothing else.
+ *   7. Sums per (k, i), one owner lane each, the chains in ascending order within an add and the adds in order:
+ *      own_sum, new_sum, zero  [K][n] Int64    exact in any order
+ *      lcp_sum, lcp_sq_sum     [K][n] Float64  lcp_sum = lcp_sum + ell;  lcp_sq_sum = lcp_sq_sum + ell * ell
+ *      (E, S)                  [K][n] Int64, [K][n][6] Int64  the harmonic-mean pair: sum of exp(-ell) without overflow, without
+ *                              a transcendental inside the running sum, and EXACT, so that it is a function of the multiset of
+ *                              the terms -- the same bits under any batching, any order and any merge:
+ *          t = (-ell) * 1.4426950408889634;  e = floor(t) (as Int64; clamped to +-1e15);  mant = exp2(t - e)
+ *          m = (UInt64)(mant * 2^52) (truncated; 0 unless 0 <= mant < 4): the term is the integer m times 2^(e - 52)
+ *          bin = floor(e / 32);  v = m << (e mod 32), a 128-bit integer;  the pair keeps the three highest bins seen:
+ *          E = the highest bin index (PMDI_LOO_E_EMPTY: none yet), S[2 j], S[2 j + 1] = the high and low 64-bit words of the
+ *          sum of the v of bin E - j, j = 0, 1, 2.  A term of a bin above E moves the window up (bins that leave it are
+ *          dropped whole); a term of a bin below E - 2 is dropped.  What is dropped is below 2^-64 of the largest term each.
+ *      The chains go through steps 1-6 in batches; step 7 is sequential in the chains, so no result depends on the batching.
+ *      On the host, with V = sum_j (S[2 j] 2^64 + S[2 j + 1]) 2^(-32 j) (the words read as unsigned):
+ *      log CPO[k][i] = -((32 E - 52) ln 2 + log V - log(T C - zero)),  -inf where zero > 0.
+ * Stage buffers of a batch of chains: the rebuilt statistics, lp 8 K n N bytes per chain (kept whole for all C chains only
+ * with keep_last), 16 K n bytes per chain of (ell, p_own, p_new).  A batch stays within PMDI_LOO_BUDGET_BYTES
+ * (pmdi_loo_set_budget lowers that for an accumulator -- never raises it: the buffers are allocated at create -- and at least
+ * one chain goes per batch).  State: the seven arrays above and an error flag.
+ * create: checked before the device is touched -- coupled needs K >= 2, and 8 K n N (8 C K n N with keep_last) at most
+ *   PMDI_PREDICT_MAX_BYTES (PMDI_E_ARG).  The accumulator is a child of h: pmdi_destroy(h) is refused (PMDI_E_STATE) while it lives.
+ * add_arrays: device arrays in the layouts of the resident state: s [C][K][n] 0-based int32, Pi [C][K][N], flags [C][sum D]
+ *   bytes or NULL = every feature on, Phi [C][K (K - 1) / 2] -- NULL exactly when the accumulator is uncoupled (a missing Phi is
+ *   PMDI_E_ARG, a Phi too many PMDI_E_STATE).  Pi and Phi are not checked.  A label outside 0..N-1 sets a device flag that
+ *   pmdi_loo_get reports as PMDI_E_DATA until pmdi_loo_reset.
+ * add_gibbs: the current s, Pi, (with feature selection) feature_flag and (coupled) Phi of every chain of g, a child of the same h.
+ * merge: the seven DEVICE arrays of another accumulator of the same shape: integers added, lcp_sum = lcp_sum + theirs, likewise
+ *   lcp_sq_sum, the pair (E, S) bin by bin by the rule of step 7 (exact: the bits of one accumulator that saw both halves),
+ *   T += theirs.  The two Float64 sums agree with one accumulator that saw both halves only to rounding (another order).
+ * get: SYNCHRONISES `stream`, then copies to the host arrays that are not NULL.
+ * last: only with keep_last (else PMDI_E_STATE): synchronises the device and copies the last add's lp [C][K][n][N], ell [C][K][n],
+ *   p_own, p_new [C][K][n] Int32 (p_own = -1 marks a degenerate row), e [C][K][n] Int64 and mant [C][K][n] to the host arrays
+ *   that are not NULL.  reset: every sum zero, every pair empty, T = 0.  One device, not thread-safe, asynchronous on `stream`
+ *   except create, destroy, get and last; all calls on one accumulator go on ONE stream. */
+#define PMDI_LOO_BUDGET_BYTES 268435456LL /* 2^28 */
+#define PMDI_LOO_E_EMPTY (-9187201950435737472LL) /* 0x80 in every byte */
+typedef struct pmdi_loo pmdi_loo;
+int pmdi_loo_create(pmdi_handle *h, int32_t coupled, int32_t keep_last, pmdi_loo **out);
+int pmdi_loo_destroy(pmdi_loo *a);
+int pmdi_loo_reset(pmdi_loo *a, void *stream);
+int64_t pmdi_loo_samples(const pmdi_loo *a);      /* T, the number of adds */
+int pmdi_loo_set_budget(pmdi_loo *a, int64_t bytes);
+int pmdi_loo_add_gibbs(pmdi_loo *a, pmdi_gibbs *g, void *stream);
+int pmdi_loo_add_arrays(pmdi_loo *a, const int32_t *s, const double *Pi, const uint8_t *flags, const double *Phi /* NULL iff uncoupled */,
+                        void *stream);
+int pmdi_loo_merge(pmdi_loo *a, const int64_t *own_sum, const int64_t *new_sum, const int64_t *zero, const double *lcp_sum,
+                   const double *lcp_sq_sum, const int64_t *E, const int64_t *S /* [K][n][6] */, int64_t T, void *stream);
+int pmdi_loo_get(pmdi_loo *a, int64_t *own_sum, int64_t *new_sum, int64_t *zero, double *lcp_sum, double *lcp_sq_sum, int64_t *E,
+                 int64_t *S /* [K][n][6] */, void *stream);
+int pmdi_loo_last(pmdi_loo *a, double *lp, double *ell, int32_t *p_own, int32_t *p_new, int64_t *e, double *mant);
+
+/* pmdi_gibbs_run5 with the sixth accumulator: after every retained local iteration acc, summ, fus, mix, pred, then loo get their
+ * add; any may be NULL, and pmdi_gibbs_run5(g, ..., pred, stream) is pmdi_gibbs_run6(g, ..., pred, NULL, stream). */
+int pmdi_gibbs_run6(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ,
+                    pmdi_fusion *fus, pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, void *stream);
+
 /* Device pointers of the resident state (zero-copy consumers; layouts of pmdi_sweep_device). */
 typedef struct {
     double *M, *gamma, *gamma0, *Phi, *vZ, *Pi, *log1p_phi, *feature_prob, *logweight;

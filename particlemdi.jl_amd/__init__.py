@@ -26,3 +26,4 @@ from .summary import (  # noqa: F401,E402
 from .mixing import MixingAccumulator, MixingSummary  # noqa: F401,E402
 from .predict import (  # noqa: F401,E402
     CoupledPredictiveCounts, PredictiveAccumulator, PredictiveCounts, check_new_rows, observed_masks)
+from .loo import LooAccumulator, LooCounts  # noqa: F401,E402

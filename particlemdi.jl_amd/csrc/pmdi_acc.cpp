@@ -1,6 +1,6 @@
 // pmdi_acc.cpp -- the streaming accumulators of include/pmdi_hip.h (pmdi_psm_acc_*, pmdi_fusion_*, pmdi_summary_*, pmdi_mixing_*,
-// pmdi_predict_*) and their driver pmdi_gibbs_run / run2 / run3 / run4 / run5, which needs nothing of a pmdi_gibbs but the public
-// pmdi_gibbs_step.
+// pmdi_predict_*, pmdi_loo_*) and their driver pmdi_gibbs_run / run2 / run3 / run4 / run5 / run6, which needs nothing of a pmdi_gibbs
+// but the public pmdi_gibbs_step.
 #include "pmdi_host.h"
 
 #include <cmath>
@@ -83,6 +83,22 @@ struct pmdi_predict {
     bool impute = false;                 // created by pmdi_predict_create_masked with impute: every add also sums the imputed locations
     char *slab3 = nullptr;               // what reset zeroes of an imputing accumulator: loc_sum, loc_joint_sum (coupled), flag_on
     size_t state3_bytes = 0;
+};
+
+// Streaming leave-one-out accumulator (pmdi_loo_* entry points): a child of the handle whose datasets and tables it reads.  One
+// device slab holds what reset clears -- own_sum, new_sum, zero, lcp_sum, lcp_sq_sum, S (six words per entry), then E (whose empty value is not 0), then
+// the error flag; the stage buffers of a batch of chains are separate allocations
+struct pmdi_loo {
+    pmdi_handle *h = nullptr;
+    int device = 0;
+    LooArgs la{};                        // everything of an add but its sources
+    bool keep_last = false, coupled = false;
+    char *slab = nullptr;
+    size_t state_bytes = 0;
+    long long per_chain = 0;             // bytes of stage buffers one chain of a batch takes
+    int Cb_alloc = 0;                    // chains per batch the stage buffers were allocated for
+    std::vector<void *> owned;           // device allocations freed in destroy
+    int64_t T = 0;                       // adds so far
 };
 
 namespace {
@@ -173,9 +189,17 @@ int predict_accepts(const pmdi_predict *a, const pmdi_gibbs *g, int64_t n_adds)
     return PMDI_OK;
 }
 
-// device memory of a predictive accumulator, freed with it
-template <class Tp>
-int predict_alloc(pmdi_predict *a, Tp **p, size_t count)
+// what pmdi_loo_add_gibbs checks before it touches anything (pmdi_gibbs_run6 asks once, before its first iteration)
+int loo_accepts(const pmdi_loo *a, const pmdi_gibbs *g, int64_t n_adds)
+{
+    if (g->h != a->h) return fail(PMDI_E_ARG, "the leave-one-out accumulator was created from another handle than the chains");
+    if (n_adds > 2147483647LL - a->T) return fail(PMDI_E_ARG, "%lld + %lld adds pass INT32_MAX", (long long)a->T, (long long)n_adds);
+    return PMDI_OK;
+}
+
+// device memory of a predictive or leave-one-out accumulator, freed with it
+template <class Acc, class Tp>
+int predict_alloc(Acc *a, Tp **p, size_t count)
 {
     size_t bytes = count * sizeof(Tp);
     if (bytes == 0) bytes = 16;
@@ -1019,8 +1043,182 @@ int pmdi_predict_last_imputed(pmdi_predict *a, double *mu)
     return PMDI_OK;
 }
 
-int pmdi_gibbs_run5(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
-                    pmdi_mixing *mix, pmdi_predict *pred, void *stream)
+int pmdi_loo_destroy(pmdi_loo *a)
+{
+    if (!a) return PMDI_OK;
+    (void)hipSetDevice(a->device);
+    (void)hipDeviceSynchronize();
+    if (a->slab) (void)hipFree(a->slab);
+    for (void *p : a->owned) (void)hipFree(p);
+    if (a->h && a->h->children > 0) a->h->children -= 1;      // (the handle outlives its children: pmdi_destroy refuses otherwise)
+    delete a;
+    return PMDI_OK;
+}
+
+// what reset leaves: every sum zero, every pair empty
+static int loo_clear(pmdi_loo *a, hipStream_t st)
+{
+    const size_t Kn = (size_t)a->la.K * a->la.n;
+    HIP_TRY(hipMemsetAsync(a->slab, 0, a->state_bytes, st));
+    HIP_TRY(hipMemsetAsync(a->la.E, 0x80, Kn * 8, st));        // PMDI_LOO_E_EMPTY in every byte
+    return PMDI_OK;
+}
+
+int pmdi_loo_create(pmdi_handle *h, int32_t coupled, int32_t keep_last, pmdi_loo **out)
+{
+    if (!h || !out) return fail(PMDI_E_ARG, "null argument");
+    *out = nullptr;
+    const int C = h->cfg.n_chains, K = h->cfg.K, N = h->cfg.N;
+    const long long n = h->cfg.n;
+    if (coupled && K < 2) return fail(PMDI_E_ARG, "a coupled accumulator needs K >= 2 datasets, the handle has K=%d", K);
+    const long double lp_bytes = 8.0L * K * (long double)n * N;
+    if ((keep_last ? lp_bytes * C : lp_bytes) > (long double)PMDI_PREDICT_MAX_BYTES)
+        return fail(PMDI_E_ARG, "the log predictives (8 %sK n N = %.0Lf bytes) pass %lld bytes", keep_last ? "C " : "", keep_last ? lp_bytes * C : lp_bytes,
+                    (long long)PMDI_PREDICT_MAX_BYTES);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    pmdi_loo *a = new (std::nothrow) pmdi_loo();
+    if (!a) return fail(PMDI_E_MEMORY, "out of host memory");
+    a->h = h; a->device = h->cfg.device; a->keep_last = keep_last != 0; a->coupled = coupled != 0;
+    h->children += 1;
+    LooArgs &p = a->la;
+    p.C = C; p.K = K; p.N = N; p.sumD = h->sumD; p.n = n; p.npairs = K * (K - 1) / 2;
+    size_t at = 0;
+    for (int k = 0; k < K; ++k) {
+        const DsetDev &d = h->ds[k];
+        p.ds[k] = d;
+        size_t per = d.kind == K_GAUSSIAN ? 16 * (size_t)d.D : d.kind == K_NEGBINOM ? 8 * (size_t)d.D : 4 * (size_t)d.D * d.L;
+        per = (per + 15) & ~(size_t)15;
+        p.stat_at[k] = at; p.stat_label[k] = per;
+        at += per * N;
+    }
+    p.stat_chain = at;
+    // chains per batch: the stage buffers of one chain are its statistics, its start terms, 8 K n N bytes of log predictives and
+    // 16 K n of per-row results; a batch stays within PMDI_LOO_BUDGET_BYTES
+    a->per_chain = (long long)at + 32LL * K * N + (long long)K * n * (8LL * N + 16);
+    long long Cb = PMDI_LOO_BUDGET_BYTES / a->per_chain;
+    p.Cb = a->Cb_alloc = (int)(Cb < 1 ? 1 : Cb > C ? C : Cb);
+    p.lp_all = a->keep_last ? 1 : 0;
+    const size_t rows = (size_t)(a->keep_last ? C : p.Cb) * K * n, CKn = (size_t)C * K * n;
+    int rc = predict_alloc(a, &p.stats, (size_t)p.Cb * p.stat_chain);
+    if (!rc) rc = predict_alloc(a, &p.start, (size_t)p.Cb * K * N * 4);
+    if (!rc) rc = predict_alloc(a, &p.cn, (size_t)C * K * N);
+    if (!rc) rc = predict_alloc(a, &p.lp, rows * N);
+    if (!rc) rc = predict_alloc(a, &p.ell, rows);
+    if (!rc) rc = predict_alloc(a, &p.pown, rows);
+    if (!rc) rc = predict_alloc(a, &p.pnew, rows);
+    if (!rc && a->keep_last) rc = predict_alloc(a, &p.e_last, CKn);
+    if (!rc && a->keep_last) rc = predict_alloc(a, &p.mant_last, CKn);
+    if (rc) { pmdi_loo_destroy(a); return rc; }
+    const size_t Kn = (size_t)K * n;
+    a->state_bytes = (12 * Kn + 1) * 8;
+    hipError_t e = hipMalloc((void **)&a->slab, a->state_bytes);
+    if (e != hipSuccess) { a->slab = nullptr; pmdi_loo_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", a->state_bytes, hipGetErrorString(e)); }
+    p.own_sum = (long long *)a->slab;
+    p.new_sum = p.own_sum + Kn;
+    p.zero = p.new_sum + Kn;
+    p.lcp_sum = (double *)(p.zero + Kn);
+    p.lcp_sq_sum = p.lcp_sum + Kn;
+    p.S = (long long *)(p.lcp_sq_sum + Kn);
+    p.E = p.S + 6 * Kn;
+    p.err = (int *)(p.E + Kn);
+    if (loo_clear(a, nullptr) != PMDI_OK || hipDeviceSynchronize() != hipSuccess) { pmdi_loo_destroy(a); return fail(PMDI_E_DEVICE, "hipMemset failed"); }
+    *out = a;
+    return PMDI_OK;
+}
+
+int pmdi_loo_set_budget(pmdi_loo *a, int64_t bytes)
+{
+    if (!a || bytes < 0) return fail(PMDI_E_ARG, "bad argument");
+    long long Cb = bytes / a->per_chain;
+    a->la.Cb = (int)(Cb < 1 ? 1 : Cb > a->Cb_alloc ? a->Cb_alloc : Cb);
+    return PMDI_OK;
+}
+
+int pmdi_loo_reset(pmdi_loo *a, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    if (const int rc = loo_clear(a, (hipStream_t)stream)) return rc;
+    a->T = 0;
+    return PMDI_OK;
+}
+
+int64_t pmdi_loo_samples(const pmdi_loo *a) { return a ? a->T : 0; }
+
+int pmdi_loo_add_arrays(pmdi_loo *a, const int32_t *s, const double *Pi, const uint8_t *flags, const double *Phi, void *stream)
+{
+    if (!a || !s || !Pi) return fail(PMDI_E_ARG, "null argument");
+    if (a->coupled && !Phi) return fail(PMDI_E_ARG, "pmdi_loo_add_arrays: a coupled accumulator needs Phi");
+    if (!a->coupled && Phi) return fail(PMDI_E_STATE, "pmdi_loo_add_arrays: Phi goes with a coupled accumulator, and only with one");
+    if (a->T >= 2147483647LL) return fail(PMDI_E_ARG, "%lld + 1 adds pass INT32_MAX", (long long)a->T);
+    HIP_TRY(hipSetDevice(a->device));
+    LooArgs p = a->la;
+    p.s = s; p.Pi = Pi; p.flags = flags; p.Phi = Phi;
+    hipError_t e = pmdi_launch_loo_add(p, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "loo-add launch: %s", hipGetErrorString(e));
+    a->T += 1;
+    return PMDI_OK;
+}
+
+int pmdi_loo_add_gibbs(pmdi_loo *a, pmdi_gibbs *g, void *stream)
+{
+    if (!a || !g) return fail(PMDI_E_ARG, "null argument");
+    if (const int rc = loo_accepts(a, g, 1)) return rc;
+    return pmdi_loo_add_arrays(a, g->ga.s, g->ga.Pi, g->feature_select ? g->flags : nullptr, a->coupled ? g->ga.Phi : nullptr, stream);
+}
+
+int pmdi_loo_merge(pmdi_loo *a, const int64_t *own_sum, const int64_t *new_sum, const int64_t *zero, const double *lcp_sum,
+                   const double *lcp_sq_sum, const int64_t *E, const int64_t *S, int64_t T, void *stream)
+{
+    if (!a || !own_sum || !new_sum || !zero || !lcp_sum || !lcp_sq_sum || !E || !S) return fail(PMDI_E_ARG, "null argument");
+    if (T < 0 || T > 2147483647LL - a->T) return fail(PMDI_E_ARG, "%lld + %lld adds are negative or pass INT32_MAX", (long long)a->T, (long long)T);
+    HIP_TRY(hipSetDevice(a->device));
+    hipError_t e = pmdi_launch_loo_merge(a->la, (const long long *)own_sum, (const long long *)new_sum, (const long long *)zero, lcp_sum,
+                                         lcp_sq_sum, (const long long *)E, (const long long *)S, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "loo-merge launch: %s", hipGetErrorString(e));
+    a->T += T;
+    return PMDI_OK;
+}
+
+int pmdi_loo_get(pmdi_loo *a, int64_t *own_sum, int64_t *new_sum, int64_t *zero, double *lcp_sum, double *lcp_sq_sum, int64_t *E, int64_t *S,
+                 void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    hipStream_t st = (hipStream_t)stream;
+    const LooArgs &p = a->la;
+    const size_t bytes = (size_t)p.K * p.n * 8;
+    int err = 0;
+    void *dst[7] = {own_sum, new_sum, zero, lcp_sum, lcp_sq_sum, E, S};
+    const void *src[7] = {p.own_sum, p.new_sum, p.zero, p.lcp_sum, p.lcp_sq_sum, p.E, p.S};
+    for (int i = 0; i < 7; ++i)
+        if (dst[i]) HIP_TRY(hipMemcpyAsync(dst[i], src[i], i == 6 ? 6 * bytes : bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&err, p.err, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (err) return fail(PMDI_E_DATA, "a label outside 0..%d was added (pmdi_loo_add_arrays); pmdi_loo_reset clears the accumulator", p.N - 1);
+    return PMDI_OK;
+}
+
+int pmdi_loo_last(pmdi_loo *a, double *lp, double *ell, int32_t *p_own, int32_t *p_new, int64_t *e, double *mant)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    if (!a->keep_last) return fail(PMDI_E_STATE, "pmdi_loo_last: the accumulator was created without keep_last");
+    if (a->T < 1) return fail(PMDI_E_STATE, "pmdi_loo_last: nothing was added yet");
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const LooArgs &p = a->la;
+    const size_t CKn = (size_t)p.C * p.K * p.n;
+    if (lp) HIP_TRY(hipMemcpy(lp, p.lp, CKn * p.N * 8, hipMemcpyDeviceToHost));
+    if (ell) HIP_TRY(hipMemcpy(ell, p.ell, CKn * 8, hipMemcpyDeviceToHost));
+    if (p_own) HIP_TRY(hipMemcpy(p_own, p.pown, CKn * 4, hipMemcpyDeviceToHost));
+    if (p_new) HIP_TRY(hipMemcpy(p_new, p.pnew, CKn * 4, hipMemcpyDeviceToHost));
+    if (e) HIP_TRY(hipMemcpy(e, p.e_last, CKn * 8, hipMemcpyDeviceToHost));
+    if (mant) HIP_TRY(hipMemcpy(mant, p.mant_last, CKn * 8, hipMemcpyDeviceToHost));
+    return PMDI_OK;
+}
+
+int pmdi_gibbs_run6(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
+                    pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, void *stream)
 {
     if (!g || n_iter < 0) return fail(PMDI_E_ARG, "bad argument");
     if (burnin < 0 || thin < 1) return fail(PMDI_E_ARG, "burnin=%lld must be >= 0 and thin=%lld >= 1", (long long)burnin, (long long)thin);
@@ -1031,6 +1229,7 @@ int pmdi_gibbs_run5(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
     if (fus && (rc = accepts(fus, "fusion accumulator", g, kept))) return rc;
     if (mix && (rc = mixing_accepts(mix, g, kept))) return rc;
     if (pred && (rc = predict_accepts(pred, g, kept))) return rc;
+    if (loo && (rc = loo_accepts(loo, g, kept))) return rc;
     for (int64_t t = 1; t <= n_iter; ++t) {
         if ((rc = pmdi_gibbs_step(g, PMDI_STEP_BEGIN, stream)) || (rc = pmdi_gibbs_step(g, PMDI_STEP_HYPERS, stream)) ||
             (rc = pmdi_gibbs_step(g, PMDI_STEP_SWEEP, stream)))
@@ -1043,9 +1242,16 @@ int pmdi_gibbs_run5(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
             if (fus && (rc = pmdi_fusion_add_gibbs(fus, g, stream))) return rc;
             if (mix && (rc = pmdi_mixing_add_gibbs(mix, g, stream))) return rc;
             if (pred && (rc = pmdi_predict_add_gibbs(pred, g, stream))) return rc;
+            if (loo && (rc = pmdi_loo_add_gibbs(loo, g, stream))) return rc;
         }
     }
     return PMDI_OK;
+}
+
+int pmdi_gibbs_run5(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
+                    pmdi_mixing *mix, pmdi_predict *pred, void *stream)
+{
+    return pmdi_gibbs_run6(g, n_iter, burnin, thin, acc, summ, fus, mix, pred, nullptr, stream);
 }
 
 int pmdi_gibbs_run4(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,

@@ -3,6 +3,7 @@
 //   uniform01                                   the counter-based uniforms (Philox4x32-10)
 //   gauss_add / gauss_add_sb / gauss_ml /       the Gaussian sufficient-statistic recurrences and the per-feature terms of
 //   gauss_term_a / gauss_term_b / gauss_terms   calc_logprob
+//   gauss_remove_sb                             the downdate of (Sigma, beta) by the last member added (leave-one-out)
 //   negbin_term                                 the NegBinom per-feature term (six look-ups of a loggamma table)
 //   resample_u_at                               draw_partstar's u += 1/P sequence, replayed exactly by binade jumps
 //   ess_needs_sequential_redo / ess_resamples   the resampling decision
@@ -91,6 +92,22 @@ PMDI_HD void gauss_add_sb(double x, int nnew, double &sg, double &bt)
     sg = sg + x;
     const double d = x - mu_prev;
     bt = bt + ((double)(nnew - 1) + 0.001) * (d * d) / (2.0 * (n + 0.001));
+}
+
+// The algebraic inverse of gauss_add_sb with x as the LAST member added: (Sigma, beta) of a cluster of size cn >= 1 become those of
+// the cn - 1 other members (the leave-one-out accumulator's own-label cluster, include/pmdi_hip.h).  beta' repeats the added term
+// with the mean of the others, so it agrees with a rebuild from the other members only to rounding -- the subtraction is
+// conditioned like beta / beta'  -- and never falls below the constructor's 0.5.  cn == 1: exactly the
+// constructor's (0, 0.5), whatever (0.5 + t) - t rounds to.
+PMDI_HD void gauss_remove_sb(double x, int cn, double &sg, double &bt)
+{
+    if (cn == 1) { sg = 0.0; bt = 0.5; return; }
+    const double n = (double)cn;
+    sg = sg - x;
+    const double mu_rest = sg / ((double)(cn - 1) + 0.001);
+    const double d = x - mu_rest;
+    bt = bt - ((double)(cn - 1) + 0.001) * (d * d) / (2.0 * (n + 0.001));
+    bt = (bt > 0.5) ? bt : 0.5;
 }
 
 // mu and lambda of a cluster of size cn from (Sigma, beta): gaussian_cluster.jl:60-63 (cn == 0: the constructor's mu = 0, lambda = 1)

@@ -399,3 +399,40 @@ void pmdi_launch_predict_couple(const PredictArgs &a, const CoupledArgs &cp, int
 void pmdi_launch_predict_coupled_reduce(const PredictArgs &a, const CoupledArgs &cp, hipStream_t stream);
 // fused_new += fused_b, lpd_joint_sum = lpd_joint_sum + lpdj_b (device arrays)
 hipError_t pmdi_launch_predict_coupled_merge(const PredictArgs &a, const CoupledArgs &cp, const long long *fused_b, const double *lpdj_b, hipStream_t stream);
+
+// One add of the streaming leave-one-out accumulator (pmdi_loo.hip): the source arrays in the GibbsArgs layouts, the handle's
+// datasets and tables, the stage buffers of a batch of chains and the accumulator's state.
+struct LooArgs {
+    int C, K, N, sumD;          // chains, datasets, labels, features of all datasets
+    int npairs;                 // K (K - 1) / 2
+    int ltile;                  // features of a categorical dataset counted per pass of the rebuild kernel (set by the launcher)
+    long long n;                // training observations
+    DsetDev ds[PMDI_KMAX_I];    // the handle's datasets: training data and tables
+    size_t stat_at[PMDI_KMAX_I];        // byte offset of dataset k's block inside one chain's statistics
+    size_t stat_label[PMDI_KMAX_I];     // bytes per label there: Gaussian 16 D (Sigma, beta), NegBinom 8 D, Categorical 4 D L
+    size_t stat_chain;          // bytes of one chain's statistics
+    const int *s;               // [C][K][n]  0-based labels
+    const double *Pi;           // [C][K][N]
+    const unsigned char *flags; // [C][sumD], or null: every feature on
+    const double *Phi;          // [C][npairs], or null: uncoupled (u = 1)
+    char *stats;                // [Cb] rebuilt statistics of one batch of chains
+    double *start;              // [Cb][K][N][4]  what calc_logprob starts from at the label's size, at that size less one, at size 0
+    int *cn;                    // [C][K][N]  members of each label in this add's sample
+    double *lp;                 // [Cb][K][n][N]  log predictives of one batch of chains (with keep_last: of all chains)
+    int lp_all;                 // 1: lp and the per-row buffers hold all C chains, a batch writes its own slice
+    int Cb;                     // chains per batch
+    double *ell;                // [Cb][K][n]  log conditional predictive density
+    int *pown, *pnew;           // [Cb][K][n]  fixed-point weights; pown = -1: a degenerate row (F = 0 or not finite)
+    long long *e_last;          // [C][K][n]  with keep_last, else null
+    double *mant_last;          // [C][K][n]  with keep_last, else null
+    int *err;                   // set to 1 by a label outside 0..N-1
+    long long *own_sum, *new_sum, *zero;        // [K][n]
+    double *lcp_sum, *lcp_sq_sum;               // [K][n]
+    long long *E;               // [K][n]  highest exponent bin of the harmonic-mean pair; PMDI_LOO_E_EMPTY_I: nothing summed yet
+    long long *S;               // [K][n][6]  its three highest bins, (high, low) words of an exact 128-bit sum each
+};
+#define PMDI_LOO_E_EMPTY_I ((long long)0x8080808080808080ULL)      // what a byte-wise memset of 0x80 leaves
+hipError_t pmdi_launch_loo_add(const LooArgs &a, hipStream_t stream);
+// ours + theirs (device arrays of another accumulator of the same shape), the pair bin by bin: exact
+hipError_t pmdi_launch_loo_merge(const LooArgs &a, const long long *own_b, const long long *new_b, const long long *zero_b,
+                                 const double *lcp_b, const double *lcpsq_b, const long long *E_b, const long long *S_b, hipStream_t stream);

@@ -146,7 +146,13 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     exactly and their values never read; a row absent from a whole dataset is placed there by Pi, or with predict_coupled through Phi
     by the datasets where it was seen.  A held-out observation with nothing observed anywhere is a ValueError.
     predict_impute (keyword only, default False; needs predict): the fifth accumulator also sums the posterior-predictive location of
-    every Gaussian entry, and the returned counts give fitted(k) and imputed(k): the held-out rows with their missing values filled in."""
+    every Gaussian entry, and the returned counts give fitted(k) and imputed(k): the held-out rows with their missing values filled in.
+    loo (keyword only, default False): a sixth accumulator (loo.LooAccumulator) takes the same retained iterations and its
+    loo.LooCounts -- per training row and dataset the log conditional predictive ordinate (log_cpo, and its sum lpml: compare kinds,
+    N or sets of datasets), the stability of the row's label (own_label) and its outlier score (new_cluster, outliers) -- is returned
+    after the predictive counts and before the draws: (counts[, summary][, fusion][, mixing][, predict][, loo][, draws]).
+    loo_coupled (keyword only; needs loo): the full conditional carries Phi against the labels the other datasets give the row.
+    Default: on when K > 1; True with one dataset is a ValueError."""
     from .fusion import FusionAccumulator, _group_masks
     fusion = more.pop("fusion", False)
     mixing = more.pop("mixing", False)
@@ -154,13 +160,20 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     predict_coupled = bool(more.pop("predict_coupled", False))
     predict_observed = more.pop("predict_observed", None)
     predict_impute = bool(more.pop("predict_impute", False))
+    loo = bool(more.pop("loo", False))
+    loo_coupled = more.pop("loo_coupled", None)
     if more:
         raise TypeError(f"pmdi_pooled() got an unexpected keyword argument {next(iter(more))!r}")
     from .psm import PsmAccumulator, _DeviceInt32View, retained_iterations
     from .summary import SummaryAccumulator
     from .mixing import MixingAccumulator
     from .predict import PredictiveAccumulator, check_new_rows
+    from .loo import LooAccumulator
     K, n_obs, names = _check_arguments(dataFiles, dataTypes, N, particles, rho)
+    if loo_coupled is not None and not loo:
+        raise ValueError("loo_coupled needs loo=True")
+    _need(K > 1 or not loo_coupled, "loo_coupled needs two or more datasets")
+    loo_coupled = K > 1 if loo_coupled is None else bool(loo_coupled)
     if predict_coupled and predict is None:
         raise ValueError("predict_coupled needs predict: the held-out rows to place")
     _need(K > 1 or not predict_coupled, "predict_coupled needs two or more datasets")
@@ -198,13 +211,15 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
         summ = SummaryAccumulator(n_chains, K, N, n_obs, sumD=sweeper.sumD if featureSelect else 0,
                                   trace_cap=len(retained_iterations(iter, burnin, thin)), device=device)
     fus = FusionAccumulator(K, n_obs, n_labels=N, groups=fusion_groups, matrix=fusion_matrix, device=device) if fusion else None
-    mix = pred = None
+    mix = pred = loo_acc = None
     try:
         if maxlag:      # ((maxlag + 1) n_chains K n bytes: inside the try, so that a failed allocation still closes the handles)
             mix = MixingAccumulator(n_chains, K, N, n_obs, maxlag=maxlag, device=device)
         if predict is not None:
             pred = PredictiveAccumulator(sweeper, predict, coupled=predict_coupled, observed=predict_observed, impute=predict_impute)
-        g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ, fusion=fus, mixing=mix, predict=pred)
+        if loo:
+            loo_acc = LooAccumulator(sweeper, coupled=loo_coupled)
+        g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ, fusion=fus, mixing=mix, predict=pred, loo=loo_acc)
         g.results()                      # synchronises; raises on a kernel-side error of any chain
         counts = acc.counts(names=names)   # (the view keeps the accumulator alive)
         out = (counts,) if summ is None else (counts, summ.summary(names=names, feature_D=sweeper.D))
@@ -214,6 +229,8 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
             out += (mix.result(names=names),)
         if pred is not None:
             out += (pred.result(names=names),)
+        if loo_acc is not None:
+            out += (loo_acc.result(names=names),)
         if final_allocations:
             import torch
             dev = torch.device("cuda", int(device))
@@ -227,5 +244,7 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
             mix.close()
         if pred is not None:
             pred.close()      # (a child of the sweeper's handle: before it)
+        if loo_acc is not None:
+            loo_acc.close()
         g.close()
         sweeper.close()
