@@ -91,7 +91,15 @@ typedef struct {
     int32_t ticket;         /* PMDI_TICKET         0: workgroup b of the settled-chain launch sweeps chain order[b]; automatic (1): it draws its
                              *                     position in the launch order from a counter, so the next chain goes to whichever workgroup slot
                              *                     of the GPU frees first (the hardware deals block indices to 32 dispatch queues statically) */
-    int32_t reserved[5];    /* -1 */
+    int32_t hold;           /* PMDI_HOLD           0: a workgroup of the settled-chain launch sweeps one chain and ends (A/B runs, reference of the
+                             *                     tests); automatic (1): once every heavy chain's workgroup of the sweep has started it keeps its
+                             *                     slot and draws the next chain of the launch order, until the order is used up -- no slot waits
+                             *                     for its dispatch queue's share of the workgroup indices; 2: it always keeps its slot (tests).
+                             *                     Needs the ticket: with ticket = 0 the workgroups are one-shot whatever this says */
+    int32_t sweep_grid;     /* PMDI_SWEEP_GRID     workgroups of the settled-chain launch (automatic: n_chains).  Fewer than n_chains only with
+                             *                     hold = 2 -- three workgroups then sweep twenty chains; with one-shot workgroups pmdi_create
+                             *                     rejects it (PMDI_E_ARG: chains would stay unswept), with hold = 1 it is ignored */
+    int32_t reserved[3];    /* -1 */
 } pmdi_tuning;
 
 typedef struct {
@@ -1150,6 +1158,20 @@ int pmdi_chain_swept_by(pmdi_handle *h, int32_t *out);
  *   workgroup, [27] its LDS bytes, [28] 1: handed-over chains are carried on in place (0: swept again from the start),
  *   [29] 1: ... by K workgroups per chain (requeue_ksplit);  [30..31] 0 */
 int pmdi_sweep_layout(const pmdi_handle *h, int32_t *out32);
+
+/* The settled-chain launch as pmdi_create settled it (pmdi_tuning hold, sweep_grid), for diagnostics and tests.  out4 (4 Int32):
+ * [0] hold in effect (0 one-shot workgroups / 1 slots are kept once the heavy chains' workgroups have started / 2 always),
+ * [1] workgroups of the launch, [2] workgroup slots of the device for that kernel (resident workgroups per CU x CUs: what the launch
+ * can keep busy at once; asks the runtime), [3] positions of the launch order the workgroups of the last sweep's launch drew
+ * (synchronises; 0 before the first sweep or without the ticket): every position below n_chains is drawn exactly once, so a value of
+ * at least n_chains says every chain of that launch's group was taken up once; at most n_chains + [1].
+ * All zeros when the handle does not have that kernel. */
+int pmdi_settled_launch(pmdi_handle *h, int32_t *out4);
+
+/* Debug, with pmdi_phase_timers: out[n_chains][2] -- when the workgroup that swept a chain in the last sweep took it up and when it
+ * was done with it, whichever kernel that was, on a 100 MHz counter the whole device shares (scripts/packing_probe.py: how the
+ * chains of a sweep pack onto the workgroup slots). */
+int pmdi_chain_stamps(pmdi_handle *h, int64_t *out);
 
 int pmdi_sum_D(const pmdi_handle *h);
 int pmdi_block_threads(const pmdi_handle *h);   /* threads per chain workgroup */

@@ -60,6 +60,7 @@ EXPORTS = [
     "pmdi_partition_rows_device", "pmdi_partition_distance_device", "pmdi_partition_refine_device",
     "pmdi_loo_create", "pmdi_loo_destroy", "pmdi_loo_reset", "pmdi_loo_samples", "pmdi_loo_set_budget", "pmdi_loo_add_gibbs",
     "pmdi_loo_add_arrays", "pmdi_loo_merge", "pmdi_loo_get", "pmdi_loo_last", "pmdi_gibbs_run6",
+    "pmdi_settled_launch", "pmdi_chain_stamps",
 ]
 
 
@@ -137,7 +138,7 @@ class _Tuning(C.Structure):
     this wrapper asks it to (pmdi_tuning_from_env) so that the PMDI_* variables keep working for tests, bench.py and the scripts."""
     _fields_ = [(name, C.c_int32) for name in (
         "settled", "continue_inplace", "sticky", "light_ids", "s2_cols", "s2_idcap", "s2_cls", "ksplit", "requeue_ksplit", "split",
-        "heavy_threads", "two_per_cu", "very_heavy", "start_gate", "terms_cap", "lds_target", "phase_timers", "profiled", "ticket")] + [("reserved", C.c_int32 * 5)]
+        "heavy_threads", "two_per_cu", "very_heavy", "start_gate", "terms_cap", "lds_target", "phase_timers", "profiled", "ticket", "hold", "sweep_grid")] + [("reserved", C.c_int32 * 3)]
 
 
 class _Config(C.Structure):
@@ -386,6 +387,10 @@ def lib():
     L.pmdi_settled_kernel.argtypes = [vp, vp]
     L.pmdi_chain_swept_by.restype = C.c_int
     L.pmdi_chain_swept_by.argtypes = [vp, vp]
+    L.pmdi_settled_launch.restype = C.c_int
+    L.pmdi_settled_launch.argtypes = [vp, vp]
+    L.pmdi_chain_stamps.restype = C.c_int
+    L.pmdi_chain_stamps.argtypes = [vp, vp]
     L.pmdi_tuning_default.restype = None
     L.pmdi_tuning_default.argtypes = [C.POINTER(_Tuning)]
     L.pmdi_tuning_from_env.restype = None
@@ -642,6 +647,21 @@ class Sweeper(_Handle):
         """Which kernel finished each chain's last sweep: 0 general, 1 settled-chain, 2 general after a hand-back."""
         out = np.zeros(self.C, dtype=np.int32)
         _check(lib().pmdi_chain_swept_by(self.h, _ptr(out)))
+        return out
+
+    def settled_launch(self):
+        """The settled-chain launch as pmdi_create settled it (pmdi_settled_launch): "hold" in effect (0 one-shot workgroups, 1 slots
+        are kept once the heavy chains' workgroups have started, 2 always), "grid" workgroups of the launch, "slots" workgroups of
+        that kernel the device holds at once, "draws" positions of the launch order the last sweep's launch drew (every position
+        below n_chains exactly once).  None when the handle does not have that kernel."""
+        v = np.zeros(4, dtype=np.int32)
+        _check(lib().pmdi_settled_launch(self.h, _ptr(v)))
+        return {"hold": int(v[0]), "grid": int(v[1]), "slots": int(v[2]), "draws": int(v[3])} if self.settled else None
+
+    def chain_stamps(self):
+        """(n_chains, 2) int64: when each chain's workgroup took it up and when it was done, 100 MHz ticks (PMDI_PHASE_TIMERS=1)."""
+        out = np.zeros((self.C, 2), dtype=np.int64)
+        _check(lib().pmdi_chain_stamps(self.h, _ptr(out)))
         return out
 
     def chain_costs(self):

@@ -138,6 +138,7 @@ void fill_sweep_common(const pmdi_handle *h, SweepArgs &a)
     a.item_cap = h->cfg.N > 32 ? PMDI_ITEM_CAP_BIGN : PMDI_ITEM_CAP;
     a.two_per_cu = pl.two_per_cu;
     a.phase = pl.phase_on ? (long long *)h->d_phase.p : nullptr;
+    a.stamp = pl.phase_on ? (long long *)h->d_stamp.p : nullptr;
     a.cost = (long long *)h->d_cost.p;
     a.work = (long long *)h->d_work.p;
     a.anclog = (int *)h->d_anclog.p; a.evpos = (int *)h->d_evpos.p;
@@ -235,6 +236,8 @@ int launch_sweep_groups(pmdi_handle *h, SweepArgs &a, hipStream_t st)
         HIP_TRY(hipEventRecord(h->ev_fork, st));
         a.group_flag = (const unsigned char *)h->d_group.p;
         a.group_sel = 1;
+        // the heavy launches count their workgroups in: the settled-chain launch's workgroups keep their slots once all are placed
+        a.heavy_left = pl.s2_ok ? (int *)h->d_heavy_left.p : nullptr;
         const int vh = pl.very_heavy < C ? pl.very_heavy : C;
         if (vh > 0) {
             // the heaviest chains bound the launch: they get the 256-register build, one CU each
@@ -263,6 +266,7 @@ int launch_sweep_groups(pmdi_handle *h, SweepArgs &a, hipStream_t st)
         if (vh > 0) HIP_TRY(hipStreamWaitEvent(st, h->ev_join3, 0));
         SweepArgs al = a;
         al.group_sel = 0; al.rank_lo = 0; al.rank_hi = C;
+        al.heavy_left = nullptr;
         pmdi_put_tables(pl.light, al);
         HIP_TRY(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
         if (pl.s2_ok) {
@@ -275,7 +279,11 @@ int launch_sweep_groups(pmdi_handle *h, SweepArgs &a, hipStream_t st)
             SweepArgs as = al;
             // its workgroups draw their positions in the launch order instead of taking blockIdx.x (SweepArgs::ticket; PMDI_TICKET=0: dealt)
             as.ticket = (h->tun.ticket != 0) ? (int *)h->d_ticket.p : nullptr;
-            e = pmdi_launch_sweep2(as, args(ARGS_SETTLED), C, h->stream2, slot);
+            // ... and, once the heavy chains' workgroups are all placed, keep their slots and draw again until the order is used up:
+            // no slot stands idle while chains are left, whatever share of the workgroup indices its dispatch queue was dealt
+            as.hold = h->hold;
+            as.heavy_left = (int *)h->d_heavy_left.p;
+            e = pmdi_launch_sweep2(as, args(ARGS_SETTLED), C, h->sweep_grid, h->stream2, slot);
             if (e == hipSuccess && idx >= 0) { e = hipEventRecord(h->ring_ev[idx], h->stream2); h->ring_used[idx] = true; }
             if (e != hipSuccess) return fail(PMDI_E_DEVICE, "sweep launch (settled chains): %s", hipGetErrorString(e));
             if (!pl.s2_continue) {
@@ -303,9 +311,11 @@ int launch_sweep_groups(pmdi_handle *h, SweepArgs &a, hipStream_t st)
     }
     if (C > 1 || pl.split) {
         const long long steps = (a.n - a.n1 + 1) * (long long)a.K;
+        if (pl.s2_ok) HIP_TRY(hipMemsetAsync(h->d_heavy_left.p, 0, 4, st));
         e = pmdi_launch_chain_order((const long long *)h->d_cost.p, (int *)h->d_lorder.p, a.stats,
                                     pl.split ? (unsigned char *)h->d_group.p : nullptr, pl.light_ids * steps, C, st,
-                                    pl.s2_ok ? (const int *)h->d_handed.p : nullptr, h->sweep_no + 3 - pl.sticky);
+                                    pl.s2_ok ? (const int *)h->d_handed.p : nullptr, h->sweep_no + 3 - pl.sticky,
+                                    pl.s2_ok ? (int *)h->d_heavy_left.p : nullptr);
         if (e != hipSuccess) return fail(PMDI_E_DEVICE, "chain-order launch: %s", hipGetErrorString(e));
         h->have_order = true;
     }
@@ -445,8 +455,17 @@ int alloc_sweep_state(pmdi_handle *h)
         ((rc = h->d_anclog.ensure((size_t)C * (size_t)n * P * 4)) || (rc = h->d_evpos.ensure((size_t)C * 2 * (size_t)n * 4))))
         return rc;
     // first sweep: every chain is heavy (PMDI_SETTLED=2: every chain starts on the settled-chain kernel -- tests of its hand-back path)
-    if (hipMemset(h->d_group.p, (h->plan.s2_ok && h->tun.settled == 2) ? 0 : 1, (size_t)C) != hipSuccess)
+    const bool all_heavy = !(h->plan.s2_ok && h->tun.settled == 2);
+    if (hipMemset(h->d_group.p, all_heavy ? 1 : 0, (size_t)C) != hipSuccess)
         return fail(PMDI_E_DEVICE, "hipMemset failed");
+    // ... and that many heavy workgroups the first sweep waits for before a settled-chain workgroup keeps its slot
+    const int heavy_first = all_heavy ? C : 0;
+    if ((rc = h->d_heavy_left.ensure(4))) return rc;
+    if (hipMemcpy(h->d_heavy_left.p, &heavy_first, 4, hipMemcpyHostToDevice) != hipSuccess) return fail(PMDI_E_DEVICE, "memcpy failed");
+    if (h->plan.phase_on) {
+        if ((rc = h->d_stamp.ensure((size_t)C * 2 * 8))) return rc;
+        if (hipMemset(h->d_stamp.p, 0, (size_t)C * 2 * 8) != hipSuccess) return fail(PMDI_E_DEVICE, "hipMemset failed");
+    }
     return PMDI_OK;
 }
 
@@ -519,6 +538,7 @@ void pmdi_tuning_from_env(pmdi_tuning *t)
     env("PMDI_KSPLIT", t->ksplit); env("PMDI_REQUEUE_KSPLIT", t->requeue_ksplit); env("PMDI_SPLIT", t->split);
     env("PMDI_HEAVY_T", t->heavy_threads); env("PMDI_TWO_PER_CU", t->two_per_cu); env("PMDI_VERY_HEAVY", t->very_heavy);
     env("PMDI_START_GATE", t->start_gate); env("PMDI_TICKET", t->ticket); env("PMDI_TERMS_CAP", t->terms_cap); env("PMDI_LDS_TARGET", t->lds_target);
+    env("PMDI_HOLD", t->hold); env("PMDI_SWEEP_GRID", t->sweep_grid);
     if (getenv("PMDI_PHASE_TIMERS")) t->phase_timers = 1;
     auto has = [](const char *name, const char *what) { const char *v = getenv(name); return v && strstr(v, what) != nullptr; };
     t->profiled = (has("LD_PRELOAD", "rocprof") || has("ROCP_TOOL_LIBRARIES", "rocprof") || has("HSA_TOOLS_LIB", "rocprof")) ? 1 : 0;
@@ -586,6 +606,15 @@ int pmdi_create(const pmdi_config *cfg, const pmdi_dataset *datasets, pmdi_handl
     h->npairs = K > 1 ? K * (K - 1) / 2 : 1;
     int rc = 0;
     auto bail = [&](int code) { pmdi_destroy(h); return code; };
+    {   // the settled-chain launch: do its workgroups keep their slots, and how many are there (pmdi_tuning::hold, sweep_grid)
+        const int hold = h->tun.hold < 0 ? 1 : h->tun.hold, grid = h->tun.sweep_grid;
+        if (hold > 2) return bail(fail(PMDI_E_ARG, "tuning.hold=%d outside 0..2", hold));
+        if (grid == 0 || grid < -1) return bail(fail(PMDI_E_ARG, "tuning.sweep_grid=%d: at least one workgroup", grid));
+        h->hold = h->tun.ticket != 0 ? hold : 0;        // (slots are kept by drawing again: no ticket, no draw)
+        if (h->hold == 0 && grid > 0 && grid < cfg->n_chains)
+            return bail(fail(PMDI_E_ARG, "tuning.sweep_grid=%d < n_chains=%d with one-shot workgroups (hold = 0, or no ticket): chains would stay unswept", grid, cfg->n_chains));
+        h->sweep_grid = (h->hold == 2 && grid > 0 && grid < cfg->n_chains) ? grid : cfg->n_chains;
+    }
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(PMDI_E_DEVICE, "hipStreamCreate failed"));
 
     for (int k = 0; k < K; ++k)
@@ -656,6 +685,34 @@ int pmdi_sweep_layout(const pmdi_handle *h, int32_t *out32)
 {
     if (!h || !out32) return fail(PMDI_E_ARG, "null argument");
     pmdi_plan_layout32(h->plan, h->start_sig != nullptr, h->d_xcnt.p != nullptr, h->cfg.K, h->cfg.P, out32);
+    return PMDI_OK;
+}
+int pmdi_settled_launch(pmdi_handle *h, int32_t *out4)
+{
+    if (!h || !out4) return fail(PMDI_E_ARG, "null argument");
+    out4[0] = out4[1] = out4[2] = out4[3] = 0;
+    if (!h->plan.s2_ok) return PMDI_OK;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    SweepArgs a;
+    fill_sweep_common(h, a);
+    pmdi_put_tables(h->plan.resume, a);         // (the launch asks for the larger of the two kernels' LDS layouts)
+    int blocks = 0, cus = 0;
+    HIP_TRY(pmdi_sweep2_blocks_per_cu(a, &blocks));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device));
+    out4[0] = h->hold; out4[1] = h->sweep_grid; out4[2] = blocks * cus;
+    if (h->tun.ticket != 0 && h->sweep_no > 0) {
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(&out4[3], h->d_ticket.p, 4, hipMemcpyDeviceToHost));
+    }
+    return PMDI_OK;
+}
+int pmdi_chain_stamps(pmdi_handle *h, int64_t *out)
+{
+    if (!h || !out) return fail(PMDI_E_ARG, "null argument");
+    if (!h->plan.phase_on) return fail(PMDI_E_STATE, "set PMDI_PHASE_TIMERS=1 before pmdi_create");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, h->d_stamp.p, (size_t)h->cfg.n_chains * 2 * 8, hipMemcpyDeviceToHost));
     return PMDI_OK;
 }
 int pmdi_sum_D(const pmdi_handle *h) { return h ? h->sumD : 0; }

@@ -62,8 +62,9 @@ struct pmdi_handle {
     DevBuf d_s_in, d_order, d_Pi, d_logphi, d_flags, d_s_out, d_lw, d_pstar, d_stats, d_err, d_trace;
     DevBuf d_swept_by, d_resume;
     DevBuf d_args[ARGS_COUNT];
-    DevBuf d_usc, d_partstar, d_kstate, d_phase, d_requeue, d_requeue_total, d_handed, d_group, d_cost, d_lorder, d_ticket, d_work, d_anclog, d_evpos, d_xcnt, d_xinc, d_xlab, d_xhdr;
+    DevBuf d_usc, d_partstar, d_kstate, d_phase, d_requeue, d_requeue_total, d_handed, d_group, d_cost, d_lorder, d_ticket, d_heavy_left, d_stamp, d_work, d_anclog, d_evpos, d_xcnt, d_xinc, d_xlab, d_xhdr;
     bool have_order = false;
+    int hold = 0, sweep_grid = 0;       // the settled-chain launch as pmdi_create settled it (pmdi_tuning::hold, sweep_grid; SweepArgs::hold)
     // argument blocks travel through a ring of pinned host slots: the stream-ordered copy is then asynchronous for the host too
     static constexpr int RING = 64;
     SweepArgs *ring = nullptr;

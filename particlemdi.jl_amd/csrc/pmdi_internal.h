@@ -153,6 +153,14 @@ struct SweepArgs {
                                 // position = blockIdx.x
     int *swept_by;              // [chain] which kernel finished the chain's last sweep: 0 general kernel, 1 settled-chain kernel,
                                 // 2 general kernel after the settled-chain kernel gave the chain back; or null
+    int *heavy_left;            // heavy chains of this sweep whose workgroup has not started yet: counted by chain_order_kernel, one
+                                // subtracted by every workgroup of the general kernel's heavy launches that has a chain to sweep.  Null:
+                                // the handle has no settled-chain kernel (or the launch is neither a heavy one nor that kernel's)
+    int hold;                   // settled-chain launch: 0 a workgroup sweeps one chain and ends; 1 it keeps its slot and draws the next
+                                // chain of the launch order once heavy_left <= 0 (a held slot never keeps a heavy chain waiting for
+                                // more than one chain's sweep); 2 it always does (tests).  Needs the ticket
+    long long *stamp;           // [chain][2] phase timers only: when the chain's workgroup took it up and when it was done with it
+                                // (100 MHz counter shared by the whole device), whichever kernel swept it; or null
 };
 
 struct ClusterBatchArgs {
@@ -215,12 +223,14 @@ hipError_t pmdi_launch_sweep(const SweepArgs &a, SweepArgs *d_args, int n_chains
 hipError_t pmdi_sweep_blocks_per_cu(const SweepArgs &a, int T, int *blocks);
 // the settled-chain kernel (pmdi_sweep2.hip; its shapes and LDS layout: pmdi_sweep2_layout.h)
 hipError_t pmdi_sweep2_blocks_per_cu(const SweepArgs &a, int *blocks);
-hipError_t pmdi_launch_sweep2(const SweepArgs &a, SweepArgs *d_args, int n_chains, hipStream_t stream, SweepArgs *staging = nullptr);
+// (grid: workgroups of the launch; fewer than n_chains only where they keep their slots, SweepArgs::hold)
+hipError_t pmdi_launch_sweep2(const SweepArgs &a, SweepArgs *d_args, int n_chains, int grid, hipStream_t stream, SweepArgs *staging = nullptr);
 hipError_t pmdi_launch_cluster_add(const ClusterBatchArgs &a, hipStream_t stream);
 hipError_t pmdi_launch_cluster_logprob(const ClusterBatchArgs &a, hipStream_t stream);
 hipError_t pmdi_launch_cluster_logmarginal(const ClusterBatchArgs &a, hipStream_t stream);
 hipError_t pmdi_launch_chain_order(const long long *cost, int *order, const long long *stats, unsigned char *group_flag,
-                                   long long light_ops_max, int n_chains, hipStream_t stream, const int *handed = nullptr, int sweep_no = 0);
+                                   long long light_ops_max, int n_chains, hipStream_t stream, const int *handed = nullptr, int sweep_no = 0,
+                                   int *heavy_left = nullptr);
 hipError_t pmdi_launch_featsel(const FeatSelArgs &a, int n_chains, hipStream_t stream);
 hipError_t pmdi_launch_psm_counts(const unsigned char *samples, long long S, int K, long long n, long long row_lo, long long row_hi,
                                   int *counts, hipStream_t stream);

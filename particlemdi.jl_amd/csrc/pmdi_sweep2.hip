@@ -26,27 +26,9 @@ namespace {
 template <int K, int PPL, int NW, bool GO>
 __global__ void __launch_bounds__(64 * NW, 2) pmdi_sweep2_kernel(const SweepArgs *__restrict__ ap)
 {
-    const SweepArgs &a = *ap;
-    int bslot = (int)blockIdx.x;
-    if (a.ticket) {
-        // the workgroup's position in the launch order is drawn, not blockIdx.x (SweepArgs::ticket): one atomic per workgroup; the
-        // general kernel's code finds it under 1 + blockIdx.x if this workgroup has to carry its chain on
-        int *tk = (int *)pm2_smem_;
-        if (threadIdx.x == 0) {
-            const int t = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.ticket + 1 + blockIdx.x, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *tk = t;
-        }
-        __syncthreads();
-        bslot = *tk;
-        __syncthreads();
-        if (bslot < 0 || bslot >= a.n_slots) return;
-    }
-    const int chain = a.chain_order ? a.chain_order[bslot] : bslot;
-    // the chains of a sweep are shared out between launches by what their previous sweep looked like (pmdi_api.cpp)
-    if (a.group_flag && ((int)a.group_flag[chain] != a.group_sel || bslot < a.rank_lo || bslot >= a.rank_hi)) return;
-    pmdi_s2::Sweep2<K, PPL, NW, GO> s;
-    s.run(ap, chain);
+    // which chains this workgroup sweeps -- the one at its index, the one it draws, or one after the other until none is left:
+    // pmdi_sweep2_body.h, sweep_slots
+    pmdi_s2::sweep_slots<K, PPL, NW, GO>(ap);
 }
 
 // the instantiations: one per shape of pmdi_s2::shape_for (pmdi_sweep2_layout.h)
@@ -107,10 +89,12 @@ hipError_t pmdi_sweep2_blocks_per_cu(const SweepArgs &a, int *blocks)
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, fn, 64 * nw, lds);
 }
 
-hipError_t pmdi_launch_sweep2(const SweepArgs &a_in, SweepArgs *d_args, int n_chains, hipStream_t stream, SweepArgs *staging)
+hipError_t pmdi_launch_sweep2(const SweepArgs &a_in, SweepArgs *d_args, int n_chains, int grid, hipStream_t stream, SweepArgs *staging)
 {
     SweepArgs a = a_in;
     a.n_slots = n_chains;
+    // (one-shot workgroups sweep one chain each; the position a workgroup drew is kept under 1 + its index: n_chains words)
+    if (grid < 1 || grid > n_chains || (grid < n_chains && !(a.ticket && a.hold == 2))) return hipErrorInvalidValue;
     int nw = 0;
     const void *fn = kernel_for(a.K, a.P, &nw, all_gaussian(a));
     if (!fn) return hipErrorInvalidValue;
@@ -127,7 +111,7 @@ hipError_t pmdi_launch_sweep2(const SweepArgs &a_in, SweepArgs *d_args, int n_ch
     }
     const SweepArgs *ap = d_args;
     void *args[] = {(void *)&ap};
-    e = hipLaunchKernel(fn, dim3((unsigned)n_chains), dim3(64u * (unsigned)nw), args, lds, stream);
+    e = hipLaunchKernel(fn, dim3((unsigned)grid), dim3(64u * (unsigned)nw), args, lds, stream);
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }

@@ -2277,4 +2277,73 @@ template <int K, int PPL, int NW, bool GO> PM2_COLD void hand_over_cold(Sweep2<K
     s.hand_over(pos, fcode, t_start);
 }
 
+// ---- the workgroup of the settled-chain launch: which chains it sweeps ---------------------------------------------------------------
+// A word that other workgroups write, or that the general kernel's code reads back after a hand-over: always through a device-scope
+// read-modify-write (the lane API has no other access that is sure to go to the L2).  word_set: one writer per word.
+PM2_DEV int word_get(int *p) { return pm2_atomic_add(p, 0); }
+PM2_DEV void word_set(int *p, int v) { pm2_atomic_add(p, v - pm2_atomic_add(p, 0)); }
+
+#ifndef PM2_SLOT_HOOK
+#define PM2_SLOT_HOOK() do { } while (0)     // (tests/emu: what the LDS holds when a chain is taken up)
+#endif
+
+// Without a ticket the workgroup sweeps the chain at its own index of the launch order and ends.  With one it DRAWS its position
+// (SweepArgs::ticket) -- the next chain of the order goes to whichever slot of the GPU frees first -- and, SweepArgs::hold, keeps
+// its slot afterwards and draws again until the order is used up: the hardware deals workgroup indices to its 32 dispatch queues
+// statically, so a queue whose chains were short would stand idle while others still hold undispatched indices, and every chain
+// would cost a workgroup's tear-down and dispatch.  hold = 1 keeps the slot only once every heavy chain's workgroup of the sweep
+// (the general kernel's own launch, 512 threads) has started: until then slots turn over one chain at a time, as with hold = 0, and
+// a heavy workgroup never waits for more than one chain's sweep.  Nobody waits for anybody here: a workgroup that may not go
+// round again ends.  run() takes the LDS as it finds it: the previous occupant is another workgroup, a chain of this one, or the
+// general kernel's layout after a hand-over.
+// (out of line: the sweep's register allocation is its own, whatever the loop around it looks like -- inlined into that loop the
+// headline build went from 52 to 70 spill slots)
+template <int K, int PPL, int NW, bool GO>
+PM2_COLD void sweep_chain(const SweepArgs *ap, int chain)
+{
+    // (arguments of a device function arrive in vector registers: both are uniform, and the sweep wants them in scalar ones)
+    const u64 v = (u64)ap;
+    const unsigned lo = (unsigned)PM2_UNI((int)(unsigned)v), hi = (unsigned)PM2_UNI((int)(unsigned)(v >> 32));
+    Sweep2<K, PPL, NW, GO> s;
+    s.run((const SweepArgs *)(((u64)hi << 32) | (u64)lo), PM2_UNI(chain));
+}
+
+template <int K, int PPL, int NW, bool GO>
+PM2_DEV void sweep_slots(const SweepArgs *ap)
+{
+    const auto &a = *ap;
+    const int tid = PM2_TID();
+    int *tk = (int *)PM2_SMEM;
+    for (bool first = true;; first = false) {
+        int bslot = PM2_BID();
+        if (a.ticket) {
+            // one thread draws; the general kernel's code finds the position under 1 + the workgroup's index if it has to carry the
+            // chain on (a chain swept to its end leaves nothing behind that the next draw could not overwrite)
+            if (tid == 0) {
+                int t = -1;
+                if (first || a.hold == 2 || (a.hold == 1 && a.heavy_left && word_get(a.heavy_left) <= 0)) {
+                    t = pm2_atomic_add(a.ticket, 1);
+                    word_set(a.ticket + 1 + PM2_BID(), t);
+                }
+                *tk = t;
+            }
+            PM2_BARRIER();
+            bslot = *tk;
+            PM2_BARRIER();
+        } else if (!first) return;
+        if (bslot < 0 || bslot >= a.n_slots) return;
+        const int chain = a.chain_order ? PM2_G(const int, a.chain_order)[bslot] : bslot;
+        // the chains of a sweep are shared out between launches by what their previous sweep looked like (pmdi_api.cpp)
+        if (a.group_flag && ((int)PM2_G(const unsigned char, a.group_flag)[chain] != a.group_sel || bslot < a.rank_lo || bslot >= a.rank_hi)) {
+            if (a.ticket && a.hold) continue;       // another launch's chain: draw the next one
+            return;
+        }
+        PM2_SLOT_HOOK();
+        if (a.stamp && tid == 0) PM2_G(long long, a.stamp)[(size_t)chain * 2] = PM2_WALLCLOCK();
+        sweep_chain<K, PPL, NW, GO>(ap, chain);
+        if (a.stamp && tid == 0) PM2_G(long long, a.stamp)[(size_t)chain * 2 + 1] = PM2_WALLCLOCK();
+        PM2_BARRIER();          // (the draw above writes LDS that lanes of this chain may still be reading)
+    }
+}
+
 }  // namespace pmdi_s2

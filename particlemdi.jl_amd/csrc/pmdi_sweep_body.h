@@ -1388,6 +1388,8 @@ __device__ __forceinline__ void pmdi_sweep_body(const SweepArgs *__restrict__ ap
     if (a.group_flag && ((int)a.group_flag[chain] != a.group_sel || bslot < a.rank_lo || bslot >= a.rank_hi)) return;
     // ... or this launch sweeps exactly the chains the settled-chain kernel (pmdi_sweep2.hip) gave back, from the start (PMDI_CONTINUE=0)
     if (a.requeue_only && !a.requeue[chain]) return;
+    // a heavy chain's workgroup is in: once all of them are, the settled-chain launch's workgroups keep their slots (SweepArgs::hold)
+    if (a.heavy_left && tid == 0) __hip_atomic_fetch_add(a.heavy_left, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // hand-off area of the split mode: per (chain, parity of the swept observation, dataset): the log-weight increment and
     // the chosen label of every particle; one arrival counter per chain
@@ -1417,7 +1419,10 @@ __device__ __forceinline__ void pmdi_sweep_body(const SweepArgs *__restrict__ ap
     if (tid < PMDI_KMAX_I * 8) sh.wk[tid] = 0;
     if (tid < PMDI_KMAX_I) sh.khint[tid] = 0;
     long long ph_t0 = 0, ph_r0 = 0;
-    if (a.phase && tid == 0) { ph_last = clock64(); ph_t0 = ph_last; ph_r0 = wall_clock64(); }
+    if (a.phase && tid == 0) {
+        ph_last = clock64(); ph_t0 = ph_last; ph_r0 = wall_clock64();
+        if (!RESUME && a.stamp && kd0 == 0) a.stamp[(size_t)chain * 2] = ph_r0;      // (RESUME: the settled-chain kernel's entry keeps the stamps)
+    }
 
     for (int p = tid; p < P; p += T) sh.lw[p] = a.lw_init;
     for (int c = tid; c <= P; c += T) { sh.lead_of[c] = PMDI_INF_I; sh.slot_of[c] = 0; }
@@ -2194,6 +2199,7 @@ __device__ __forceinline__ void pmdi_sweep_body(const SweepArgs *__restrict__ ap
     }
     if (a.phase && tid == 0) {
         sh.ph[14] = clock64() - ph_t0; sh.ph[15] = wall_clock64() - ph_r0;
+        if (!RESUME && a.stamp && kd0 == 0) a.stamp[(size_t)chain * 2 + 1] = ph_r0 + sh.ph[15];
     }
     __syncthreads();
     if (a.phase && tid < 16 && kd0 == 0) a.phase[(size_t)chain * 16 + tid] = sh.ph[tid];
