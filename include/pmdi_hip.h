@@ -1054,6 +1054,79 @@ int pmdi_loo_last(pmdi_loo *a, double *lp, double *ell, int32_t *p_own, int32_t 
 int pmdi_gibbs_run6(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ,
                     pmdi_fusion *fus, pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, void *stream);
 
+/* ---- streaming density accumulator: the log density of the states the chains visit ----
+ * The seventh accumulator.  For every retained state it evaluates the collapsed log likelihood of every dataset given the chain's
+ * allocations and feature flags, the log prior of the allocations given Pi and Phi, and their sum (the quantity Stan calls lp__);
+ * it keeps their traces, the highest-density state every chain has visited, and the sums behind the Rao-Blackwellised feature
+ * relevance.  Like the leave-one-out accumulator it is a child of the handle and reads its datasets, its tables and the null
+ * marginals fnull[g] = -calc_logmarginal(feature g of the one-cluster allocation) that pmdi_create computes.  C = n_chains, K
+ * datasets, N labels, n observations, G = K (K - 1) / 2; one retained state of chain c is s[c][k][i] (0-based), Pi[c][k][.],
+ * feature_flag[c][.] and Phi[c][.] in Phi's pair order (0,1), (0,2), ..., (K-2,K-1).  g = (k, q) numbers the features of all
+ * datasets, sum(D) of them.  Per add, separate IEEE double operations in this order, never fused:
+ *   1. Statistics.  For every (c, k, label l): cn[l], first[l] = the lowest row index holding l (PMDI_INF = 2^31 - 1: none), and per
+ *      feature the statistics of the label's cluster rebuilt from its members in ascending row index WITH EVERY FEATURE ON, as
+ *      src/pmdi.jl:360-364 and pmdi_feature_select do: Gaussian (Sigma, beta) through the gauss_add recurrence, the categorical
+ *      level counts, the NegBinom sum.  A label outside 0..N-1 is a member of nothing and sets the error flag.
+ *   2. lm[l][q] = calc_logmarginal of that cluster's feature q, for every occupied l, with pmdi_feature_select's expressions:
+ *      Gaussian  (-(cn / 2.0 + 0.5)) * log(beta) + LM[cn];   NegBinom  LG[S + 1] - LG[S + (cn + 1 + 1)] + LG[1 + cn];
+ *      Categorical  v = 0.0;  v += LGH[2 mc] - LGH[2 (mc + cn)];  then the levels r = 0..mc-1 ascending,  v += LGH[2 count_r + 1]
+ *      (mc = the column's maximum).  lm of an empty label is 0.0 and enters nothing.
+ *   3. Per feature g, the occupied labels in order of first[l] ascending:
+ *      bf[g] = fnull[g] + 0.0;  bf[g] += lm[l][q]      the log Bayes factor "clustered against one cluster": the bits of
+ *                                                      pmdi_feature_select's feature_prob
+ *      cl[g] = 0.0;             cl[g] += lm[l][q]
+ *   4. ll[c][k] = ((t_0 + t_1) + ...) over the dataset's features ascending,  t_q = flag ? cl[g] : -fnull[g]:  the reference's
+ *      collapsed log marginal of dataset k given its allocations and the chain's flags, as the reference writes it -- Gaussian: the
+ *      normal-inverse-gamma marginal; NegBinom: exact; Categorical: the reference's constant (its Dirichlet-multinomial expression
+ *      with half-integer arguments, kept as written).
+ *   5. Prior of the allocations.  agree[c][p] = #{i : s_a(i) == s_b(i)} for pair p = (a, b).  Z[c] = the sum over the N^K label
+ *      tuples of prod_k Pi[k][c_k] prod_{a<b} (1 + Phi_ab [c_a == c_b]), by the subset recursion the hyper-parameter updates use
+ *      (fill_W, compute_T with ge = Pi, conn_all, zs_all; K = 1: T[1], the sum of Pi).  lprior = 0.0;  for k ascending, l ascending
+ *      with cn > 0:  lprior += (double)cn * log(Pi[c][k][l]);  pairs ascending:  lprior += (double)agree * log(1.0 + Phi);  finally
+ *      lprior -= (double)n * log(Z).
+ *   6. lj[c] = ((ll[c][0] + ll[c][1]) + ...) + lprior[c].
+ *   7. State.  Traces ll [cap][C][K], lprior [cap][C], lj [cap][C]: row T is written (rows never written are 0).
+ *      Best state per chain: best_val [C] (-inf), best_t [C] Int64 (-1), best_s [C][K][n] bytes: if lj[c] > best_val[c] the chain's
+ *      allocations are copied and best_t = T; a tie keeps the earlier state, a NaN never wins.
+ *      Feature sums [sum D], one owner lane per feature, the chains ascending within an add and the adds in order:
+ *      bf_sum += bf;  bf_sq_sum += bf * bf;  p_sum += q (Int64) with pr = 1.0 - 1.0 / exp(bf + 1.0) (src/pmdi.jl:367) and
+ *      q = pr > 0 ? floor(pr * 2^20 + 0.5) : 0;  a bf that is not finite adds 1 to bad[g] instead of all three.  T += 1.
+ * The chains go through steps 1-3 in batches whose stage buffer (lm, 8 sum(D) N bytes per chain) stays within
+ * PMDI_DENSITY_BUDGET_BYTES (pmdi_density_set_budget lowers that for an accumulator -- never raises it -- and at least one chain
+ * goes per batch); everything after is per chain or sequential in the chains, so no result depends on the batching.
+ * create: checked before the device is touched -- 1 <= trace_cap <= INT32_MAX, and 8 trace_cap C (K + 2) and 8 sum(D) N (8 C sum(D) N
+ *   with keep_last) at most PMDI_PREDICT_MAX_BYTES (PMDI_E_ARG).  A child of h: pmdi_destroy(h) is refused (PMDI_E_STATE) while it lives.
+ * add_arrays: device arrays in the layouts of the resident state: s [C][K][n] 0-based int32, Pi [C][K][N], flags [C][sum D] bytes or
+ *   NULL = every feature on, Phi [C][max(1, G)] (K = 1: not read, may be NULL; else a missing Phi is PMDI_E_ARG).  An add with
+ *   T = trace_cap is PMDI_E_STATE and changes nothing.  A label outside 0..N-1 sets a device flag that pmdi_density_get reports as
+ *   PMDI_E_DATA until pmdi_density_reset.
+ * add_gibbs: the current s, Pi, Phi and (with feature selection) feature_flag of every chain of g, a child of the same h.
+ * get: SYNCHRONISES `stream`, then copies to the host arrays that are not NULL (the traces whole, all trace_cap rows).
+ * last: only with keep_last (else PMDI_E_STATE): synchronises the device and copies the last add's cn, first [C][K][N] Int32,
+ *   lm [C][sum D][N], bf, cl [C][sum D], q [C][sum D] Int64, agree [C][max(1, G)] Int64 and logZ [C] to the host arrays that are
+ *   not NULL.  reset: traces and sums zero, no best state, T = 0.
+ * There is no merge: a trace is a sequence in time of one set of chains and has no meaning across accumulators.
+ * One device, not thread-safe, asynchronous on `stream` except create, destroy, get and last; all calls on one accumulator go on
+ * ONE stream. */
+#define PMDI_DENSITY_BUDGET_BYTES 268435456LL /* 2^28 */
+typedef struct pmdi_density pmdi_density;
+int pmdi_density_create(pmdi_handle *h, int64_t trace_cap, int32_t keep_last, pmdi_density **out);
+int pmdi_density_destroy(pmdi_density *a);
+int pmdi_density_reset(pmdi_density *a, void *stream);
+int64_t pmdi_density_samples(const pmdi_density *a);      /* T, the number of adds */
+int pmdi_density_set_budget(pmdi_density *a, int64_t bytes);
+int pmdi_density_add_gibbs(pmdi_density *a, pmdi_gibbs *g, void *stream);
+int pmdi_density_add_arrays(pmdi_density *a, const int32_t *s, const double *Pi, const uint8_t *flags, const double *Phi, void *stream);
+int pmdi_density_get(pmdi_density *a, double *ll, double *lprior, double *lj, double *best_val, int64_t *best_t, uint8_t *best_s,
+                     double *bf_sum, double *bf_sq_sum, int64_t *p_sum, int64_t *bad, void *stream);
+int pmdi_density_last(pmdi_density *a, int32_t *cn, int32_t *first, double *lm, double *bf, double *cl, int64_t *q, int64_t *agree,
+                      double *logZ);
+
+/* pmdi_gibbs_run6 with the seventh accumulator: after every retained local iteration acc, summ, fus, mix, pred, loo, then dens get
+ * their add; any may be NULL, and pmdi_gibbs_run6(g, ..., loo, stream) is pmdi_gibbs_run7(g, ..., loo, NULL, stream). */
+int pmdi_gibbs_run7(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ,
+                    pmdi_fusion *fus, pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, pmdi_density *dens, void *stream);
+
 /* Device pointers of the resident state (zero-copy consumers; layouts of pmdi_sweep_device). */
 typedef struct {
     double *M, *gamma, *gamma0, *Phi, *vZ, *Pi, *log1p_phi, *feature_prob, *logweight;

@@ -27,3 +27,4 @@ from .mixing import MixingAccumulator, MixingSummary  # noqa: F401,E402
 from .predict import (  # noqa: F401,E402
     CoupledPredictiveCounts, PredictiveAccumulator, PredictiveCounts, check_new_rows, observed_masks)
 from .loo import LooAccumulator, LooCounts  # noqa: F401,E402
+from .density import DensityAccumulator, DensityResult  # noqa: F401,E402

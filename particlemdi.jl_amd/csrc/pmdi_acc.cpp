@@ -1,5 +1,5 @@
 // pmdi_acc.cpp -- the streaming accumulators of include/pmdi_hip.h (pmdi_psm_acc_*, pmdi_fusion_*, pmdi_summary_*, pmdi_mixing_*,
-// pmdi_predict_*, pmdi_loo_*) and their driver pmdi_gibbs_run / run2 / run3 / run4 / run5 / run6, which needs nothing of a pmdi_gibbs
+// pmdi_predict_*, pmdi_loo_*, pmdi_density_*) and their driver pmdi_gibbs_run / run2 / ... / run7, which needs nothing of a pmdi_gibbs
 // but the public pmdi_gibbs_step.
 #include "pmdi_host.h"
 
@@ -101,6 +101,22 @@ struct pmdi_loo {
     int64_t T = 0;                       // adds so far
 };
 
+// Streaming density accumulator (pmdi_density_* entry points): a child of the handle whose datasets, tables and null marginals it
+// reads.  One device slab holds what reset zeroes -- the traces, the four feature sums, the error flag; best_val, best_t and
+// best_s, the stage buffers and the last add's values are separate allocations
+struct pmdi_density {
+    pmdi_handle *h = nullptr;
+    int device = 0;
+    DensityArgs da{};                    // everything of an add but its sources
+    bool keep_last = false;
+    char *slab = nullptr;
+    size_t state_bytes = 0;
+    long long per_chain = 0;             // bytes of stage buffers one chain of a batch takes
+    int Cb_alloc = 0;                    // chains per batch the stage buffer was allocated for
+    std::vector<void *> owned;           // device allocations freed in destroy
+    int64_t T = 0;                       // adds so far
+};
+
 namespace {
 
 // the device of a new accumulator: it exists, and is the current one from here on
@@ -197,7 +213,16 @@ int loo_accepts(const pmdi_loo *a, const pmdi_gibbs *g, int64_t n_adds)
     return PMDI_OK;
 }
 
-// device memory of a predictive or leave-one-out accumulator, freed with it
+// what pmdi_density_add_gibbs checks before it touches anything (pmdi_gibbs_run7 asks once, before its first iteration)
+int density_accepts(const pmdi_density *a, const pmdi_gibbs *g, int64_t n_adds)
+{
+    if (g->h != a->h) return fail(PMDI_E_ARG, "the density accumulator was created from another handle than the chains");
+    if (n_adds > (int64_t)a->da.cap - a->T)
+        return fail(PMDI_E_STATE, "%lld + %lld adds pass the trace capacity %d", (long long)a->T, (long long)n_adds, a->da.cap);
+    return PMDI_OK;
+}
+
+// device memory of a predictive, leave-one-out or density accumulator, freed with it
 template <class Acc, class Tp>
 int predict_alloc(Acc *a, Tp **p, size_t count)
 {
@@ -1217,8 +1242,175 @@ int pmdi_loo_last(pmdi_loo *a, double *lp, double *ell, int32_t *p_own, int32_t 
     return PMDI_OK;
 }
 
-int pmdi_gibbs_run6(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
-                    pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, void *stream)
+int pmdi_density_destroy(pmdi_density *a)
+{
+    if (!a) return PMDI_OK;
+    (void)hipSetDevice(a->device);
+    (void)hipDeviceSynchronize();
+    if (a->slab) (void)hipFree(a->slab);
+    for (void *p : a->owned) (void)hipFree(p);
+    if (a->h && a->h->children > 0) a->h->children -= 1;      // (the handle outlives its children: pmdi_destroy refuses otherwise)
+    delete a;
+    return PMDI_OK;
+}
+
+// what reset leaves: traces and sums zero, no best state
+static int density_clear(pmdi_density *a, hipStream_t st)
+{
+    HIP_TRY(hipMemsetAsync(a->slab, 0, a->state_bytes, st));
+    HIP_TRY(hipMemsetAsync(a->da.best_s, 0, (size_t)a->da.C * a->da.K * a->da.n, st));
+    hipError_t e = pmdi_launch_density_clear(a->da, st);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "density-clear launch: %s", hipGetErrorString(e));
+    return PMDI_OK;
+}
+
+int pmdi_density_create(pmdi_handle *h, int64_t trace_cap, int32_t keep_last, pmdi_density **out)
+{
+    if (!h || !out) return fail(PMDI_E_ARG, "null argument");
+    *out = nullptr;
+    const int C = h->cfg.n_chains, K = h->cfg.K, N = h->cfg.N, sumD = h->sumD;
+    const long long n = h->cfg.n;
+    if (trace_cap < 1 || trace_cap > 2147483647LL) return fail(PMDI_E_ARG, "trace_cap=%lld must be in 1..INT32_MAX", (long long)trace_cap);
+    const long double trace_bytes = 8.0L * (long double)trace_cap * C * (K + 2);
+    if (trace_bytes > (long double)PMDI_PREDICT_MAX_BYTES)
+        return fail(PMDI_E_ARG, "the traces (8 trace_cap C (K + 2) = %.0Lf bytes) pass %lld bytes", trace_bytes, (long long)PMDI_PREDICT_MAX_BYTES);
+    const long double lm_bytes = 8.0L * sumD * N;
+    if ((keep_last ? lm_bytes * C : lm_bytes) > (long double)PMDI_PREDICT_MAX_BYTES)
+        return fail(PMDI_E_ARG, "the log marginals (8 %ssum(D) N = %.0Lf bytes) pass %lld bytes", keep_last ? "C " : "",
+                    keep_last ? lm_bytes * C : lm_bytes, (long long)PMDI_PREDICT_MAX_BYTES);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    pmdi_density *a = new (std::nothrow) pmdi_density();
+    if (!a) return fail(PMDI_E_MEMORY, "out of host memory");
+    a->h = h; a->device = h->cfg.device; a->keep_last = keep_last != 0;
+    h->children += 1;
+    DensityArgs &p = a->da;
+    p.C = C; p.K = K; p.N = N; p.sumD = sumD; p.n = n; p.G = K * (K - 1) / 2; p.npairs = p.G > 1 ? p.G : 1; p.cap = (int)trace_cap;
+    for (int k = 0; k < K; ++k) p.ds[k] = h->ds[k];
+    p.fnull = (const double *)h->d_fnull.p;
+    // chains per batch: the stage buffer of one chain is its 8 sum(D) N bytes of log marginals; a batch stays within
+    // PMDI_DENSITY_BUDGET_BYTES
+    a->per_chain = 8LL * sumD * N;
+    long long Cb = PMDI_DENSITY_BUDGET_BYTES / a->per_chain;
+    p.Cb = a->Cb_alloc = (int)(Cb < 1 ? 1 : Cb > C ? C : Cb);
+    p.lm_all = a->keep_last ? 1 : 0;
+    const size_t CKN = (size_t)C * K * N, CD = (size_t)C * sumD;
+    int rc = predict_alloc(a, &p.lm, (size_t)(a->keep_last ? C : p.Cb) * sumD * N);
+    if (!rc) rc = predict_alloc(a, &p.cn, CKN);
+    if (!rc) rc = predict_alloc(a, &p.first, CKN);
+    if (!rc) rc = predict_alloc(a, &p.ord, CKN);
+    if (!rc) rc = predict_alloc(a, &p.nocc, (size_t)C * K);
+    if (!rc) rc = predict_alloc(a, &p.bf, CD);
+    if (!rc) rc = predict_alloc(a, &p.cl, CD);
+    if (!rc) rc = predict_alloc(a, &p.q, CD);
+    if (!rc) rc = predict_alloc(a, &p.agree, (size_t)C * p.npairs);
+    if (!rc) rc = predict_alloc(a, &p.logZ, (size_t)C);
+    if (!rc) rc = predict_alloc(a, &p.take, (size_t)C);
+    if (!rc) rc = predict_alloc(a, &p.best_val, (size_t)C);
+    if (!rc) rc = predict_alloc(a, &p.best_t, (size_t)C);
+    if (!rc) rc = predict_alloc(a, &p.best_s, (size_t)C * K * n);
+    if (rc) { pmdi_density_destroy(a); return rc; }
+    const size_t tc = (size_t)trace_cap * C;
+    a->state_bytes = (tc * (K + 2) + 4 * (size_t)sumD + 1) * 8;
+    hipError_t e = hipMalloc((void **)&a->slab, a->state_bytes);
+    if (e != hipSuccess) { a->slab = nullptr; pmdi_density_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", a->state_bytes, hipGetErrorString(e)); }
+    p.tr_ll = (double *)a->slab;
+    p.tr_lprior = p.tr_ll + tc * K;
+    p.tr_lj = p.tr_lprior + tc;
+    p.bf_sum = p.tr_lj + tc;
+    p.bf_sq_sum = p.bf_sum + sumD;
+    p.p_sum = (long long *)(p.bf_sq_sum + sumD);
+    p.bad = p.p_sum + sumD;
+    p.err = (int *)(p.bad + sumD);
+    if (hipMemset(p.agree, 0, (size_t)C * p.npairs * 8) != hipSuccess || density_clear(a, nullptr) != PMDI_OK || hipDeviceSynchronize() != hipSuccess) {
+        pmdi_density_destroy(a);
+        return fail(PMDI_E_DEVICE, "hipMemset failed");
+    }
+    *out = a;
+    return PMDI_OK;
+}
+
+int pmdi_density_set_budget(pmdi_density *a, int64_t bytes)
+{
+    if (!a || bytes < 0) return fail(PMDI_E_ARG, "bad argument");
+    long long Cb = bytes / a->per_chain;
+    a->da.Cb = (int)(Cb < 1 ? 1 : Cb > a->Cb_alloc ? a->Cb_alloc : Cb);
+    return PMDI_OK;
+}
+
+int pmdi_density_reset(pmdi_density *a, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    if (const int rc = density_clear(a, (hipStream_t)stream)) return rc;
+    a->T = 0;
+    return PMDI_OK;
+}
+
+int64_t pmdi_density_samples(const pmdi_density *a) { return a ? a->T : 0; }
+
+int pmdi_density_add_arrays(pmdi_density *a, const int32_t *s, const double *Pi, const uint8_t *flags, const double *Phi, void *stream)
+{
+    if (!a || !s || !Pi) return fail(PMDI_E_ARG, "null argument");
+    if (a->da.G > 0 && !Phi) return fail(PMDI_E_ARG, "pmdi_density_add_arrays: K >= 2 datasets need Phi");
+    if (a->T >= a->da.cap) return fail(PMDI_E_STATE, "pmdi_density_add_arrays: the traces are full (trace_cap=%d)", a->da.cap);
+    HIP_TRY(hipSetDevice(a->device));
+    DensityArgs p = a->da;
+    p.s = s; p.Pi = Pi; p.flags = flags; p.Phi = Phi; p.T = (int)a->T;
+    hipError_t e = pmdi_launch_density_add(p, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "density-add launch: %s", hipGetErrorString(e));
+    a->T += 1;
+    return PMDI_OK;
+}
+
+int pmdi_density_add_gibbs(pmdi_density *a, pmdi_gibbs *g, void *stream)
+{
+    if (!a || !g) return fail(PMDI_E_ARG, "null argument");
+    if (const int rc = density_accepts(a, g, 1)) return rc;
+    return pmdi_density_add_arrays(a, g->ga.s, g->ga.Pi, g->feature_select ? g->flags : nullptr, g->ga.Phi, stream);
+}
+
+int pmdi_density_get(pmdi_density *a, double *ll, double *lprior, double *lj, double *best_val, int64_t *best_t, uint8_t *best_s,
+                     double *bf_sum, double *bf_sq_sum, int64_t *p_sum, int64_t *bad, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    hipStream_t st = (hipStream_t)stream;
+    const DensityArgs &p = a->da;
+    const size_t tc = (size_t)p.cap * p.C * 8, c8 = (size_t)p.C * 8, d8 = (size_t)p.sumD * 8;
+    int err = 0;
+    void *dst[10] = {ll, lprior, lj, best_val, best_t, best_s, bf_sum, bf_sq_sum, p_sum, bad};
+    const void *src[10] = {p.tr_ll, p.tr_lprior, p.tr_lj, p.best_val, p.best_t, p.best_s, p.bf_sum, p.bf_sq_sum, p.p_sum, p.bad};
+    const size_t bytes[10] = {tc * p.K, tc, tc, c8, c8, (size_t)p.C * p.K * p.n, d8, d8, d8, d8};
+    for (int i = 0; i < 10; ++i)
+        if (dst[i]) HIP_TRY(hipMemcpyAsync(dst[i], src[i], bytes[i], hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&err, p.err, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (err) return fail(PMDI_E_DATA, "a label outside 0..%d was added (pmdi_density_add_arrays); pmdi_density_reset clears the accumulator", p.N - 1);
+    return PMDI_OK;
+}
+
+int pmdi_density_last(pmdi_density *a, int32_t *cn, int32_t *first, double *lm, double *bf, double *cl, int64_t *q, int64_t *agree, double *logZ)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    if (!a->keep_last) return fail(PMDI_E_STATE, "pmdi_density_last: the accumulator was created without keep_last");
+    if (a->T < 1) return fail(PMDI_E_STATE, "pmdi_density_last: nothing was added yet");
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const DensityArgs &p = a->da;
+    const size_t CKN = (size_t)p.C * p.K * p.N, CD = (size_t)p.C * p.sumD;
+    if (cn) HIP_TRY(hipMemcpy(cn, p.cn, CKN * 4, hipMemcpyDeviceToHost));
+    if (first) HIP_TRY(hipMemcpy(first, p.first, CKN * 4, hipMemcpyDeviceToHost));
+    if (lm) HIP_TRY(hipMemcpy(lm, p.lm, CD * p.N * 8, hipMemcpyDeviceToHost));
+    if (bf) HIP_TRY(hipMemcpy(bf, p.bf, CD * 8, hipMemcpyDeviceToHost));
+    if (cl) HIP_TRY(hipMemcpy(cl, p.cl, CD * 8, hipMemcpyDeviceToHost));
+    if (q) HIP_TRY(hipMemcpy(q, p.q, CD * 8, hipMemcpyDeviceToHost));
+    if (agree) HIP_TRY(hipMemcpy(agree, p.agree, (size_t)p.C * p.npairs * 8, hipMemcpyDeviceToHost));
+    if (logZ) HIP_TRY(hipMemcpy(logZ, p.logZ, (size_t)p.C * 8, hipMemcpyDeviceToHost));
+    return PMDI_OK;
+}
+
+int pmdi_gibbs_run7(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
+                    pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, pmdi_density *dens, void *stream)
 {
     if (!g || n_iter < 0) return fail(PMDI_E_ARG, "bad argument");
     if (burnin < 0 || thin < 1) return fail(PMDI_E_ARG, "burnin=%lld must be >= 0 and thin=%lld >= 1", (long long)burnin, (long long)thin);
@@ -1230,6 +1422,7 @@ int pmdi_gibbs_run6(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
     if (mix && (rc = mixing_accepts(mix, g, kept))) return rc;
     if (pred && (rc = predict_accepts(pred, g, kept))) return rc;
     if (loo && (rc = loo_accepts(loo, g, kept))) return rc;
+    if (dens && (rc = density_accepts(dens, g, kept))) return rc;
     for (int64_t t = 1; t <= n_iter; ++t) {
         if ((rc = pmdi_gibbs_step(g, PMDI_STEP_BEGIN, stream)) || (rc = pmdi_gibbs_step(g, PMDI_STEP_HYPERS, stream)) ||
             (rc = pmdi_gibbs_step(g, PMDI_STEP_SWEEP, stream)))
@@ -1243,9 +1436,16 @@ int pmdi_gibbs_run6(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
             if (mix && (rc = pmdi_mixing_add_gibbs(mix, g, stream))) return rc;
             if (pred && (rc = pmdi_predict_add_gibbs(pred, g, stream))) return rc;
             if (loo && (rc = pmdi_loo_add_gibbs(loo, g, stream))) return rc;
+            if (dens && (rc = pmdi_density_add_gibbs(dens, g, stream))) return rc;
         }
     }
     return PMDI_OK;
+}
+
+int pmdi_gibbs_run6(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
+                    pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, void *stream)
+{
+    return pmdi_gibbs_run7(g, n_iter, burnin, thin, acc, summ, fus, mix, pred, loo, nullptr, stream);
 }
 
 int pmdi_gibbs_run5(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,

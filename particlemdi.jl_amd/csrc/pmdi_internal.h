@@ -446,3 +446,41 @@ hipError_t pmdi_launch_loo_add(const LooArgs &a, hipStream_t stream);
 // ours + theirs (device arrays of another accumulator of the same shape), the pair bin by bin: exact
 hipError_t pmdi_launch_loo_merge(const LooArgs &a, const long long *own_b, const long long *new_b, const long long *zero_b,
                                  const double *lcp_b, const double *lcpsq_b, const long long *E_b, const long long *S_b, hipStream_t stream);
+
+// One add of the streaming density accumulator (pmdi_density.hip): the source arrays in the GibbsArgs layouts, the handle's
+// datasets, tables and null marginals, the stage buffers of the add and the accumulator's state.
+struct DensityArgs {
+    int C, K, N, sumD;          // chains, datasets, labels, features of all datasets
+    int G;                      // K (K - 1) / 2 pairs
+    int npairs;                 // max(1, G): the row length of Phi and of agree
+    int cap;                    // rows of the traces
+    int T;                      // adds before this one: the trace row it writes
+    long long n;                // training observations
+    DsetDev ds[PMDI_KMAX_I];    // the handle's datasets: training data and tables
+    const int *s;               // [C][K][n]  0-based labels
+    const double *Pi;           // [C][K][N]
+    const unsigned char *flags; // [C][sumD], or null: every feature on
+    const double *Phi;          // [C][npairs]
+    const double *fnull;        // [sumD]  -(log marginal of the one-cluster allocation): the handle's
+    double *lm;                 // [Cb][sumD][N]  log marginals of one batch of chains (with keep_last: of all chains); 0.0 for an empty label
+    int lm_all;                 // 1: lm holds all C chains, a batch writes its own slice
+    int Cb;                     // chains per batch
+    int *cn, *first;            // [C][K][N]  members of each label, and the lowest row holding it (PMDI_INF_I: none)
+    int *ord;                   // [C][K][N]  the occupied labels by ascending `first`
+    int *nocc;                  // [C][K]     how many
+    double *bf, *cl;            // [C][sumD]  log Bayes factor against one cluster; sum of the labels' log marginals
+    long long *q;               // [C][sumD]  fixed-point probability of the feature (0 where bf is not finite)
+    long long *agree;           // [C][npairs]
+    double *logZ;               // [C]
+    int *take;                  // [C]  1: this add's state is the chain's best so far
+    int *err;                   // set to 1 by a label outside 0..N-1
+    double *tr_ll, *tr_lprior, *tr_lj;          // [cap][C][K], [cap][C], [cap][C]
+    double *best_val;           // [C]
+    long long *best_t;          // [C]
+    unsigned char *best_s;      // [C][K][n]
+    double *bf_sum, *bf_sq_sum; // [sumD]
+    long long *p_sum, *bad;     // [sumD]
+};
+hipError_t pmdi_launch_density_add(const DensityArgs &a, hipStream_t stream);
+// best_val = -inf, best_t = -1 (the rest of a reset is memsets)
+hipError_t pmdi_launch_density_clear(const DensityArgs &a, hipStream_t stream);

@@ -152,7 +152,14 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     N or sets of datasets), the stability of the row's label (own_label) and its outlier score (new_cluster, outliers) -- is returned
     after the predictive counts and before the draws: (counts[, summary][, fusion][, mixing][, predict][, loo][, draws]).
     loo_coupled (keyword only; needs loo): the full conditional carries Phi against the labels the other datasets give the row.
-    Default: on when K > 1; True with one dataset is a ValueError."""
+    Default: on when K > 1; True with one dataset is a ValueError.
+    density (keyword only, default False; True or False, anything else is a ValueError): a seventh accumulator
+    (density.DensityAccumulator, one trace row per retained iteration) takes the same retained iterations and its
+    density.DensityResult -- the traces of every dataset's collapsed log likelihood, of the log prior of the allocations and of the
+    log joint (trace, rhat), the highest-density state every chain visited (best, best_per_chain: candidates and starts for
+    psm.best_sampled_allocation and minimise_expected_loss) and the Rao-Blackwellised feature relevance (feature_bayes_factor,
+    feature_probs; featureSelect need not be on) -- is returned after the leave-one-out counts and before the draws:
+    (counts[, summary][, fusion][, mixing][, predict][, loo][, density][, draws])."""
     from .fusion import FusionAccumulator, _group_masks
     fusion = more.pop("fusion", False)
     mixing = more.pop("mixing", False)
@@ -162,6 +169,7 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     predict_impute = bool(more.pop("predict_impute", False))
     loo = bool(more.pop("loo", False))
     loo_coupled = more.pop("loo_coupled", None)
+    density = more.pop("density", False)
     if more:
         raise TypeError(f"pmdi_pooled() got an unexpected keyword argument {next(iter(more))!r}")
     from .psm import PsmAccumulator, _DeviceInt32View, retained_iterations
@@ -169,7 +177,9 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     from .mixing import MixingAccumulator
     from .predict import PredictiveAccumulator, check_new_rows
     from .loo import LooAccumulator
+    from .density import DensityAccumulator
     K, n_obs, names = _check_arguments(dataFiles, dataTypes, N, particles, rho)
+    _need(density is True or density is False, "density must be True or False")
     if loo_coupled is not None and not loo:
         raise ValueError("loo_coupled needs loo=True")
     _need(K > 1 or not loo_coupled, "loo_coupled needs two or more datasets")
@@ -211,7 +221,7 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
         summ = SummaryAccumulator(n_chains, K, N, n_obs, sumD=sweeper.sumD if featureSelect else 0,
                                   trace_cap=len(retained_iterations(iter, burnin, thin)), device=device)
     fus = FusionAccumulator(K, n_obs, n_labels=N, groups=fusion_groups, matrix=fusion_matrix, device=device) if fusion else None
-    mix = pred = loo_acc = None
+    mix = pred = loo_acc = dens = None
     try:
         if maxlag:      # ((maxlag + 1) n_chains K n bytes: inside the try, so that a failed allocation still closes the handles)
             mix = MixingAccumulator(n_chains, K, N, n_obs, maxlag=maxlag, device=device)
@@ -219,7 +229,9 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
             pred = PredictiveAccumulator(sweeper, predict, coupled=predict_coupled, observed=predict_observed, impute=predict_impute)
         if loo:
             loo_acc = LooAccumulator(sweeper, coupled=loo_coupled)
-        g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ, fusion=fus, mixing=mix, predict=pred, loo=loo_acc)
+        if density:
+            dens = DensityAccumulator(sweeper, trace_cap=len(retained_iterations(iter, burnin, thin)))
+        g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ, fusion=fus, mixing=mix, predict=pred, loo=loo_acc, density=dens)
         g.results()                      # synchronises; raises on a kernel-side error of any chain
         counts = acc.counts(names=names)   # (the view keeps the accumulator alive)
         out = (counts,) if summ is None else (counts, summ.summary(names=names, feature_D=sweeper.D))
@@ -231,6 +243,8 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
             out += (pred.result(names=names),)
         if loo_acc is not None:
             out += (loo_acc.result(names=names),)
+        if dens is not None:
+            out += (dens.result(names=names),)
         if final_allocations:
             import torch
             dev = torch.device("cuda", int(device))
@@ -246,5 +260,7 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
             pred.close()      # (a child of the sweeper's handle: before it)
         if loo_acc is not None:
             loo_acc.close()
+        if dens is not None:
+            dens.close()
         g.close()
         sweeper.close()
