@@ -1127,6 +1127,70 @@ int pmdi_density_last(pmdi_density *a, int32_t *cn, int32_t *first, double *lm, 
 int pmdi_gibbs_run7(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ,
                     pmdi_fusion *fus, pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, pmdi_density *dens, void *stream);
 
+/* ---- streaming agreement accumulator: the adjusted Rand index between datasets and against known classes ----
+ * The eighth accumulator.  For every retained state of every chain it compares the clusterings of every two datasets with each
+ * other, and every dataset's clustering with each of R reference labellings known in advance, through the contingency table of
+ * the two sides; it keeps per chain the sums behind the posterior mean of the adjusted Rand index (ARI), of the Rand index, of the
+ * variation of information (VI) and of the mutual information, a histogram and a trace of the ARI.  It is label-free: two datasets
+ * with the same partition under different names agree fully.  It reads no handle: C = n_chains, K datasets, N labels, n
+ * observations, G = K (K - 1) / 2; one retained state of chain c is s[c][k][i] (0-based).
+ *   Comparisons.  Q = G + R K of them per chain.  q < G: the dataset pairs (a < b) in Phi's order (0,1), (0,2), ..., (K-2,K-1),
+ *     x = the labels of a, y = the labels of b.  q = G + r K + k: x = the labels of dataset k, y = the classes of reference r.
+ *   References.  ref [R][n] Int32, 0 <= R <= 8 (R = 0: ref is not read and may be NULL).  The classes of a reference are 0..Gr-1 with
+ *     Gr <= 255; -1 = the class of the observation is unknown: it takes no part in the comparisons with that reference.  The
+ *     labellings are copied to the device once, as bytes (255 for unknown).
+ *   Per add, chain c and comparison q, exact Int64: an observation counts iff its x label is in 0..N-1 and its y label is in 0..N-1
+ *     (a pair) or known (a reference).  Over the n_q observations that count, with n_ab = #{i : x_i = a, y_i = b}, n_a. and n_.b the
+ *     row and column sums of that table, C(v, 2) = v (v - 1) / 2 and L the fixed-point log2 of pmdi_psm_refine_vi_device
+ *     (pmdi_vi_log2_table; v L(v) = 0 for v = 0):
+ *       both = sum_ab C(n_ab, 2)      jl = sum_ab n_ab L(n_ab)
+ *       px = sum_a C(n_a., 2)         py = sum_b C(n_.b, 2)
+ *       hx = sum_a n_a. L(n_a.)       hy = sum_b n_.b L(n_.b)         T2 = C(n_q, 2)
+ *     For a reference the x marginal is therefore the histogram of the dataset's labels over the labelled observations only.  A
+ *     label of s outside 0..N-1 takes part in nothing and sets the error flag; n_q and both marginals are then the sums of the
+ *     cells that remain: every marginal is a row or column sum of n_ab, always.
+ *   ari, separate IEEE double operations in this order, never fused (the lines of the mixing accumulator):  T2 == 0: ari = 1.0;
+ *     else  e = (double)px * (double)py;  e = e / (double)T2;  m = (double)px + (double)py;  m = m / 2.0;  den = m - e;
+ *     den == 0.0: ari = 1.0;  else  ari = ((double)both - e) / den.
+ *   State (every word owned by one lane of one launch, or an integer atomic; the launches ordered on the accumulator's stream):
+ *     rand_num [C][Q] Int64    += T2 + 2 both - px - py                 the pairs of observations on which x and y agree
+ *     ari_sum  [C][Q] Float64  = ari_sum + ari                          in the order of the adds
+ *     ari_sq   [C][Q] Float64  = ari_sq + ari * ari
+ *     vi_sum   [C][Q] Int64    += hx + hy - 2 jl                        VI in bits = this / (2^30 n_q)
+ *     mi_sum   [C][Q] Int64    += n_q L(n_q) - hx - hy + jl             (0 L(0) = 0)
+ *     ari_hist [Q][256] Int64  += 1 in bin min(255, max(0, (int)floor((ari + 1.0) * 128.0))), one per (chain, q)
+ *     trace    [trace_cap][Q] Float64   row T = ((0.0 + ari_0) + ari_1) + ... + ari_{C-1}, the chains in order; an add with
+ *                                       T >= trace_cap writes no row (as the summary accumulator's trace)
+ *     last     [C][Q][7] Int64          both, jl, px, py, hx, hy, n_q of the latest add
+ * create: checked before the device is touched (PMDI_E_ARG) -- 1 <= K <= PMDI_KMAX_I, 2 <= N <= 255, 1 <= n <= 65535, n_chains >= 1
+ *   (n_chains K <= INT32_MAX), 0 <= R <= 8, every reference value in -1..254, Q >= 1 (one dataset needs a reference),
+ *   0 <= trace_cap <= INT32_MAX.  `device` must exist (PMDI_E_DEVICE: no CPU path).
+ * add_arrays: s, a device array [C][K][n] Int32.  add_gibbs: the current allocations of every chain of g, which must have the
+ *   accumulator's n_chains, K, N, n and device (PMDI_E_ARG otherwise, nothing changed).
+ * get: SYNCHRONISES `stream`, then copies to the host arrays that are not NULL; PMDI_E_DATA (after the copies) if a label outside
+ *   0..N-1 was added since the last reset.  last: synchronises `stream` and copies last.  reset: every array zero, T = 0.
+ * samples: T, the number of adds (0 for NULL); destroy(NULL) is PMDI_OK; a NULL accumulator is PMDI_E_ARG everywhere else.
+ * There is no merge on the device: the state is per chain, and the chains of two accumulators are pooled by concatenation.
+ * One device, not thread-safe, asynchronous on `stream` except create, destroy, get and last; all calls on one accumulator go on
+ * ONE stream. */
+typedef struct pmdi_agreement pmdi_agreement;
+int pmdi_agreement_create(int32_t device, int32_t n_chains, int32_t K, int32_t N, int64_t n, int32_t R, const int32_t *ref,
+                          int64_t trace_cap, pmdi_agreement **out);
+int pmdi_agreement_destroy(pmdi_agreement *a);
+int pmdi_agreement_reset(pmdi_agreement *a, void *stream);
+int pmdi_agreement_add_gibbs(pmdi_agreement *a, pmdi_gibbs *g, void *stream);
+int pmdi_agreement_add_arrays(pmdi_agreement *a, const int32_t *s, void *stream);
+int64_t pmdi_agreement_samples(const pmdi_agreement *a);      /* T, the number of adds */
+int pmdi_agreement_get(pmdi_agreement *a, int64_t *rand_num, double *ari_sum, double *ari_sq, int64_t *vi_sum, int64_t *mi_sum,
+                       int64_t *ari_hist, double *trace, void *stream);
+int pmdi_agreement_last(pmdi_agreement *a, int64_t *last, void *stream);
+
+/* pmdi_gibbs_run7 with the eighth accumulator: after every retained local iteration acc, summ, fus, mix, pred, loo, dens, then agr
+ * get their add; any may be NULL, and pmdi_gibbs_run7(g, ..., dens, stream) is pmdi_gibbs_run8(g, ..., dens, NULL, stream). */
+int pmdi_gibbs_run8(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ,
+                    pmdi_fusion *fus, pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, pmdi_density *dens, pmdi_agreement *agr,
+                    void *stream);
+
 /* Device pointers of the resident state (zero-copy consumers; layouts of pmdi_sweep_device). */
 typedef struct {
     double *M, *gamma, *gamma0, *Phi, *vZ, *Pi, *log1p_phi, *feature_prob, *logweight;

@@ -28,3 +28,4 @@ from .predict import (  # noqa: F401,E402
     CoupledPredictiveCounts, PredictiveAccumulator, PredictiveCounts, check_new_rows, observed_masks)
 from .loo import LooAccumulator, LooCounts  # noqa: F401,E402
 from .density import DensityAccumulator, DensityResult  # noqa: F401,E402
+from .agreement import AgreementAccumulator, AgreementSummary  # noqa: F401,E402

@@ -13,7 +13,7 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("PMDI_LIB_PATH") or os.path.join(_PKG, "libpmdi_hip.so")   # override: A/B builds only
-_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_fusion.hip", "pmdi_summary.hip", "pmdi_mixing.hip", "pmdi_predict.hip", "pmdi_predict_coupled.hip", "pmdi_loo.hip", "pmdi_density.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_psm_refine_vi.hip", "pmdi_partdist.hip", "pmdi_partdist_refine.hip", "pmdi_psm_blocksum.hip", "pmdi_data_groupsum.hip", "pmdi_api.cpp", "pmdi_plan.cpp", "pmdi_acc.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
+_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_fusion.hip", "pmdi_summary.hip", "pmdi_mixing.hip", "pmdi_predict.hip", "pmdi_predict_coupled.hip", "pmdi_loo.hip", "pmdi_density.hip", "pmdi_agreement.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_psm_refine_vi.hip", "pmdi_partdist.hip", "pmdi_partdist_refine.hip", "pmdi_psm_blocksum.hip", "pmdi_data_groupsum.hip", "pmdi_api.cpp", "pmdi_plan.cpp", "pmdi_acc.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
 # every header decides when to rebuild: a new one cannot be forgotten
 _HEADERS = sorted(glob.glob(os.path.join(_PKG, "csrc", "*.h"))) + [os.path.join(_ROOT, "include", "pmdi_hip.h")]
 
@@ -63,6 +63,8 @@ EXPORTS = [
     "pmdi_settled_launch", "pmdi_chain_stamps",
     "pmdi_density_create", "pmdi_density_destroy", "pmdi_density_reset", "pmdi_density_samples", "pmdi_density_set_budget",
     "pmdi_density_add_gibbs", "pmdi_density_add_arrays", "pmdi_density_get", "pmdi_density_last", "pmdi_gibbs_run7",
+    "pmdi_agreement_create", "pmdi_agreement_destroy", "pmdi_agreement_reset", "pmdi_agreement_add_gibbs", "pmdi_agreement_add_arrays",
+    "pmdi_agreement_samples", "pmdi_agreement_get", "pmdi_agreement_last", "pmdi_gibbs_run8",
 ]
 
 
@@ -272,6 +274,23 @@ def lib():
     L.pmdi_gibbs_run6.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]
     L.pmdi_gibbs_run7.restype = C.c_int
     L.pmdi_gibbs_run7.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pmdi_gibbs_run8.restype = C.c_int
+    L.pmdi_gibbs_run8.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pmdi_agreement_create.restype = C.c_int
+    L.pmdi_agreement_create.argtypes = [i32, i32, i32, i32, i64, i32, vp, i64, C.POINTER(vp)]
+    L.pmdi_agreement_destroy.argtypes = [vp]
+    L.pmdi_agreement_reset.restype = C.c_int
+    L.pmdi_agreement_reset.argtypes = [vp, vp]
+    L.pmdi_agreement_samples.restype = i64
+    L.pmdi_agreement_samples.argtypes = [vp]
+    L.pmdi_agreement_add_gibbs.restype = C.c_int
+    L.pmdi_agreement_add_gibbs.argtypes = [vp, vp, vp]
+    L.pmdi_agreement_add_arrays.restype = C.c_int
+    L.pmdi_agreement_add_arrays.argtypes = [vp, vp, vp]
+    L.pmdi_agreement_get.restype = C.c_int
+    L.pmdi_agreement_get.argtypes = [vp] + [vp] * 7 + [vp]
+    L.pmdi_agreement_last.restype = C.c_int
+    L.pmdi_agreement_last.argtypes = [vp, vp, vp]
     L.pmdi_density_create.restype = C.c_int
     L.pmdi_density_create.argtypes = [vp, i64, i32, C.POINTER(vp)]
     L.pmdi_density_destroy.argtypes = [vp]
@@ -489,7 +508,7 @@ class _Handle:
 
 class _Accumulator(_Handle):
     """What the streaming accumulators (psm.PsmAccumulator, fusion.FusionAccumulator, summary.SummaryAccumulator, mixing.MixingAccumulator,
-    predict.PredictiveAccumulator, loo.LooAccumulator, density.DensityAccumulator) share: the
+    predict.PredictiveAccumulator, loo.LooAccumulator, density.DensityAccumulator, agreement.AgreementAccumulator) share: the
     entry points `_prefix`_destroy / _reset / _add_gibbs / _samples, and every call on the current torch stream of `self.device`."""
 
     def _stream(self):
@@ -805,18 +824,20 @@ class Gibbs(_Handle):
                                         C.c_void_p(stream) if stream else None))
 
     def run(self, n_iter, burnin=0, thin=1, acc=None, stream=None, summary=None, fusion=None, mixing=None, predict=None, loo=None,
-            density=None):
-        """pmdi_gibbs_run7: n_iter iterations; after local iteration t = 1..n_iter the state of every chain is added to `acc` (a
+            density=None, agreement=None):
+        """pmdi_gibbs_run8: n_iter iterations; after local iteration t = 1..n_iter the state of every chain is added to `acc` (a
         psm.PsmAccumulator: the allocations), to `summary` (a summary.SummaryAccumulator: M, Phi, cluster counts, feature
         flags), to `fusion` (a fusion.FusionAccumulator: which observations the datasets cluster alike), to `mixing` (a
         mixing.MixingAccumulator: the autocorrelation inside every chain), to `predict` (a predict.PredictiveAccumulator:
-        where held-out rows fall), to `loo` (a loo.LooAccumulator: how well every training row is explained by the others) and to
-        `density` (a density.DensityAccumulator: the log density of the state) iff t > burnin and (t - burnin - 1) % thin == 0
+        where held-out rows fall), to `loo` (a loo.LooAccumulator: how well every training row is explained by the others), to
+        `density` (a density.DensityAccumulator: the log density of the state) and to `agreement` (an
+        agreement.AgreementAccumulator: how alike the datasets cluster, and how alike known classes) iff t > burnin and (t - burnin - 1) % thin == 0
         (psm.retained_iterations).  Any may be None."""
-        _check(lib().pmdi_gibbs_run7(self.h, int(n_iter), int(burnin), int(thin), acc.h if acc is not None else None,
+        _check(lib().pmdi_gibbs_run8(self.h, int(n_iter), int(burnin), int(thin), acc.h if acc is not None else None,
                                      summary.h if summary is not None else None, fusion.h if fusion is not None else None,
                                      mixing.h if mixing is not None else None, predict.h if predict is not None else None,
                                      loo.h if loo is not None else None, density.h if density is not None else None,
+                                     agreement.h if agreement is not None else None,
                                      C.c_void_p(stream) if stream else None))
 
     def pack_samples(self, out_ptr, stream=None):

@@ -1,5 +1,5 @@
 // pmdi_acc.cpp -- the streaming accumulators of include/pmdi_hip.h (pmdi_psm_acc_*, pmdi_fusion_*, pmdi_summary_*, pmdi_mixing_*,
-// pmdi_predict_*, pmdi_loo_*, pmdi_density_*) and their driver pmdi_gibbs_run / run2 / ... / run7, which needs nothing of a pmdi_gibbs
+// pmdi_predict_*, pmdi_loo_*, pmdi_density_*, pmdi_agreement_*) and their driver pmdi_gibbs_run / run2 / ... / run8, which needs nothing of a pmdi_gibbs
 // but the public pmdi_gibbs_step.
 #include "pmdi_host.h"
 
@@ -117,6 +117,21 @@ struct pmdi_density {
     int64_t T = 0;                       // adds so far
 };
 
+// Streaming agreement accumulator (pmdi_agreement_* entry points): one device slab -- the arrays of include/pmdi_hip.h one after
+// the other (8-byte elements), the error flag and the last add's integers (what reset zeroes), then the reference bytes and the
+// label bytes of an add
+enum { AGR_RAND, AGR_ARI, AGR_ARISQ, AGR_VI, AGR_MI, AGR_HIST, AGR_TRACE, AGR_ARRAYS };      // the order of pmdi_agreement_get's arguments
+struct pmdi_agreement {
+    int device = 0;
+    AgreementArgs aa{};                  // everything of an add but its source
+    long long trace_cap = 0;
+    char *slab = nullptr;
+    size_t state_bytes = 0;              // what reset zeroes: every array, the error flag and last
+    size_t count[AGR_ARRAYS] = {};       // elements of each array ...
+    char *at[AGR_ARRAYS] = {};           // ... and where it starts in the slab (double: ari_sum, ari_sq, trace; else int64)
+    int64_t T = 0;                       // adds so far
+};
+
 namespace {
 
 // the device of a new accumulator: it exists, and is the current one from here on
@@ -219,6 +234,19 @@ int density_accepts(const pmdi_density *a, const pmdi_gibbs *g, int64_t n_adds)
     if (g->h != a->h) return fail(PMDI_E_ARG, "the density accumulator was created from another handle than the chains");
     if (n_adds > (int64_t)a->da.cap - a->T)
         return fail(PMDI_E_STATE, "%lld + %lld adds pass the trace capacity %d", (long long)a->T, (long long)n_adds, a->da.cap);
+    return PMDI_OK;
+}
+
+// what pmdi_agreement_add_gibbs checks before it touches anything (pmdi_gibbs_run8 asks once, before its first iteration)
+int agreement_accepts(const pmdi_agreement *a, const pmdi_gibbs *g, int64_t n_adds)
+{
+    const pmdi_config &c = g->h->cfg;
+    const AgreementArgs &m = a->aa;
+    if (c.n_chains != m.C || c.K != m.K || c.N != m.N || c.n != m.n)
+        return fail(PMDI_E_ARG, "the accumulator holds n_chains=%d K=%d N=%d n=%lld, the chains n_chains=%d K=%d N=%d n=%lld", m.C, m.K, m.N,
+                    m.n, c.n_chains, c.K, c.N, (long long)c.n);
+    if (c.device != a->device) return fail(PMDI_E_ARG, "the chains live on device %d, the accumulator on device %d", c.device, a->device);
+    if (n_adds > 2147483647LL - a->T) return fail(PMDI_E_ARG, "%lld + %lld adds pass INT32_MAX", (long long)a->T, (long long)n_adds);
     return PMDI_OK;
 }
 
@@ -1409,8 +1437,140 @@ int pmdi_density_last(pmdi_density *a, int32_t *cn, int32_t *first, double *lm, 
     return PMDI_OK;
 }
 
-int pmdi_gibbs_run7(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
-                    pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, pmdi_density *dens, void *stream)
+int pmdi_agreement_destroy(pmdi_agreement *a)
+{
+    if (!a) return PMDI_OK;
+    (void)hipSetDevice(a->device);
+    (void)hipDeviceSynchronize();
+    if (a->slab) (void)hipFree(a->slab);
+    delete a;
+    return PMDI_OK;
+}
+
+int pmdi_agreement_create(int32_t device, int32_t n_chains, int32_t K, int32_t N, int64_t n, int32_t R, const int32_t *ref, int64_t trace_cap,
+                          pmdi_agreement **out)
+{
+    if (!out) return fail(PMDI_E_ARG, "null argument");
+    *out = nullptr;
+    if (K < 1 || K > PMDI_KMAX_I) return fail(PMDI_E_ARG, "K=%d outside 1..%d", K, PMDI_KMAX_I);
+    if (N < 2 || N > 255) return fail(PMDI_E_ARG, "N=%d outside 2..255", N);
+    if (n < 1 || n > 65535) return fail(PMDI_E_ARG, "n=%lld outside 1..65535", (long long)n);
+    if (R < 0 || R > 8) return fail(PMDI_E_ARG, "R=%d reference labellings outside 0..8", R);
+    if (R > 0 && !ref) return fail(PMDI_E_ARG, "R=%d reference labellings, but ref is null", R);
+    if (n_chains < 1 || (long long)n_chains * K > 2147483647LL) return fail(PMDI_E_ARG, "n_chains=%d: need n_chains >= 1 and n_chains * K <= INT32_MAX", n_chains);
+    if (trace_cap < 0 || trace_cap > 2147483647LL) return fail(PMDI_E_ARG, "trace_cap=%lld outside 0..INT32_MAX (the bound of the number of adds)", (long long)trace_cap);
+    const int G = K * (K - 1) / 2, Q = G + R * K, np = (int)((n + 31) / 32 * 32);
+    if (Q < 1) return fail(PMDI_E_ARG, "nothing to compare: one dataset needs a reference labelling");
+    int gr[8] = {1, 1, 1, 1, 1, 1, 1, 1};
+    for (int r = 0; r < R; ++r)
+        for (long long i = 0; i < n; ++i) {
+            const int v = ref[(long long)r * n + i];
+            if (v < -1 || v > 254) return fail(PMDI_E_ARG, "ref[%d][%lld]=%d outside -1..254 (-1: unknown)", r, i, v);
+            if (v + 1 > gr[r]) gr[r] = v + 1;
+        }
+    const size_t CQ = (size_t)n_chains * Q, CK = (size_t)n_chains * K;
+    const size_t counts[AGR_ARRAYS] = {CQ, CQ, CQ, CQ, CQ, (size_t)Q * 256, (size_t)trace_cap * Q};
+    // 8-byte elements: the arrays, err, last; then the reference bytes and the label bytes (256-byte aligned)
+    long double total = 1.0L + 7.0L * (long double)CQ;
+    for (size_t c : counts) total += (long double)c;
+    total = total * 8.0L + 256.0L + ((long double)R + (long double)CK) * np;
+    if (total > 4.0e18L) return fail(PMDI_E_MEMORY, "the accumulator would need more than 4e18 bytes");
+    std::vector<unsigned char> ref_bytes((size_t)R * np, (unsigned char)255);
+    for (int r = 0; r < R; ++r)
+        for (long long i = 0; i < n; ++i) {
+            const int v = ref[(long long)r * n + i];
+            if (v >= 0) ref_bytes[(size_t)r * np + i] = (unsigned char)v;
+        }
+    if (const int rc = open_device(device)) return rc;
+    pmdi_agreement *a = new (std::nothrow) pmdi_agreement();
+    if (!a) return fail(PMDI_E_MEMORY, "out of host memory");
+    a->device = device; a->trace_cap = trace_cap;
+    AgreementArgs &m = a->aa;
+    m.C = n_chains; m.K = K; m.N = N; m.R = R; m.G = G; m.Q = Q; m.np = np; m.n = n;
+    for (int r = 0; r < 8; ++r) m.gr[r] = gr[r];
+    a->state_bytes = 8 + CQ * 7 * 8;
+    for (int i = 0; i < AGR_ARRAYS; ++i) { a->count[i] = counts[i]; a->state_bytes += counts[i] * 8; }
+    const size_t ref_at = (a->state_bytes + 255) & ~(size_t)255, bytes_at = ref_at + (((size_t)R * np + 255) & ~(size_t)255);
+    const size_t bytes = bytes_at + CK * np;
+    hipError_t e = hipMalloc((void **)&a->slab, bytes);
+    if (e != hipSuccess) { a->slab = nullptr; pmdi_agreement_destroy(a); return fail(PMDI_E_MEMORY, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e)); }
+    if (hipMemset(a->slab, 0, a->state_bytes) != hipSuccess ||
+        (R > 0 && hipMemcpy(a->slab + ref_at, ref_bytes.data(), ref_bytes.size(), hipMemcpyHostToDevice) != hipSuccess)) {
+        pmdi_agreement_destroy(a);
+        return fail(PMDI_E_DEVICE, "hipMemset / hipMemcpy failed");
+    }
+    char *p = a->slab;
+    for (int i = 0; i < AGR_ARRAYS; ++i) { a->at[i] = p; p += a->count[i] * 8; }
+    m.err = (int *)p; p += 8;
+    m.last = (long long *)p;
+    m.ref = (const unsigned char *)a->slab + ref_at;
+    m.bytes = (unsigned char *)a->slab + bytes_at;
+    m.rand_num = (long long *)a->at[AGR_RAND]; m.ari_sum = (double *)a->at[AGR_ARI]; m.ari_sq = (double *)a->at[AGR_ARISQ];
+    m.vi_sum = (long long *)a->at[AGR_VI]; m.mi_sum = (long long *)a->at[AGR_MI]; m.ari_hist = (long long *)a->at[AGR_HIST];
+    *out = a;
+    return PMDI_OK;
+}
+
+int pmdi_agreement_reset(pmdi_agreement *a, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipMemsetAsync(a->slab, 0, a->state_bytes, (hipStream_t)stream));
+    a->T = 0;
+    return PMDI_OK;
+}
+
+int pmdi_agreement_add_arrays(pmdi_agreement *a, const int32_t *s, void *stream)
+{
+    if (!a || !s) return fail(PMDI_E_ARG, "null argument");
+    if (a->T >= 2147483647LL) return fail(PMDI_E_ARG, "%lld + 1 adds pass INT32_MAX", (long long)a->T);
+    HIP_TRY(hipSetDevice(a->device));
+    AgreementArgs m = a->aa;
+    m.s = s;
+    double *trace_row = a->T < a->trace_cap ? (double *)a->at[AGR_TRACE] + (size_t)a->T * m.Q : nullptr;
+    hipError_t e = pmdi_launch_agreement_add(m, trace_row, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "agreement-add launch: %s", hipGetErrorString(e));
+    a->T += 1;
+    return PMDI_OK;
+}
+
+int pmdi_agreement_add_gibbs(pmdi_agreement *a, pmdi_gibbs *g, void *stream)
+{
+    if (!a || !g) return fail(PMDI_E_ARG, "null argument");
+    if (const int rc = agreement_accepts(a, g, 1)) return rc;
+    return pmdi_agreement_add_arrays(a, g->ga.s, stream);
+}
+
+int64_t pmdi_agreement_samples(const pmdi_agreement *a) { return a ? a->T : 0; }
+
+int pmdi_agreement_get(pmdi_agreement *a, int64_t *rand_num, double *ari_sum, double *ari_sq, int64_t *vi_sum, int64_t *mi_sum,
+                       int64_t *ari_hist, double *trace, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    hipStream_t st = (hipStream_t)stream;
+    int err = 0;
+    void *const dst[AGR_ARRAYS] = {rand_num, ari_sum, ari_sq, vi_sum, mi_sum, ari_hist, trace};
+    for (int i = 0; i < AGR_ARRAYS; ++i)
+        if (dst[i] && a->count[i]) HIP_TRY(hipMemcpyAsync(dst[i], a->at[i], a->count[i] * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&err, a->aa.err, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (err) return fail(PMDI_E_DATA, "a label outside 0..%d was added (pmdi_agreement_add_arrays); pmdi_agreement_reset clears the accumulator", a->aa.N - 1);
+    return PMDI_OK;
+}
+
+int pmdi_agreement_last(pmdi_agreement *a, int64_t *last, void *stream)
+{
+    if (!a || !last) return fail(PMDI_E_ARG, "null argument");
+    HIP_TRY(hipSetDevice(a->device));
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(last, a->aa.last, (size_t)a->aa.C * a->aa.Q * 7 * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PMDI_OK;
+}
+
+int pmdi_gibbs_run8(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
+                    pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, pmdi_density *dens, pmdi_agreement *agr, void *stream)
 {
     if (!g || n_iter < 0) return fail(PMDI_E_ARG, "bad argument");
     if (burnin < 0 || thin < 1) return fail(PMDI_E_ARG, "burnin=%lld must be >= 0 and thin=%lld >= 1", (long long)burnin, (long long)thin);
@@ -1423,6 +1583,7 @@ int pmdi_gibbs_run7(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
     if (pred && (rc = predict_accepts(pred, g, kept))) return rc;
     if (loo && (rc = loo_accepts(loo, g, kept))) return rc;
     if (dens && (rc = density_accepts(dens, g, kept))) return rc;
+    if (agr && (rc = agreement_accepts(agr, g, kept))) return rc;
     for (int64_t t = 1; t <= n_iter; ++t) {
         if ((rc = pmdi_gibbs_step(g, PMDI_STEP_BEGIN, stream)) || (rc = pmdi_gibbs_step(g, PMDI_STEP_HYPERS, stream)) ||
             (rc = pmdi_gibbs_step(g, PMDI_STEP_SWEEP, stream)))
@@ -1437,9 +1598,16 @@ int pmdi_gibbs_run7(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
             if (pred && (rc = pmdi_predict_add_gibbs(pred, g, stream))) return rc;
             if (loo && (rc = pmdi_loo_add_gibbs(loo, g, stream))) return rc;
             if (dens && (rc = pmdi_density_add_gibbs(dens, g, stream))) return rc;
+            if (agr && (rc = pmdi_agreement_add_gibbs(agr, g, stream))) return rc;
         }
     }
     return PMDI_OK;
+}
+
+int pmdi_gibbs_run7(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
+                    pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, pmdi_density *dens, void *stream)
+{
+    return pmdi_gibbs_run8(g, n_iter, burnin, thin, acc, summ, fus, mix, pred, loo, dens, nullptr, stream);
 }
 
 int pmdi_gibbs_run6(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,

@@ -484,3 +484,25 @@ struct DensityArgs {
 hipError_t pmdi_launch_density_add(const DensityArgs &a, hipStream_t stream);
 // best_val = -inf, best_t = -1 (the rest of a reset is memsets)
 hipError_t pmdi_launch_density_clear(const DensityArgs &a, hipStream_t stream);
+
+// One add of the streaming agreement accumulator (pmdi_agreement.hip): the allocations in the GibbsArgs layout, the reference
+// labellings, the per-add scratch and the accumulator's state.  Q = G + R K comparisons per chain: the G dataset pairs in the
+// order of Phi, then comparison G + r K + k = dataset k against reference r.
+struct AgreementArgs {
+    int C, K, N;                // chains, datasets, labels
+    int R, G, Q;                // reference labellings (0..8), K (K - 1) / 2 pairs, comparisons
+    int np;                     // n rounded up to a multiple of 32: the row stride of the label bytes
+    int gr[8];                  // classes of reference r: its largest class + 1 (1 when every class is unknown)
+    long long n;
+    const int *s;               // [C][K][n]  0-based labels
+    const unsigned char *ref;   // [R][np]    class bytes; 255 = unknown, and behind n
+    unsigned char *bytes;       // [C K][np]  scratch: this add's label bytes; 255 = no label
+    int *err;                   // set to 1 by a label outside 0..N-1
+    long long *last;            // [C][Q][7]  both, jl, px, py, hx, hy, n_q of the latest add
+    long long *rand_num;        // [C][Q]
+    double *ari_sum, *ari_sq;   // [C][Q]
+    long long *vi_sum, *mi_sum; // [C][Q]
+    long long *ari_hist;        // [Q][256]
+};
+// trace_row: this add's row [Q] of the trace, or null when the trace is full (or has no rows)
+hipError_t pmdi_launch_agreement_add(const AgreementArgs &a, double *trace_row, hipStream_t stream);

@@ -159,7 +159,14 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     log joint (trace, rhat), the highest-density state every chain visited (best, best_per_chain: candidates and starts for
     psm.best_sampled_allocation and minimise_expected_loss) and the Rao-Blackwellised feature relevance (feature_bayes_factor,
     feature_probs; featureSelect need not be on) -- is returned after the leave-one-out counts and before the draws:
-    (counts[, summary][, fusion][, mixing][, predict][, loo][, density][, draws])."""
+    (counts[, summary][, fusion][, mixing][, predict][, loo][, density][, draws]).
+    agreement (keyword only, default False): an eighth accumulator (agreement.AgreementAccumulator, one trace row per retained
+    iteration) takes the same retained iterations and its agreement.AgreementSummary -- the posterior mean of the adjusted Rand
+    index between the clusterings of every two datasets (ari_matrix, beside phi_matrix) and between every dataset's clustering and
+    known classes (against), with its R-hat, credible interval and trace -- is returned after the density result and before the
+    draws: (counts[, summary][, fusion][, mixing][, predict][, loo][, density][, agreement][, draws]).  True = the dataset pairs
+    (needs K > 1); an (n,) or (R, n) integer array of known classes 0..254, -1 where the class is unknown = the pairs and those
+    R <= 8 reference labellings (one dataset: the references alone); anything else is a ValueError."""
     from .fusion import FusionAccumulator, _group_masks
     fusion = more.pop("fusion", False)
     mixing = more.pop("mixing", False)
@@ -170,6 +177,7 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     loo = bool(more.pop("loo", False))
     loo_coupled = more.pop("loo_coupled", None)
     density = more.pop("density", False)
+    agreement = more.pop("agreement", False)
     if more:
         raise TypeError(f"pmdi_pooled() got an unexpected keyword argument {next(iter(more))!r}")
     from .psm import PsmAccumulator, _DeviceInt32View, retained_iterations
@@ -178,8 +186,17 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     from .predict import PredictiveAccumulator, check_new_rows
     from .loo import LooAccumulator
     from .density import DensityAccumulator
+    from .agreement import AgreementAccumulator, as_references
     K, n_obs, names = _check_arguments(dataFiles, dataTypes, N, particles, rho)
     _need(density is True or density is False, "density must be True or False")
+    agr_ref = None
+    if agreement is not False and agreement is not None:
+        if agreement is True:
+            _need(K > 1, "agreement=True compares the datasets with each other: it needs two or more (or give known classes)")
+        else:
+            _need(isinstance(agreement, (np.ndarray, list, tuple)), "agreement must be True or an (n,) or (R, n) integer array of known classes")
+            agr_ref = as_references(agreement, n_obs)
+        agreement = True
     if loo_coupled is not None and not loo:
         raise ValueError("loo_coupled needs loo=True")
     _need(K > 1 or not loo_coupled, "loo_coupled needs two or more datasets")
@@ -221,7 +238,7 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
         summ = SummaryAccumulator(n_chains, K, N, n_obs, sumD=sweeper.sumD if featureSelect else 0,
                                   trace_cap=len(retained_iterations(iter, burnin, thin)), device=device)
     fus = FusionAccumulator(K, n_obs, n_labels=N, groups=fusion_groups, matrix=fusion_matrix, device=device) if fusion else None
-    mix = pred = loo_acc = dens = None
+    mix = pred = loo_acc = dens = agr = None
     try:
         if maxlag:      # ((maxlag + 1) n_chains K n bytes: inside the try, so that a failed allocation still closes the handles)
             mix = MixingAccumulator(n_chains, K, N, n_obs, maxlag=maxlag, device=device)
@@ -231,7 +248,10 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
             loo_acc = LooAccumulator(sweeper, coupled=loo_coupled)
         if density:
             dens = DensityAccumulator(sweeper, trace_cap=len(retained_iterations(iter, burnin, thin)))
-        g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ, fusion=fus, mixing=mix, predict=pred, loo=loo_acc, density=dens)
+        if agreement:
+            agr = AgreementAccumulator(n_chains, K, N, n_obs, ref=agr_ref, trace_cap=len(retained_iterations(iter, burnin, thin)), device=device)
+        g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ, fusion=fus, mixing=mix, predict=pred, loo=loo_acc, density=dens,
+              agreement=agr)
         g.results()                      # synchronises; raises on a kernel-side error of any chain
         counts = acc.counts(names=names)   # (the view keeps the accumulator alive)
         out = (counts,) if summ is None else (counts, summ.summary(names=names, feature_D=sweeper.D))
@@ -245,6 +265,8 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
             out += (loo_acc.result(names=names),)
         if dens is not None:
             out += (dens.result(names=names),)
+        if agr is not None:
+            out += (agr.result(names=names),)
         if final_allocations:
             import torch
             dev = torch.device("cuda", int(device))
@@ -262,5 +284,7 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
             loo_acc.close()
         if dens is not None:
             dens.close()
+        if agr is not None:
+            agr.close()
         g.close()
         sweeper.close()
