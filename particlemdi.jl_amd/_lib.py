@@ -260,22 +260,9 @@ def lib():
     L.pmdi_psm_acc_samples.argtypes = [vp]
     L.pmdi_psm_acc_counts.restype = C.c_int
     L.pmdi_psm_acc_counts.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), vp]
-    L.pmdi_gibbs_run.restype = C.c_int
-    L.pmdi_gibbs_run.argtypes = [vp, i64, i64, i64, vp, vp]
-    L.pmdi_gibbs_run2.restype = C.c_int
-    L.pmdi_gibbs_run2.argtypes = [vp, i64, i64, i64, vp, vp, vp]
-    L.pmdi_gibbs_run3.restype = C.c_int
-    L.pmdi_gibbs_run3.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp]
-    L.pmdi_gibbs_run4.restype = C.c_int
-    L.pmdi_gibbs_run4.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp]
-    L.pmdi_gibbs_run5.restype = C.c_int
-    L.pmdi_gibbs_run5.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]
-    L.pmdi_gibbs_run6.restype = C.c_int
-    L.pmdi_gibbs_run6.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]
-    L.pmdi_gibbs_run7.restype = C.c_int
-    L.pmdi_gibbs_run7.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pmdi_gibbs_run8.restype = C.c_int
-    L.pmdi_gibbs_run8.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    for sinks, name in enumerate(("run", "run2", "run3", "run4", "run5", "run6", "run7", "run8"), 1):      # one more accumulator each
+        run = getattr(L, "pmdi_gibbs_" + name)
+        run.restype, run.argtypes = C.c_int, [vp, i64, i64, i64] + [vp] * sinks + [vp]
     L.pmdi_agreement_create.restype = C.c_int
     L.pmdi_agreement_create.argtypes = [i32, i32, i32, i32, i64, i32, vp, i64, C.POINTER(vp)]
     L.pmdi_agreement_destroy.argtypes = [vp]
@@ -833,11 +820,8 @@ class Gibbs(_Handle):
         `density` (a density.DensityAccumulator: the log density of the state) and to `agreement` (an
         agreement.AgreementAccumulator: how alike the datasets cluster, and how alike known classes) iff t > burnin and (t - burnin - 1) % thin == 0
         (psm.retained_iterations).  Any may be None."""
-        _check(lib().pmdi_gibbs_run8(self.h, int(n_iter), int(burnin), int(thin), acc.h if acc is not None else None,
-                                     summary.h if summary is not None else None, fusion.h if fusion is not None else None,
-                                     mixing.h if mixing is not None else None, predict.h if predict is not None else None,
-                                     loo.h if loo is not None else None, density.h if density is not None else None,
-                                     agreement.h if agreement is not None else None,
+        sinks = (acc, summary, fusion, mixing, predict, loo, density, agreement)      # the order of pmdi_gibbs_run8's arguments
+        _check(lib().pmdi_gibbs_run8(self.h, int(n_iter), int(burnin), int(thin), *(a.h if a is not None else None for a in sinks),
                                      C.c_void_p(stream) if stream else None))
 
     def pack_samples(self, out_ptr, stream=None):

@@ -2,8 +2,8 @@
 half-built object holds no handle, and close() -- once, twice -- and __del__ neither call the library's destroy function nor
 raise.  The invalid arguments are those of the classes' own validation tests (test_abi.py::
 test_argument_validation_happens_before_device_use and the test_create_validates_before_any_device_use of
-test_psm_acc_host.py, test_fusion_host.py, test_summary_host.py); Gibbs and ClusterBatch are given a sweeper without a handle,
-CsvWriter K = 0 and Comm a rank outside the communicator."""
+test_psm_acc_host.py, test_fusion_host.py, test_summary_host.py, test_mixing_host.py, test_agreement_host.py); Gibbs and
+ClusterBatch are given a sweeper without a handle, CsvWriter K = 0 and Comm a rank outside the communicator."""
 import types
 
 import numpy as np
@@ -23,6 +23,8 @@ CASES = {
     "PsmAccumulator": ("pmdi_psm_acc_destroy", lambda pkg: ((0, 10, 4), {})),
     "FusionAccumulator": ("pmdi_fusion_destroy", lambda pkg: ((1, 100, 12), {"groups": ((0, 1), (0, 1, 2))})),
     "SummaryAccumulator": ("pmdi_summary_destroy", lambda pkg: ((4, 2, 1, 100), {"sumD": 5, "trace_cap": 3})),
+    "MixingAccumulator": ("pmdi_mixing_destroy", lambda pkg: ((4, 2, 6, 100), {"maxlag": 1025})),
+    "AgreementAccumulator": ("pmdi_agreement_destroy", lambda pkg: ((4, 2, 6, 100), {"ref": np.full(100, 255), "trace_cap": 3})),
 }
 
 
