@@ -1191,6 +1191,81 @@ int pmdi_gibbs_run8(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
                     pmdi_fusion *fus, pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, pmdi_density *dens, pmdi_agreement *agr,
                     void *stream);
 
+/* ---- streaming relabelling accumulator: per-component allocation probabilities against a pivot clustering ----
+ * The ninth accumulator.  Labels are aligned across the K datasets of one state, not across chains: label 3 of one chain and
+ * label 3 of another are different clusters, so nothing indexed by label can be pooled.  For every retained state of every chain
+ * this finds the permutation sigma of the N labels that agrees best with a pivot clustering fixed in advance (the assignment step
+ * of Stephens 2000; ECR of Papastamoulis & Iliopoulos 2010), applies it and counts.  It reads no handle: C = n_chains, K datasets,
+ * N labels, n observations; one retained state of chain c is s[c][k][i] (0-based).
+ *   Pivot.  pivot [K][n] Int32 in -1..N-1; -1: the observation takes no part in the matching, but is counted in alloc like any
+ *     other.  Copied to the device as bytes (255 for -1).
+ *   Units.  shared = 1: one permutation per chain for all its datasets (U = 1), which keeps every event [c_a = c_b] intact;
+ *     shared = 0: one per (chain, dataset) (U = K, unit u = dataset u).
+ *   Table of chain c and unit u, exact Int32:  W[l][g] = sum over the unit's datasets k of #{i : s[c][k][i] = l, pivot[k][i] = g}.
+ *     A label of s outside 0..N-1 is in no cell, counts nowhere in alloc and sets the error flag.
+ *   Assignment.  sigma maximises sum_l W[l][sigma(l)] and is, among the maximisers, the one this loop finds -- Int64 throughout,
+ *     cost[l][g] = -W[l][g], potentials u[0..N-1] and v[0..N] all 0 at the start, p[j] = the row matched to column j or -1, column N
+ *     the dummy; rows are inserted in the order i = 0, 1, ..., N-1:
+ *       1. p[N] = i, j0 = N, minv[j] = +inf and used[j] = false for every j.
+ *       2. repeat until p[j0] = -1:
+ *            used[j0] = true, i0 = p[j0];
+ *            for the columns j < N that are not used, ascending: cur = cost[i0][j] - u[i0] - v[j]; if cur < minv[j]: minv[j] = cur, way[j] = j0;
+ *            delta = the smallest minv[j] over the columns j < N that are not used, j1 = the SMALLEST such j that attains it;
+ *            for every used j, the dummy included: u[p[j]] += delta, v[j] -= delta;  for every j < N not used: minv[j] -= delta;
+ *            j0 = j1.
+ *       3. repeat j1 = way[j0], p[j0] = p[j1], j0 = j1 until j0 = N.
+ *     At the end sigma(p[j]) = j for j < N; value = sum_l W[l][sigma(l)].  A plain loop in any language reproduces every
+ *     permutation bit for bit.  Where the cost matrix lives on the device (LDS up to N = 192, the table itself beyond) changes nothing.
+ *   State (every word owned by one lane of one launch; the launches ordered on the accumulator's stream: bit-defined by the order
+ *   of the adds):
+ *     alloc     [K][n][N] Int32    alloc[k][i][sigma_c(s[c][k][i])] += 1 for every chain c (sigma_c of the chain, or of its unit k)
+ *     match_sum [C][U] Int64       += value: the (observation, dataset) pairs of the unit that agree with the pivot after relabelling
+ *     moved     [C][U] Int64       += 1 when sigma(l) != l for some label l whose row of W is not all zero (a label some matched
+ *                                  observation of the unit carries in this state): the labels switched against the pivot
+ *     w_sum     [C][K][N] Float64  w_sum[c][k][sigma(l)] = w_sum[c][k][sigma(l)] + Pi[c][k][l]
+ *     w_sq      [C][K][N] Float64  w_sq[c][k][sigma(l)] = w_sq[c][k][sigma(l)] + Pi[c][k][l] * Pi[c][k][l], separate IEEE operations,
+ *                                  never fused, in the order of the adds; an add without Pi leaves both untouched
+ *     perm [C][U][N] UInt8, value [C][U] Int64   sigma and its value of the latest add (pmdi_relabel_last)
+ * create: checked before the device is touched (PMDI_E_ARG) -- 1 <= K <= PMDI_KMAX_I, 2 <= N <= 255, 1 <= n <= 65535,
+ *   n_chains >= 1, every pivot value in -1..N-1, shared 0 or 1.  `device` must exist (PMDI_E_DEVICE: no CPU path).
+ * set_pivot: another pivot [K][n] (values checked as in create), only while T = 0 (PMDI_E_STATE otherwise: the counts were matched
+ *   to the old one); synchronises `stream`.  An iterated relabelling resets, sets the hard clustering of the last pass and adds again.
+ * set_budget: the tables of a batch of chains are 4 U N^2 bytes per chain of scratch and stay within PMDI_RELABEL_BUDGET_BYTES
+ *   (at least one chain per batch); set_budget lowers that budget (tests: it never changes a result, only the number of launches).
+ * add_arrays: s, a device array [C][K][n] Int32; Pi, a device array [C][K][N] Float64 in the layout of pmdi_predict_add_arrays,
+ *   or NULL.  add_gibbs: the current allocations and Pi of every chain of g, which must have the accumulator's n_chains, K, N, n and
+ *   device (PMDI_E_ARG otherwise, nothing changed).  (T + 1) C must not pass INT32_MAX (PMDI_E_ARG): the bound of a count.
+ * get: SYNCHRONISES `stream`, then copies to the host arrays that are not NULL; PMDI_E_DATA (after the copies) if a label outside
+ *   0..N-1 was added since the last reset.  last: synchronises `stream` and copies perm and value (either may be NULL);
+ *   PMDI_E_STATE before the first add.  reset: every array of the state zero, T = 0; the pivot stays.
+ * samples: T, the number of adds (0 for NULL); destroy(NULL) is PMDI_OK; a NULL accumulator is PMDI_E_ARG everywhere else.
+ * There is no merge on the device: alloc of two accumulators with the same pivot is added on the host, the per-chain arrays are
+ * concatenated.
+ * assign_device: the solver alone, asynchronous on `stream`.  tables, a device array [B][N][N] Int32 of ANY values (that is why the
+ *   loop is Int64); perm [B][N] UInt8 and value [B] Int64, device arrays.  0 <= B <= INT32_MAX, 2 <= N <= 255 (PMDI_E_ARG).
+ * One device, not thread-safe, asynchronous on `stream` except create, destroy, set_pivot, get and last; all calls on one
+ * accumulator go on ONE stream. */
+#define PMDI_RELABEL_BUDGET_BYTES 268435456LL /* 2^28 */
+typedef struct pmdi_relabel pmdi_relabel;
+int pmdi_relabel_create(int32_t device, int32_t n_chains, int32_t K, int32_t N, int64_t n, const int32_t *pivot, int32_t shared,
+                        pmdi_relabel **out);
+int pmdi_relabel_destroy(pmdi_relabel *a);
+int pmdi_relabel_reset(pmdi_relabel *a, void *stream);
+int pmdi_relabel_set_pivot(pmdi_relabel *a, const int32_t *pivot, void *stream);
+int pmdi_relabel_set_budget(pmdi_relabel *a, int64_t bytes);
+int pmdi_relabel_add_gibbs(pmdi_relabel *a, pmdi_gibbs *g, void *stream);
+int pmdi_relabel_add_arrays(pmdi_relabel *a, const int32_t *s, const double *Pi, void *stream);
+int64_t pmdi_relabel_samples(const pmdi_relabel *a);          /* T, the number of adds */
+int pmdi_relabel_get(pmdi_relabel *a, int32_t *alloc, int64_t *match_sum, int64_t *moved, double *w_sum, double *w_sq, void *stream);
+int pmdi_relabel_last(pmdi_relabel *a, uint8_t *perm, int64_t *value, void *stream);
+int pmdi_relabel_assign_device(int32_t device, const int32_t *tables, int64_t B, int32_t N, uint8_t *perm, int64_t *value, void *stream);
+
+/* pmdi_gibbs_run8 with the ninth accumulator: after every retained local iteration acc, summ, fus, mix, pred, loo, dens, agr, then
+ * rel get their add; any may be NULL, and pmdi_gibbs_run8(g, ..., agr, stream) is pmdi_gibbs_run9(g, ..., agr, NULL, stream). */
+int pmdi_gibbs_run9(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ,
+                    pmdi_fusion *fus, pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, pmdi_density *dens, pmdi_agreement *agr,
+                    pmdi_relabel *rel, void *stream);
+
 /* Device pointers of the resident state (zero-copy consumers; layouts of pmdi_sweep_device). */
 typedef struct {
     double *M, *gamma, *gamma0, *Phi, *vZ, *Pi, *log1p_phi, *feature_prob, *logweight;

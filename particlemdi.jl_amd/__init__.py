@@ -29,3 +29,5 @@ from .predict import (  # noqa: F401,E402
 from .loo import LooAccumulator, LooCounts  # noqa: F401,E402
 from .density import DensityAccumulator, DensityResult  # noqa: F401,E402
 from .agreement import AgreementAccumulator, AgreementSummary  # noqa: F401,E402
+from .relabel import (  # noqa: F401,E402
+    AllocationProbabilities, RelabelAccumulator, allocation_probabilities, assign_labels)

@@ -13,7 +13,7 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("PMDI_LIB_PATH") or os.path.join(_PKG, "libpmdi_hip.so")   # override: A/B builds only
-_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_fusion.hip", "pmdi_summary.hip", "pmdi_mixing.hip", "pmdi_predict.hip", "pmdi_predict_coupled.hip", "pmdi_loo.hip", "pmdi_density.hip", "pmdi_agreement.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_psm_refine_vi.hip", "pmdi_partdist.hip", "pmdi_partdist_refine.hip", "pmdi_psm_blocksum.hip", "pmdi_data_groupsum.hip", "pmdi_api.cpp", "pmdi_plan.cpp", "pmdi_acc.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
+_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("pmdi_sweep.hip", "pmdi_sweep2.hip", "pmdi_kernels.hip", "pmdi_psm_acc.hip", "pmdi_fusion.hip", "pmdi_summary.hip", "pmdi_mixing.hip", "pmdi_predict.hip", "pmdi_predict_coupled.hip", "pmdi_loo.hip", "pmdi_density.hip", "pmdi_agreement.hip", "pmdi_relabel.hip", "pmdi_hypers.hip", "pmdi_hclust.hip", "pmdi_psm_score.hip", "pmdi_psm_rowscore.hip", "pmdi_psm_refine.hip", "pmdi_psm_refine_vi.hip", "pmdi_partdist.hip", "pmdi_partdist_refine.hip", "pmdi_psm_blocksum.hip", "pmdi_data_groupsum.hip", "pmdi_api.cpp", "pmdi_plan.cpp", "pmdi_acc.cpp", "pmdi_csv.cpp", "pmdi_comm.cpp")]
 # every header decides when to rebuild: a new one cannot be forgotten
 _HEADERS = sorted(glob.glob(os.path.join(_PKG, "csrc", "*.h"))) + [os.path.join(_ROOT, "include", "pmdi_hip.h")]
 
@@ -65,6 +65,9 @@ EXPORTS = [
     "pmdi_density_add_gibbs", "pmdi_density_add_arrays", "pmdi_density_get", "pmdi_density_last", "pmdi_gibbs_run7",
     "pmdi_agreement_create", "pmdi_agreement_destroy", "pmdi_agreement_reset", "pmdi_agreement_add_gibbs", "pmdi_agreement_add_arrays",
     "pmdi_agreement_samples", "pmdi_agreement_get", "pmdi_agreement_last", "pmdi_gibbs_run8",
+    "pmdi_relabel_create", "pmdi_relabel_destroy", "pmdi_relabel_reset", "pmdi_relabel_set_pivot", "pmdi_relabel_set_budget",
+    "pmdi_relabel_add_gibbs", "pmdi_relabel_add_arrays", "pmdi_relabel_samples", "pmdi_relabel_get", "pmdi_relabel_last",
+    "pmdi_relabel_assign_device", "pmdi_gibbs_run9",
 ]
 
 
@@ -260,7 +263,7 @@ def lib():
     L.pmdi_psm_acc_samples.argtypes = [vp]
     L.pmdi_psm_acc_counts.restype = C.c_int
     L.pmdi_psm_acc_counts.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), vp]
-    for sinks, name in enumerate(("run", "run2", "run3", "run4", "run5", "run6", "run7", "run8"), 1):      # one more accumulator each
+    for sinks, name in enumerate(("run", "run2", "run3", "run4", "run5", "run6", "run7", "run8", "run9"), 1):      # one more accumulator each
         run = getattr(L, "pmdi_gibbs_" + name)
         run.restype, run.argtypes = C.c_int, [vp, i64, i64, i64] + [vp] * sinks + [vp]
     L.pmdi_agreement_create.restype = C.c_int
@@ -278,6 +281,27 @@ def lib():
     L.pmdi_agreement_get.argtypes = [vp] + [vp] * 7 + [vp]
     L.pmdi_agreement_last.restype = C.c_int
     L.pmdi_agreement_last.argtypes = [vp, vp, vp]
+    L.pmdi_relabel_create.restype = C.c_int
+    L.pmdi_relabel_create.argtypes = [i32, i32, i32, i32, i64, vp, i32, C.POINTER(vp)]
+    L.pmdi_relabel_destroy.argtypes = [vp]
+    L.pmdi_relabel_reset.restype = C.c_int
+    L.pmdi_relabel_reset.argtypes = [vp, vp]
+    L.pmdi_relabel_set_pivot.restype = C.c_int
+    L.pmdi_relabel_set_pivot.argtypes = [vp, vp, vp]
+    L.pmdi_relabel_set_budget.restype = C.c_int
+    L.pmdi_relabel_set_budget.argtypes = [vp, i64]
+    L.pmdi_relabel_samples.restype = i64
+    L.pmdi_relabel_samples.argtypes = [vp]
+    L.pmdi_relabel_add_gibbs.restype = C.c_int
+    L.pmdi_relabel_add_gibbs.argtypes = [vp, vp, vp]
+    L.pmdi_relabel_add_arrays.restype = C.c_int
+    L.pmdi_relabel_add_arrays.argtypes = [vp, vp, vp, vp]
+    L.pmdi_relabel_get.restype = C.c_int
+    L.pmdi_relabel_get.argtypes = [vp] + [vp] * 5 + [vp]
+    L.pmdi_relabel_last.restype = C.c_int
+    L.pmdi_relabel_last.argtypes = [vp, vp, vp, vp]
+    L.pmdi_relabel_assign_device.restype = C.c_int
+    L.pmdi_relabel_assign_device.argtypes = [i32, vp, i64, i32, vp, vp, vp]
     L.pmdi_density_create.restype = C.c_int
     L.pmdi_density_create.argtypes = [vp, i64, i32, C.POINTER(vp)]
     L.pmdi_density_destroy.argtypes = [vp]
@@ -495,7 +519,8 @@ class _Handle:
 
 class _Accumulator(_Handle):
     """What the streaming accumulators (psm.PsmAccumulator, fusion.FusionAccumulator, summary.SummaryAccumulator, mixing.MixingAccumulator,
-    predict.PredictiveAccumulator, loo.LooAccumulator, density.DensityAccumulator, agreement.AgreementAccumulator) share: the
+    predict.PredictiveAccumulator, loo.LooAccumulator, density.DensityAccumulator, agreement.AgreementAccumulator,
+    relabel.RelabelAccumulator) share: the
     entry points `_prefix`_destroy / _reset / _add_gibbs / _samples, and every call on the current torch stream of `self.device`."""
 
     def _stream(self):
@@ -811,17 +836,18 @@ class Gibbs(_Handle):
                                         C.c_void_p(stream) if stream else None))
 
     def run(self, n_iter, burnin=0, thin=1, acc=None, stream=None, summary=None, fusion=None, mixing=None, predict=None, loo=None,
-            density=None, agreement=None):
-        """pmdi_gibbs_run8: n_iter iterations; after local iteration t = 1..n_iter the state of every chain is added to `acc` (a
+            density=None, agreement=None, relabel=None):
+        """pmdi_gibbs_run9: n_iter iterations; after local iteration t = 1..n_iter the state of every chain is added to `acc` (a
         psm.PsmAccumulator: the allocations), to `summary` (a summary.SummaryAccumulator: M, Phi, cluster counts, feature
         flags), to `fusion` (a fusion.FusionAccumulator: which observations the datasets cluster alike), to `mixing` (a
         mixing.MixingAccumulator: the autocorrelation inside every chain), to `predict` (a predict.PredictiveAccumulator:
         where held-out rows fall), to `loo` (a loo.LooAccumulator: how well every training row is explained by the others), to
-        `density` (a density.DensityAccumulator: the log density of the state) and to `agreement` (an
-        agreement.AgreementAccumulator: how alike the datasets cluster, and how alike known classes) iff t > burnin and (t - burnin - 1) % thin == 0
+        `density` (a density.DensityAccumulator: the log density of the state), to `agreement` (an
+        agreement.AgreementAccumulator: how alike the datasets cluster, and how alike known classes) and to `relabel` (a
+        relabel.RelabelAccumulator: the allocations under the labels of a pivot clustering) iff t > burnin and (t - burnin - 1) % thin == 0
         (psm.retained_iterations).  Any may be None."""
-        sinks = (acc, summary, fusion, mixing, predict, loo, density, agreement)      # the order of pmdi_gibbs_run8's arguments
-        _check(lib().pmdi_gibbs_run8(self.h, int(n_iter), int(burnin), int(thin), *(a.h if a is not None else None for a in sinks),
+        sinks = (acc, summary, fusion, mixing, predict, loo, density, agreement, relabel)      # the order of pmdi_gibbs_run9's arguments
+        _check(lib().pmdi_gibbs_run9(self.h, int(n_iter), int(burnin), int(thin), *(a.h if a is not None else None for a in sinks),
                                      C.c_void_p(stream) if stream else None))
 
     def pack_samples(self, out_ptr, stream=None):

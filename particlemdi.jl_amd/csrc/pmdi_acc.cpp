@@ -1,5 +1,5 @@
 // pmdi_acc.cpp -- the streaming accumulators of include/pmdi_hip.h (pmdi_psm_acc_*, pmdi_fusion_*, pmdi_summary_*, pmdi_mixing_*,
-// pmdi_predict_*, pmdi_loo_*, pmdi_density_*, pmdi_agreement_*) and their driver, the pmdi_gibbs_run family, which needs nothing
+// pmdi_predict_*, pmdi_loo_*, pmdi_density_*, pmdi_agreement_*, pmdi_relabel_*) and their driver, the pmdi_gibbs_run family, which needs nothing
 // of a pmdi_gibbs but the public pmdi_gibbs_step.  Every accumulator stands on one host base (Acc): what it owns on the device,
 // what reset zeroes, how many adds it holds, and the two operations the driver asks of it.
 #include "pmdi_host.h"
@@ -127,6 +127,16 @@ enum { AGR_RAND, AGR_ARI, AGR_ARISQ, AGR_VI, AGR_MI, AGR_HIST, AGR_TRACE, AGR_AR
 struct pmdi_agreement : SlabAcc {
     AgreementArgs aa{};                  // everything of an add but its source
     long long trace_cap = 0;
+    int accepts(const pmdi_gibbs *g, int64_t n_adds) const override;
+    int put(pmdi_gibbs *g, void *stream) override;
+};
+
+// Streaming relabelling accumulator (pmdi_relabel_* entry points).  One state region -- match_sum, moved, w_sum, w_sq (8-byte
+// elements), alloc, the error flag; the pivot bytes, the label bytes, the tables of a batch of chains and the latest add's perm,
+// value and moved flags are separate allocations
+struct pmdi_relabel : Acc {
+    RelabelArgs ra{};                    // everything of an add but its sources
+    unsigned char *pivot = nullptr;      // the device copy ra.pivot points to
     int accepts(const pmdi_gibbs *g, int64_t n_adds) const override;
     int put(pmdi_gibbs *g, void *stream) override;
 };
@@ -329,7 +339,7 @@ int slab_get(const SlabAcc *a, void *const *dst, int n, int N, const char *prefi
     return copy_out(a, out, n, a->err, N, prefix, "", stream);
 }
 
-// ---- what the accepts of the eight are made of --------------------------------------------------------------------------------------
+// ---- what the accepts of the nine are made of -----------------------------------------------------------------------------------------
 
 // the chains are as many and as large as the accumulator (summary, mixing, agreement) was created for
 int same_shape(int C, int K, int N, long long n, const pmdi_config &c)
@@ -415,7 +425,7 @@ int needs_impute(const pmdi_predict *a, const char *fn)
 
 }  // namespace
 
-// ---- accepts and put of the eight ------------------------------------------------------------------------------------------------------
+// ---- accepts and put of the nine ----------------------------------------------------------------------------------------------------------
 
 int pmdi_psm_acc::accepts(const pmdi_gibbs *g, int64_t n_adds) const { return ::accepts(this, "accumulator", g, n_adds); }
 
@@ -466,6 +476,20 @@ int pmdi_agreement::accepts(const pmdi_gibbs *g, int64_t n_adds) const
 int pmdi_agreement::put(pmdi_gibbs *g, void *stream)
 {
     return pmdi_agreement_add_arrays(this, g->ga.s, stream);
+}
+
+int pmdi_relabel::accepts(const pmdi_gibbs *g, int64_t n_adds) const
+{
+    if (const int rc = same_shape(ra.C, ra.K, ra.N, ra.n, g->h->cfg)) return rc;
+    if (g->h->cfg.device != device) return fail(PMDI_E_ARG, "the chains live on device %d, the accumulator on device %d", g->h->cfg.device, device);
+    if (n_adds > 2147483647LL / ra.C - T)
+        return fail(PMDI_E_ARG, "(%lld + %lld) adds x %d chains overflow the int32 counts", (long long)T, (long long)n_adds, ra.C);
+    return PMDI_OK;
+}
+
+int pmdi_relabel::put(pmdi_gibbs *g, void *stream)
+{
+    return pmdi_relabel_add_arrays(this, g->ga.s, g->ga.Pi, stream);
 }
 
 int pmdi_predict::accepts(const pmdi_gibbs *g, int64_t n_adds) const
@@ -1460,15 +1484,142 @@ int pmdi_agreement_last(pmdi_agreement *a, int64_t *last, void *stream)
     return PMDI_OK;
 }
 
+int pmdi_relabel_destroy(pmdi_relabel *a) { return release(a); }
+
+// the pivot [K][n] as the bytes [K][np] of the table kernel's y side: 255 for -1 and behind n; PMDI_E_ARG for a value outside -1..N-1
+static int pivot_bytes(const int32_t *pivot, int K, int N, long long n, int np, std::vector<unsigned char> *out)
+{
+    out->assign((size_t)K * np, (unsigned char)255);
+    for (int k = 0; k < K; ++k)
+        for (long long i = 0; i < n; ++i) {
+            const int v = pivot[(long long)k * n + i];
+            if (v < -1 || v >= N) return fail(PMDI_E_ARG, "pivot[%d][%lld]=%d outside -1..%d (-1: not part of the matching)", k, i, v, N - 1);
+            if (v >= 0) (*out)[(size_t)k * np + i] = (unsigned char)v;
+        }
+    return PMDI_OK;
+}
+
+int pmdi_relabel_create(int32_t device, int32_t n_chains, int32_t K, int32_t N, int64_t n, const int32_t *pivot, int32_t shared, pmdi_relabel **out)
+{
+    if (!out) return fail(PMDI_E_ARG, "null argument");
+    *out = nullptr;
+    if (K < 1 || K > PMDI_KMAX_I) return fail(PMDI_E_ARG, "K=%d outside 1..%d", K, PMDI_KMAX_I);
+    if (N < 2 || N > 255) return fail(PMDI_E_ARG, "N=%d outside 2..255", N);
+    if (n < 1 || n > 65535) return fail(PMDI_E_ARG, "n=%lld outside 1..65535", (long long)n);
+    if (n_chains < 1) return fail(PMDI_E_ARG, "n_chains=%d < 1", n_chains);
+    if (shared != 0 && shared != 1) return fail(PMDI_E_ARG, "shared=%d is neither 0 nor 1", shared);
+    if (!pivot) return fail(PMDI_E_ARG, "null argument");
+    const int np = (int)((n + 31) / 32 * 32), U = shared ? 1 : K;
+    std::vector<unsigned char> pb;
+    int rc = pivot_bytes(pivot, K, N, n, np, &pb);
+    if (rc || (rc = open_device(device))) return rc;
+    pmdi_relabel *a = new (std::nothrow) pmdi_relabel();
+    if (!a) return fail(PMDI_E_MEMORY, "out of host memory");
+    a->device = device;
+    RelabelArgs &p = a->ra;
+    p.C = n_chains; p.K = K; p.N = N; p.U = U; p.np = np; p.n = n;
+    // chains per batch: the stage buffer of one chain is its U tables of N x N int32; a batch stays within PMDI_RELABEL_BUDGET_BYTES
+    plan_batches(a, &p.Cb, 4LL * U * N * N, PMDI_RELABEL_BUDGET_BYTES, n_chains);
+    const size_t CU = (size_t)n_chains * U, CKN = (size_t)n_chains * K * N, KnN = (size_t)K * n * N;
+    char *state = nullptr;
+    rc = dev_state(a, &state, 16 * CU + 16 * CKN + 4 * KnN + 4);
+    if (!rc) rc = dev_alloc(a, &a->pivot, pb.size());
+    if (!rc) rc = dev_alloc(a, &p.bytes, (size_t)n_chains * K * np);
+    if (!rc) rc = dev_alloc(a, &p.tables, (size_t)p.Cb * U * N * N);
+    if (!rc) rc = dev_alloc(a, &p.perm, CU * N);
+    if (!rc) rc = dev_alloc(a, &p.value, CU);
+    if (!rc) rc = dev_alloc(a, &p.flag, CU);
+    if (rc) { release(a); return rc; }
+    if (hipMemcpy(a->pivot, pb.data(), pb.size(), hipMemcpyHostToDevice) != hipSuccess) { release(a); return fail(PMDI_E_DEVICE, "hipMemcpy failed"); }
+    p.pivot = a->pivot;
+    p.match_sum = (long long *)state;
+    p.moved = p.match_sum + CU;
+    p.w_sum = (double *)(p.moved + CU);
+    p.w_sq = p.w_sum + CKN;
+    p.alloc = (int *)(p.w_sq + CKN);
+    p.err = p.alloc + KnN;
+    *out = a;
+    return PMDI_OK;
+}
+
+int pmdi_relabel_reset(pmdi_relabel *a, void *stream) { return reset(a, stream); }
+
+int pmdi_relabel_set_pivot(pmdi_relabel *a, const int32_t *pivot, void *stream)
+{
+    if (!a || !pivot) return fail(PMDI_E_ARG, "null argument");
+    if (a->T != 0) return fail(PMDI_E_STATE, "pmdi_relabel_set_pivot: %lld adds were matched to the old pivot; pmdi_relabel_reset first", (long long)a->T);
+    const RelabelArgs &p = a->ra;
+    std::vector<unsigned char> pb;
+    if (const int rc = pivot_bytes(pivot, p.K, p.N, p.n, p.np, &pb)) return rc;
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipMemcpyAsync(a->pivot, pb.data(), pb.size(), hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));      // (pb goes with this call)
+    return PMDI_OK;
+}
+
+int pmdi_relabel_set_budget(pmdi_relabel *a, int64_t bytes) { return set_budget(a, bytes); }
+
+int pmdi_relabel_add_arrays(pmdi_relabel *a, const int32_t *s, const double *Pi, void *stream)
+{
+    if (!a || !s) return fail(PMDI_E_ARG, "null argument");
+    if (a->T >= 2147483647LL / a->ra.C) return fail(PMDI_E_ARG, "(%lld + 1) adds x %d chains overflow the int32 counts", (long long)a->T, a->ra.C);
+    HIP_TRY(hipSetDevice(a->device));
+    RelabelArgs p = a->ra;
+    p.s = s; p.Pi = Pi;
+    hipError_t e = pmdi_launch_relabel_add(p, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "relabel-add launch: %s", hipGetErrorString(e));
+    a->T += 1;
+    return PMDI_OK;
+}
+
+int pmdi_relabel_add_gibbs(pmdi_relabel *a, pmdi_gibbs *g, void *stream) { return add_gibbs(a, g, stream); }
+
+int64_t pmdi_relabel_samples(const pmdi_relabel *a) { return samples(a); }
+
+int pmdi_relabel_get(pmdi_relabel *a, int32_t *alloc, int64_t *match_sum, int64_t *moved, double *w_sum, double *w_sq, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    const RelabelArgs &p = a->ra;
+    const size_t cu8 = (size_t)p.C * p.U * 8, ckn8 = (size_t)p.C * p.K * p.N * 8;
+    const Out out[] = {{alloc, p.alloc, (size_t)p.K * p.n * p.N * 4}, {match_sum, p.match_sum, cu8}, {moved, p.moved, cu8}, {w_sum, p.w_sum, ckn8},
+                       {w_sq, p.w_sq, ckn8}};
+    return copy_out(a, out, 5, p.err, p.N, "relabel", "", stream);
+}
+
+int pmdi_relabel_last(pmdi_relabel *a, uint8_t *perm, int64_t *value, void *stream)
+{
+    if (!a) return fail(PMDI_E_ARG, "null argument");
+    if (a->T < 1) return fail(PMDI_E_STATE, "pmdi_relabel_last: nothing was added yet");
+    const RelabelArgs &p = a->ra;
+    HIP_TRY(hipSetDevice(a->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (perm) HIP_TRY(hipMemcpyAsync(perm, p.perm, (size_t)p.C * p.U * p.N, hipMemcpyDeviceToHost, st));
+    if (value) HIP_TRY(hipMemcpyAsync(value, p.value, (size_t)p.C * p.U * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PMDI_OK;
+}
+
+int pmdi_relabel_assign_device(int32_t device, const int32_t *tables, int64_t B, int32_t N, uint8_t *perm, int64_t *value, void *stream)
+{
+    if (B < 0 || B > 2147483647LL) return fail(PMDI_E_ARG, "B=%lld outside 0..INT32_MAX", (long long)B);
+    if (N < 2 || N > 255) return fail(PMDI_E_ARG, "N=%d outside 2..255", N);
+    if (B == 0) return PMDI_OK;
+    if (!tables || !perm || !value) return fail(PMDI_E_ARG, "null argument");
+    if (const int rc = open_device(device)) return rc;
+    hipError_t e = pmdi_launch_relabel_assign(tables, B, N, perm, (long long *)value, nullptr, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PMDI_E_DEVICE, "relabel-assign launch: %s", hipGetErrorString(e));
+    return PMDI_OK;
+}
+
 // The driver.  Every sink is asked before the first iteration whether all its adds will fit, so that a refusal costs no iteration;
 // after a retained iteration the sinks take the chains' state in the order of the arguments
-int pmdi_gibbs_run8(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
-                    pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, pmdi_density *dens, pmdi_agreement *agr, void *stream)
+int pmdi_gibbs_run9(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
+                    pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, pmdi_density *dens, pmdi_agreement *agr, pmdi_relabel *rel, void *stream)
 {
     if (!g || n_iter < 0) return fail(PMDI_E_ARG, "bad argument");
     if (burnin < 0 || thin < 1) return fail(PMDI_E_ARG, "burnin=%lld must be >= 0 and thin=%lld >= 1", (long long)burnin, (long long)thin);
     const int64_t kept = n_iter > burnin ? (n_iter - burnin - 1) / thin + 1 : 0;
-    Acc *const sinks[8] = {acc, summ, fus, mix, pred, loo, dens, agr};
+    Acc *const sinks[9] = {acc, summ, fus, mix, pred, loo, dens, agr, rel};
     int rc;
     for (const Acc *a : sinks)
         if (a && (rc = a->accepts(g, kept))) return rc;
@@ -1485,44 +1636,50 @@ int pmdi_gibbs_run8(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin,
     return PMDI_OK;
 }
 
+int pmdi_gibbs_run8(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
+                    pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, pmdi_density *dens, pmdi_agreement *agr, void *stream)
+{
+    return pmdi_gibbs_run9(g, n_iter, burnin, thin, acc, summ, fus, mix, pred, loo, dens, agr, nullptr, stream);
+}
+
 int pmdi_gibbs_run7(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
                     pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, pmdi_density *dens, void *stream)
 {
-    return pmdi_gibbs_run8(g, n_iter, burnin, thin, acc, summ, fus, mix, pred, loo, dens, nullptr, stream);
+    return pmdi_gibbs_run9(g, n_iter, burnin, thin, acc, summ, fus, mix, pred, loo, dens, nullptr, nullptr, stream);
 }
 
 int pmdi_gibbs_run6(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
                     pmdi_mixing *mix, pmdi_predict *pred, pmdi_loo *loo, void *stream)
 {
-    return pmdi_gibbs_run8(g, n_iter, burnin, thin, acc, summ, fus, mix, pred, loo, nullptr, nullptr, stream);
+    return pmdi_gibbs_run9(g, n_iter, burnin, thin, acc, summ, fus, mix, pred, loo, nullptr, nullptr, nullptr, stream);
 }
 
 int pmdi_gibbs_run5(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
                     pmdi_mixing *mix, pmdi_predict *pred, void *stream)
 {
-    return pmdi_gibbs_run8(g, n_iter, burnin, thin, acc, summ, fus, mix, pred, nullptr, nullptr, nullptr, stream);
+    return pmdi_gibbs_run9(g, n_iter, burnin, thin, acc, summ, fus, mix, pred, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int pmdi_gibbs_run4(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
                     pmdi_mixing *mix, void *stream)
 {
-    return pmdi_gibbs_run8(g, n_iter, burnin, thin, acc, summ, fus, mix, nullptr, nullptr, nullptr, nullptr, stream);
+    return pmdi_gibbs_run9(g, n_iter, burnin, thin, acc, summ, fus, mix, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int pmdi_gibbs_run3(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, pmdi_fusion *fus,
                     void *stream)
 {
-    return pmdi_gibbs_run8(g, n_iter, burnin, thin, acc, summ, fus, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+    return pmdi_gibbs_run9(g, n_iter, burnin, thin, acc, summ, fus, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int pmdi_gibbs_run2(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, pmdi_summary *summ, void *stream)
 {
-    return pmdi_gibbs_run8(g, n_iter, burnin, thin, acc, summ, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+    return pmdi_gibbs_run9(g, n_iter, burnin, thin, acc, summ, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int pmdi_gibbs_run(pmdi_gibbs *g, int64_t n_iter, int64_t burnin, int64_t thin, pmdi_psm_acc *acc, void *stream)
 {
-    return pmdi_gibbs_run8(g, n_iter, burnin, thin, acc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+    return pmdi_gibbs_run9(g, n_iter, burnin, thin, acc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 }  // extern "C"

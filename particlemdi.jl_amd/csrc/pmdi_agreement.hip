@@ -36,36 +36,14 @@ __device__ const int ag_table[AG_TABLE] = {
 };
 
 // Row `row` = chain * K + dataset of s [rows][n] into bytes out [rows][np] (np = n rounded up to 32; the bytes behind n are
-// MX_PAD), one wavefront per row, 4 rows per workgroup; a lane packs four consecutive labels into one aligned dword.  A label
-// outside 0..N-1 (a negative one is a large one) goes out as MX_PAD and sets *err.
+// MX_PAD), one wavefront per row, 4 rows per workgroup (mx_label_row).  A label outside 0..N-1 goes out as MX_PAD and sets *err.
 __global__ void __launch_bounds__(256) agreement_rows_kernel(const int *__restrict__ s, long long n_rows, long long n, int np, int N,
                                                              unsigned char *__restrict__ out, int *__restrict__ err)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long row = (long long)blockIdx.x * 4 + wave;
     if (row >= n_rows) return;                               // (the same in every lane of a wave; no barrier below)
-    const int *p = s + row * n;
-    unsigned *o = (unsigned *)(out + row * np);
-    unsigned bad = 0u;
-    const int nd = np >> 2;
-#pragma unroll 4
-    for (int j = lane; j < nd; j += 64) {
-        unsigned u[4], w = 0u;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {                        // every address is clamped into the row and the guard selects
-            const long long i = 4ll * j + b;                 // afterwards: no load sits under a branch
-            u[b] = (unsigned)p[i < n ? i : n - 1];
-        }
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const bool in_row = 4ll * j + b < n, ok = in_row && u[b] < (unsigned)N;
-            bad |= (in_row && !ok) ? 1u : 0u;
-            w |= (ok ? u[b] : MX_PAD) << (8 * b);
-        }
-        o[j] = w;
-    }
-    bad |= (unsigned)__shfl_xor((int)bad, 32); bad |= (unsigned)__shfl_xor((int)bad, 16); bad |= (unsigned)__shfl_xor((int)bad, 8);
-    bad |= (unsigned)__shfl_xor((int)bad, 4); bad |= (unsigned)__shfl_xor((int)bad, 2); bad |= (unsigned)__shfl_xor((int)bad, 1);
+    const bool bad = mx_label_row(s + row * n, n, np, N, (unsigned *)(out + row * np), lane);
     if (lane == 0 && bad) *err = 1;
 }
 

@@ -506,3 +506,29 @@ struct AgreementArgs {
 };
 // trace_row: this add's row [Q] of the trace, or null when the trace is full (or has no rows)
 hipError_t pmdi_launch_agreement_add(const AgreementArgs &a, double *trace_row, hipStream_t stream);
+
+// One add of the streaming relabelling accumulator (pmdi_relabel.hip): the source arrays in the GibbsArgs layouts, the pivot
+// bytes, the stage buffers and the accumulator's state.  U assignment units per chain: 1 (one permutation for the K datasets)
+// or K (one per dataset).
+struct RelabelArgs {
+    int C, K, N, U;             // chains, datasets, labels, units per chain
+    int np;                     // n rounded up to a multiple of 32: the row stride of the label bytes
+    int Cb;                     // chains per batch of tables
+    long long n;
+    const int *s;               // [C][K][n]  0-based labels
+    const double *Pi;           // [C][K][N], or null: w_sum and w_sq are left alone
+    const unsigned char *pivot; // [K][np]    pivot bytes; 255 = not part of the matching, and behind n
+    unsigned char *bytes;       // [C K][np]  scratch: this add's label bytes; 255 = no label
+    int *tables;                // [Cb][U][N][N]  scratch: the contingency tables of one batch of chains
+    unsigned char *perm;        // [C][U][N]  sigma of the latest add
+    long long *value;           // [C][U]     its optimal value
+    int *flag;                  // [C][U]     1: sigma moves an occupied label
+    int *err;                   // set to 1 by a label outside 0..N-1
+    int *alloc;                 // [K][n][N]
+    long long *match_sum, *moved;       // [C][U]
+    double *w_sum, *w_sq;       // [C][K][N]
+};
+hipError_t pmdi_launch_relabel_add(const RelabelArgs &a, hipStream_t stream);
+// the solver alone: tables [B][N][N], perm [B][N], value [B], moved [B] or null (device arrays)
+hipError_t pmdi_launch_relabel_assign(const int *tables, long long B, int N, unsigned char *perm, long long *value, int *moved, hipStream_t stream);
+int pmdi_relabel_tile(int N);   // observations per workgroup of the count kernel

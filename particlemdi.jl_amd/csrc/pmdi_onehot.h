@@ -1,7 +1,8 @@
 // pmdi_onehot.h -- what the kernels that form a contingency table as a product of one-hot int8 matrices share
-// (pmdi_mixing.hip: a chain against its own past; pmdi_partdist.hip: every candidate against every draw): the fragment types of
-// v_mfma_i32_32x32x32_i8, the padding byte, the ordering of one wave's LDS accesses, the exact 64-bit sum over a wave and the
-// byte compare that makes the one-hot fragments.  Device code only.
+// (pmdi_mixing.hip: a chain against its own past; pmdi_partdist.hip: every candidate against every draw; pmdi_agreement.hip: a
+// dataset against another or against known classes; pmdi_relabel.hip: a state against the pivot): the fragment types of
+// v_mfma_i32_32x32x32_i8, the padding byte, the ordering of one wave's LDS accesses, the exact 64-bit sum over a wave, the
+// byte compare that makes the one-hot fragments and the packing of a row of int32 labels into bytes.  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,6 +46,34 @@ __device__ __forceinline__ mx_v4i mx_onehot(mx_v4u w, unsigned rep, unsigned one
         f[d] = (int)(~nz & one);
     }
     return f;
+}
+
+// One wavefront turns row p [n] of int32 labels into bytes o [np] (np = n rounded up to 32; the bytes behind n are MX_PAD); a
+// lane packs four consecutive labels into one aligned dword.  A label outside 0..N-1 (a negative one is a large one) goes out
+// as MX_PAD; the result, the same in every lane, says whether the row held one.
+__device__ __forceinline__ bool mx_label_row(const int *__restrict__ p, long long n, int np, int N, unsigned *__restrict__ o, int lane)
+{
+    unsigned bad = 0u;
+    const int nd = np >> 2;
+#pragma unroll 4
+    for (int j = lane; j < nd; j += 64) {
+        unsigned u[4], w = 0u;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {                        // every address is clamped into the row and the guard selects
+            const long long i = 4ll * j + b;                 // afterwards: no load sits under a branch
+            u[b] = (unsigned)p[i < n ? i : n - 1];
+        }
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const bool in_row = 4ll * j + b < n, ok = in_row && u[b] < (unsigned)N;
+            bad |= (in_row && !ok) ? 1u : 0u;
+            w |= (ok ? u[b] : MX_PAD) << (8 * b);
+        }
+        o[j] = w;
+    }
+    bad |= (unsigned)__shfl_xor((int)bad, 32); bad |= (unsigned)__shfl_xor((int)bad, 16); bad |= (unsigned)__shfl_xor((int)bad, 8);
+    bad |= (unsigned)__shfl_xor((int)bad, 4); bad |= (unsigned)__shfl_xor((int)bad, 2); bad |= (unsigned)__shfl_xor((int)bad, 1);
+    return bad != 0u;
 }
 
 }  // namespace

@@ -166,7 +166,16 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     known classes (against), with its R-hat, credible interval and trace -- is returned after the density result and before the
     draws: (counts[, summary][, fusion][, mixing][, predict][, loo][, density][, agreement][, draws]).  True = the dataset pairs
     (needs K > 1); an (n,) or (R, n) integer array of known classes 0..254, -1 where the class is unknown = the pairs and those
-    R <= 8 reference labellings (one dataset: the references alone); anything else is a ValueError."""
+    R <= 8 reference labellings (one dataset: the references alone); anything else is a ValueError.
+    relabel (keyword only, default None): a pivot clustering, an (n,) or (K, n) integer array of labels 0..N-1 with -1 where the
+    observation takes no part in the matching (known classes, a consensus clustering, DensityResult.best() of an earlier run).  A
+    ninth accumulator (relabel.RelabelAccumulator) takes the same retained iterations, permutes the labels of every state to agree
+    best with the pivot and its relabel.AllocationProbabilities -- per observation the probability of every component (probabilities,
+    hard, confidence), the relabelled mixture weights with their R-hat, the share of every chain that matches the pivot and how
+    often the labels switched -- is returned after the agreement summary and before the draws:
+    (counts[, summary][, fusion][, mixing][, predict][, loo][, density][, agreement][, relabel][, draws]).
+    relabel_shared (keyword only, default True; needs relabel): one permutation per state for all K datasets, which keeps the
+    events [c_a = c_b] intact; False = one per dataset."""
     from .fusion import FusionAccumulator, _group_masks
     fusion = more.pop("fusion", False)
     mixing = more.pop("mixing", False)
@@ -178,6 +187,8 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     loo_coupled = more.pop("loo_coupled", None)
     density = more.pop("density", False)
     agreement = more.pop("agreement", False)
+    relabel = more.pop("relabel", None)
+    relabel_shared = more.pop("relabel_shared", None)
     if more:
         raise TypeError(f"pmdi_pooled() got an unexpected keyword argument {next(iter(more))!r}")
     from .psm import PsmAccumulator, _DeviceInt32View, retained_iterations
@@ -187,7 +198,15 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
     from .loo import LooAccumulator
     from .density import DensityAccumulator
     from .agreement import AgreementAccumulator, as_references
+    from .relabel import RelabelAccumulator, as_pivot
     K, n_obs, names = _check_arguments(dataFiles, dataTypes, N, particles, rho)
+    if relabel is None:
+        _need(relabel_shared is None, "relabel_shared needs relabel: the pivot clustering")
+    else:
+        _need(isinstance(relabel, (np.ndarray, list, tuple)), "relabel must be an (n,) or (K, n) integer array: the pivot clustering")
+        _need(relabel_shared is None or isinstance(relabel_shared, (bool, np.bool_)), "relabel_shared must be True or False")
+        relabel = as_pivot(relabel, K, n_obs, N)
+        relabel_shared = True if relabel_shared is None else bool(relabel_shared)
     _need(density is True or density is False, "density must be True or False")
     agr_ref = None
     if agreement is not False and agreement is not None:
@@ -238,7 +257,7 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
         summ = SummaryAccumulator(n_chains, K, N, n_obs, sumD=sweeper.sumD if featureSelect else 0,
                                   trace_cap=len(retained_iterations(iter, burnin, thin)), device=device)
     fus = FusionAccumulator(K, n_obs, n_labels=N, groups=fusion_groups, matrix=fusion_matrix, device=device) if fusion else None
-    mix = pred = loo_acc = dens = agr = None
+    mix = pred = loo_acc = dens = agr = rel = None
     try:
         if maxlag:      # ((maxlag + 1) n_chains K n bytes: inside the try, so that a failed allocation still closes the handles)
             mix = MixingAccumulator(n_chains, K, N, n_obs, maxlag=maxlag, device=device)
@@ -250,8 +269,10 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
             dens = DensityAccumulator(sweeper, trace_cap=len(retained_iterations(iter, burnin, thin)))
         if agreement:
             agr = AgreementAccumulator(n_chains, K, N, n_obs, ref=agr_ref, trace_cap=len(retained_iterations(iter, burnin, thin)), device=device)
+        if relabel is not None:
+            rel = RelabelAccumulator(n_chains, K, N, n_obs, relabel, shared=relabel_shared, device=device)
         g.run(iter, burnin=burnin, thin=thin, acc=acc, summary=summ, fusion=fus, mixing=mix, predict=pred, loo=loo_acc, density=dens,
-              agreement=agr)
+              agreement=agr, relabel=rel)
         g.results()                      # synchronises; raises on a kernel-side error of any chain
         counts = acc.counts(names=names)   # (the view keeps the accumulator alive)
         out = (counts,) if summ is None else (counts, summ.summary(names=names, feature_D=sweeper.D))
@@ -267,6 +288,8 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
             out += (dens.result(names=names),)
         if agr is not None:
             out += (agr.result(names=names),)
+        if rel is not None:
+            out += (rel.result(names=names),)
         if final_allocations:
             import torch
             dev = torch.device("cuda", int(device))
@@ -286,5 +309,7 @@ def pmdi_pooled(dataFiles, dataTypes, N, particles, rho, iter, n_chains, burnin=
             dens.close()
         if agr is not None:
             agr.close()
+        if rel is not None:
+            rel.close()
         g.close()
         sweeper.close()
